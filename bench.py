@@ -15,6 +15,11 @@ timed region.
 value = proposals (the reference's totalUpdates counter, GapsRunner.cpp:297,476) processed by all
 ranks in the timed region / max-over-ranks wall time.  Inputs are resident in HBM before the timed
 region starts (session creation uploads them).
+
+A plain run prints the headline line (with the roofline figures of its own timed region) and nothing
+else; `--full` adds the CPU baseline (the oracle port timed on the host on the same window, and the
+committed reference-build comparison).  `--dump-outputs DIR` writes what the timed chain computed --
+the run's result after its last step -- as DIR/<name>.npy (float32 / float64, at most 64 MB in all).
 """
 import argparse
 import json
@@ -29,6 +34,40 @@ sys.path.insert(0, ROOT)
 
 METRIC = "Gibbs atom proposals/sec, 20000x2000 dense D, nPatterns=50, at 1/2/4/8 GPUs"
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def session_outputs(S):
+    """what a caller of the timed path receives after its last step: the run's result (cogaps_session_finish: posterior means and
+    standard deviations, chi2 and atom-count histories, totals) and the factor matrices of the chain's current state"""
+    r = S.finish()
+    out = {k: r[k] for k in ("Amean", "Asd", "Pmean", "Psd")}
+    out["chisqHistory"] = r["chisq"].astype(np.float32)
+    out["atomHistoryA"] = r["atomsA"].astype(np.float64)
+    out["atomHistoryP"] = r["atomsP"].astype(np.float64)
+    out["totals"] = np.array([r["totalUpdates"], r["meanChiSq"], r["averageQueueLengthA"], r["averageQueueLengthP"]], dtype=np.float64)
+    out["A"] = S.matrix("A")
+    out["P"] = S.matrix("P")
+    return out
+
+
+def dump_outputs(dirname, outputs, budget=DUMP_BUDGET_BYTES):
+    """outputs: name -> array.  Written as DIR/<name>.npy in float32 (float64 where the array is wider).  When they would exceed the
+    budget, every array of more than 4096 elements keeps a fixed, seeded sample of its rows (the same rows on every run), so two
+    builds can still be compared output for output."""
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype.itemsize > 4 else np.float32) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        small = sum(a.nbytes for a in arrs.values() if a.size <= 4096)
+        frac = max(0.0, (budget - small) / float(total - small))
+        for k, a in arrs.items():
+            if a.size > 4096:
+                n = max(1, int(a.shape[0] * frac))
+                rows = np.sort(np.random.Generator(np.random.MT19937(20240)).choice(a.shape[0], size=n, replace=False))
+                arrs[k] = np.ascontiguousarray(a[rows])
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def synthetic_dense(n_genes, n_samples, rank=10, seed=12345):
@@ -203,7 +242,7 @@ def chains_main(args):
     phase(burn, W)
     upd = [0] * C
     # every chain's state at the start of the timed window, for the CPU comparator's like-for-like legs (copied out before the timed region)
-    cpu_states = None if args.no_cpu else [{"atomsA": s.atoms("A"), "A": s.rows("A"), "atomsP": s.atoms("P"), "P": s.rows("P")} for s in S]
+    cpu_states = None if (args.no_cpu or not args.full) else [{"atomsA": s.atoms("A"), "A": s.rows("A"), "atomsP": s.atoms("P"), "P": s.rows("P")} for s in S]
     perf0 = [{w: s.perf(w) for w in "AP"} for s in S]
     for b_ in BB:
         b_.set_timing(True)
@@ -279,6 +318,11 @@ def chains_main(args):
               "window_covered": covered}
         if cb["value"]:
             cb["gpu_over_cpu_same_window" if covered >= 1.0 else "gpu_over_cpu_partial_window"] = (sum(upd) / dt) / cb["value"]
+    if args.dump_outputs:
+        outs = {}
+        for c in range(C):
+            outs.update({"chain%d_%s" % (c, k): v for k, v in session_outputs(S[c]).items()})
+        dump_outputs(args.dump_outputs, outs)
     print(json.dumps({"metric": METRIC + " [informational: %d chains on one GPU, %s]" % (C, "batched multi-chain launches" if batched else "one thread and stream per chain"),
                       "value": sum(upd) / dt, "unit": "proposals/s",
                       "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": 1e3 * dt / K, "higher_is_better": True, "scaling": "weak",
@@ -320,7 +364,14 @@ def main():
     ap.add_argument("--samples", type=int, default=2000)
     ap.add_argument("--patterns", type=int, default=50)
     ap.add_argument("--cpu-seconds", type=float, default=64.0, help="time budget of the CPU baseline legs (the oracle port on this host: 8 / 16 / 24 / 32 OpenMP threads and one, from the GPU chain's state at the start of its timed window; a leg ends when it has covered the window).  N > 1 ranks, or --chains C: every shard's port run is made side by side -- one leg per shard, all at once, min(16, host threads / shards) threads each, 0.4 of the budget -- and the figure is their sum")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line's own figures, measure the CPU baseline (the oracle port on this host, --cpu-seconds) and "
+                         "quote the committed reference-build comparison; a plain run leaves them out (cpu_baseline: null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed chain computed (the run's result: Amean, Asd, Pmean, Psd, chi2 and atom "
+                         "histories, totals, and the factor matrices A and P) as DIR/<name>.npy; with N > 1 ranks as DIR/rank<r>_<name>.npy, with "
+                         "--chains C as DIR/chain<c>_<name>.npy")
     ap.add_argument("--sparse", action="store_true",
                     help="not the headline: the SparseNormalModel on the same product with 95 %% of the entries zeroed (BASELINE configs[4] "
                          "uses --genes 50000 --samples 12500 per GPU)")
@@ -330,6 +381,8 @@ def main():
     ap.add_argument("--chains-mode", choices=("batched", "threads"), default="batched")
     ap.add_argument("--chain-groups", type=int, default=1, help="with --chains: split the chains into this many batches, each driven by its own host thread and stream")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     # RCCL across processes needs dmabuf IPC on this driver (hipIpcGetMemHandle fails without it): set before torch / HIP initialise,
     # whoever launched the ranks (the driver's torch.distributed.run line never passes through self_launch)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -409,7 +462,8 @@ def main():
     run_steps(burn, W)
     # the chain state at the start of the timed window, for the CPU baseline's like-for-like sample (copied out before the timed region)
     cpu_state = None
-    if (rank == 0 or world > 1) and not args.no_cpu:      # (N > 1: every rank times the port on ITS shard, all at once: below)
+    with_cpu = args.full and not args.no_cpu
+    if (rank == 0 or world > 1) and with_cpu:      # (N > 1: every rank times the port on ITS shard, all at once: below)
         cpu_state = {"atomsA": S.atoms("A"), "A": S.rows("A"), "atomsP": S.atoms("P"), "P": S.rows("P")}
     perf0 = {w: S.perf(w) for w in "AP"}
     S.set_timing(True)
@@ -432,6 +486,13 @@ def main():
     S.set_timing(False)
     perf1 = {w: S.perf(w) for w in "AP"}
 
+    def dump():
+        if args.dump_outputs:
+            outs = session_outputs(S)
+            if world > 1:
+                outs = {"rank%d_%s" % (rank, k): v for k, v in outs.items()}
+            dump_outputs(args.dump_outputs, outs, DUMP_BUDGET_BYTES // world)
+
     tot_updates, max_dt, rank_seconds = float(updates), dt, [dt]
     if dist is not None:
         t = torch.tensor([float(updates), dt], dtype=torch.float64, device=comm_dev)
@@ -448,7 +509,7 @@ def main():
     # side, not extrapolated from one shard: every rank runs the port on its own shard's timed window at the same time (one leg,
     # min(16, host threads / ranks) OpenMP threads each, started behind a barrier), and the job's figure is the sum of the ranks' rates
     side_by_side = None
-    if world > 1 and not args.no_cpu:
+    if world > 1 and with_cpu:
         thr = max(1, min(16, (os.cpu_count() or 1) // world))
         dist.barrier()
         mine = cpu_baseline(data, params, args.cpu_seconds, cpu_state, burn + W, K, threads_only=thr)
@@ -590,7 +651,7 @@ def main():
                          "achieved_over_wall": (b_alg / 1e9) / dt, "frac_over_wall": (b_alg / 1e9) / dt / HBM_PEAK_GBS,
                          "kernels": kernels},
         }
-        if not args.no_cpu:
+        if with_cpu:
             if world > 1:
                 # measured above, all shards at once (round 4 multiplied rank 0's figure by nSets)
                 cb = dict(side_by_side["rank0"])
@@ -616,7 +677,10 @@ def main():
             out["cpu_baseline"] = cb
         else:
             out["cpu_baseline"] = None
+        dump()
         print(json.dumps(out))
+    else:
+        dump()
     S.close()
     if dist is not None:
         dist.destroy_process_group()

@@ -285,6 +285,26 @@ def test_native_subset_reader_reads_only_the_named_rows_or_columns(tmp_path, gis
         _capi.read_matrix_file(str(f), lib=L)
 
 
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_rows(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files; above the budget every large array keeps a fixed, seeded sample of its
+    rows -- the same rows on every run -- and the files stay within it"""
+    import bench
+    rng = np.random.default_rng(3)
+    outs = {"Amean": rng.random((20000, 50), dtype=np.float32), "hist": np.arange(20, dtype=np.uint32), "totals": np.array([1.5, 2.0])}
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    a = {f.name: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert np.array_equal(a["Amean.npy"], outs["Amean"]) and a["hist.npy"].dtype == np.float32 and a["totals.npy"].dtype == np.float64
+    budget = 1 << 20
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / ("s%d" % k)), outs, budget=budget)
+    s0 = {f.name: np.load(f) for f in (tmp_path / "s0").glob("*.npy")}
+    s1 = {f.name: np.load(f) for f in (tmp_path / "s1").glob("*.npy")}
+    assert sum(v.nbytes for v in s0.values()) <= budget and 0 < s0["Amean.npy"].shape[0] < 20000 and s0["Amean.npy"].shape[1] == 50
+    assert all(np.array_equal(s0[n], s1[n]) for n in s0) and np.array_equal(s0["hist.npy"], outs["hist"])
+    rows = [int(np.flatnonzero((outs["Amean"] == r).all(axis=1))[0]) for r in s0["Amean.npy"][:5]]
+    assert rows == sorted(rows)
+
+
 def test_bench_refuses_to_report_fewer_gpus_than_asked_for():
     """`python bench.py --gpus 2` without a launcher starts its own two ranks (torch.distributed.run, 127.0.0.1); where they cannot
     come up -- here: no GPU at all -- the command fails and prints NO bench line: never `n_gpus: 1` for `--gpus 2`"""

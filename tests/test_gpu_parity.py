@@ -689,7 +689,7 @@ def test_bench_multi_rank_path_on_one_gpu():
     env = dict(os.environ, COGAPS_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4",
-                          "--genes", "4000", "--samples", "400", "--patterns", "10", "--cpu-seconds", "8"],
+                          "--genes", "4000", "--samples", "400", "--patterns", "10", "--full", "--cpu-seconds", "8"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -783,7 +783,7 @@ def test_gwcogaps_driver_on_the_gpu(hip_lib, gist):
 
 
 def test_bench_lines_small_workload():
-    """bench.py end to end on a small workload: the default line carries roofline + cpu_baseline (the oracle port timed on
+    """bench.py end to end on a small workload: the --full line carries roofline + cpu_baseline (the oracle port timed on
     the host), `--chains` and `--sparse` print their informational lines"""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -795,7 +795,7 @@ def test_bench_lines_small_workload():
         js = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         assert len(js) == 1
         return json.loads(js[0])
-    d = line(["--cpu-seconds", "2"])
+    d = line(["--full", "--cpu-seconds", "2"])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["higher_is_better"] and d["dtype"] == "f32" and d["vs_baseline"] is None
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and r["traffic"] is None
@@ -807,6 +807,32 @@ def test_bench_lines_small_workload():
     assert line(["--no-cpu", "--chains", "2", "--chains-mode", "threads"])["value"] > 0
     s = line(["--no-cpu", "--sparse"])
     assert s["value"] > 0 and "sparse" in s["config"]["workload"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain bench.py run prints the headline line without the CPU baseline; --dump-outputs DIR writes the run's result after the
+    timed steps (float32 / float64 .npy files), and two runs with the same arguments write the same arrays"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--genes", "3000", "--samples", "300", "--patterns", "8", "--steps", "16", "--warmup", "4"]
+    runs = []
+    for k in range(2):
+        d_ = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + ["--dump-outputs", str(d_)], cwd=root, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1
+        d = json.loads(js[0])
+        assert d["steps"] == 16 and d["warmup"] == 4 and d["value"] > 0 and d["ms_per_step"] > 0 and d["cpu_baseline"] is None
+        assert abs(d["ms_per_step"] - d["config"]["timed_region_ms_rank0"] / 16) < 1e-6 * d["ms_per_step"]
+        runs.append({f.name: np.load(f) for f in sorted(d_.glob("*.npy"))})
+    a, b = runs
+    assert sorted(a) == sorted(b) and {"Amean.npy", "Asd.npy", "Pmean.npy", "Psd.npy", "A.npy", "P.npy", "chisqHistory.npy"} <= set(a)
+    assert a["Amean.npy"].shape == (3000, 8) and a["Pmean.npy"].shape == (300, 8) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    assert a["Amean.npy"].any() and a["totals.npy"][0] > 0
 
 
 def test_sccogaps_sparse_driver_on_the_gpu(hip_lib):

@@ -1,15 +1,16 @@
-import sys, ctypes as C, numpy as np, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/oracle')
+import os, sys, ctypes as C, numpy as np, time
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,R); sys.path.insert(0,os.path.join(R,'oracle'))
 import pyoracle as po
 from cogaps_amd import _capi
 win = sys.argv[1] if len(sys.argv)>1 else '256'
 which = sys.argv[2] if len(sys.argv)>2 else 'gist'
 niter = int(sys.argv[3]) if len(sys.argv)>3 else 40
-L = _capi.load() if win=='hip' else _capi.bind(C.CDLL('/root/repo/tests/emul/libcogaps_emul_TESTONLY_w%s.so'%win))
+L = _capi.load() if win=='hip' else _capi.bind(C.CDLL(os.path.join(R,'tests','emul','libcogaps_emul_TESTONLY_w%s.so'%win)))
 if which=='gist':
-    d = po.read_mtx('/root/repo/tests/golden/GIST.mtx'); K=7
+    d = po.read_mtx(os.path.join(R,'tests','golden','GIST.mtx')); K=7
 else:
-    d = np.loadtxt('/root/repo/tests/golden/modsimdata.csv', delimiter=',').astype(np.float32); K=3
+    d = np.loadtxt(os.path.join(R,'tests','golden','modsimdata.csv'), delimiter=',').astype(np.float32); K=3
 NI=max(niter,2)
 kw = dict(nPatterns=K, nIterations=NI, seed=42)
 S = _capi.Session(d, lib=L, **kw)

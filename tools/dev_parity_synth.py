@@ -1,9 +1,10 @@
-import sys, ctypes as C, numpy as np, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/oracle')
+import os, sys, ctypes as C, numpy as np, time
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,R); sys.path.insert(0,os.path.join(R,'oracle'))
 import pyoracle as po
 from cogaps_amd import _capi
 lib = sys.argv[1]; G=int(sys.argv[2]); Sm=int(sys.argv[3]); K=int(sys.argv[4]); niter=int(sys.argv[5])
-L = _capi.load() if lib=='hip' else _capi.bind(C.CDLL('/root/repo/tests/emul/libcogaps_emul_TESTONLY_w%s.so'%lib))
+L = _capi.load() if lib=='hip' else _capi.bind(C.CDLL(os.path.join(R,'tests','emul','libcogaps_emul_TESTONLY_w%s.so'%lib)))
 rng = np.random.default_rng(7)
 a0 = rng.gamma(2.0,0.5,(G,3))*(rng.random((G,3))>0.5); p0 = rng.gamma(2.0,0.5,(Sm,3))*(rng.random((Sm,3))>0.3)
 d = ((a0@p0.T)*(0.9+0.2*rng.random((G,Sm)))+0.01).astype(np.float32)

@@ -98,6 +98,55 @@ def run(binary, data, unc=None, subset=None, subsetDim=0, fixed="N", fixedFile=N
     return out
 
 
+def save_outputs(path, outputs):
+    """outputs: case name -> what run() returned.  Written as one .npz of plain arrays (the probe's printed values, no timings), so
+    that the tests can compare against the reference build's output where the reference sources are not at hand"""
+    arrs = {}
+    for name, ref in outputs.items():
+        p = name + "|"
+        if "dims" in ref:
+            arrs[p + "dims"] = np.array(ref["dims"], dtype=np.int64)
+        for k in ("atomsA", "atomsP"):
+            arrs[p + k] = np.asarray(ref[k], dtype=np.uint32)
+        arrs[p + "chisq"] = np.asarray(ref["chisq"], dtype=np.float32)
+        arrs[p + "totalUpdates"] = np.array(ref["totalUpdates"], dtype=np.int64)
+        for k in ("meanChiSq", "qA", "qP"):
+            arrs[p + k] = np.array(ref[k], dtype=np.float32)
+        for (n, r), v in ref["rows"].items():
+            arrs[p + "row|%s|%d" % (n, r)] = np.asarray(v, dtype=np.float32)
+        for n, (h, cnt) in ref["hashes"].items():
+            arrs[p + "hash|" + n] = np.array([h, cnt], dtype=np.uint64)
+        for k in ("snapE", "snapS"):
+            arrs[p + k] = np.array(ref[k], dtype=np.uint64).reshape(-1, 2)
+    np.savez_compressed(path, **arrs)
+
+
+def load_outputs(path):
+    """-> case name -> dict shaped as run() returns it (without the timings)"""
+    out = {}
+    with np.load(path) as z:
+        for key in z.files:
+            name, field = key.split("|", 1)
+            ref = out.setdefault(name, {"rows": {}, "hashes": {}})
+            v = z[key]
+            if field == "dims":
+                ref["dims"] = tuple(int(x) for x in v)
+            elif field == "totalUpdates":
+                ref[field] = int(v)
+            elif field in ("meanChiSq", "qA", "qP"):
+                ref[field] = np.float32(v)
+            elif field.startswith("row|"):
+                _, n, r = field.split("|")
+                ref["rows"][(n, int(r))] = v
+            elif field.startswith("hash|"):
+                ref["hashes"][field[5:]] = (int(v[0]), int(v[1]))
+            elif field in ("snapE", "snapS"):
+                ref[field] = [(int(a), int(b)) for a, b in v]
+            else:
+                ref[field] = v
+    return out
+
+
 def fnv_matrix(m):
     """the driver's hash: FNV-1a 64 over the float32 bit patterns, row-major, little-endian bytes"""
     h = 1469598103934665603

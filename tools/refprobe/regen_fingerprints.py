@@ -4,6 +4,8 @@
     python tools/refprobe/regen_fingerprints.py            # check every table entry except the two headline-sized ones
     python tools/refprobe/regen_fingerprints.py --all      # ... those as well (minutes)
     python tools/refprobe/regen_fingerprints.py --print NAME   # the probe's output for one entry, as the table would hold it
+    python tools/refprobe/regen_fingerprints.py --record   # write tests/golden/refprobe_outputs.npz: the probe's output for every
+                                                           # entry but the big ones and for the random configurations of the tests
 """
 import os
 import sys
@@ -17,6 +19,7 @@ sys.path[:0] = [HERE, ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "ora
 import refprobe as rp          # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+RECORD = os.path.join(GOLDEN, "refprobe_outputs.npz")
 
 
 def _synthetic(tmp, name, d):
@@ -101,6 +104,16 @@ def main():
             data, kw, _ = cs[name]
             ref = rp.run(binary, data, **kw)
             print(name, "atomsA=%s, atomsP=%s, totalUpdates=%d, meanChiSq=%.9g, qA=%.9g, qP=%.9g, lastChisq=%.9g" % (ref["atomsA"].tolist(), ref["atomsP"].tolist(), ref["totalUpdates"], ref["meanChiSq"], ref["qA"], ref["qP"], ref["chisq"][-1]))
+            return 0
+        if "--record" in sys.argv:
+            import test_oracle_pin as T
+            rec = {name: rp.run(binary, data, **kw) for name, (data, kw, _) in cs.items()}
+            for i in range(T.N_RANDOM_REFERENCE_CONFIGS):
+                sub = os.path.join(tmp, "random_%d" % i)
+                os.makedirs(sub)
+                rec["random_%d" % i] = T.run_reference_config(rp, binary, T.random_reference_config(i), sub)[0]
+            rp.save_outputs(RECORD, rec)
+            print("%d outputs -> %s (%d bytes)" % (len(rec), os.path.relpath(RECORD, ROOT), os.path.getsize(RECORD)))
             return 0
         bad = 0
         for name, (data, kw, fp) in cs.items():
