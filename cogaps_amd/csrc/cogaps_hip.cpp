@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <time.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #ifndef GEN_WIN
@@ -190,6 +191,54 @@ static const char *dev_env(const char *name)
 }
 static const uint32_t SEQ_SPARSE_GRID = 256;      // workgroups of the sparse model's verification-mode evaluation (one scratch region each)
 
+// Calls f(std::integral_constant<int, WIN>()) for the generator window `win`: the library's instantiations are GEN_WIN, GEN_WIN_HALF and,
+// for the sparse model's chained launch only (Wide), GEN_WIN_WIDE.
+template <bool Wide = false, class F> static void by_window(uint32_t win, F &&f)
+{
+    if constexpr (Wide && GEN_WIN_WIDE != GEN_WIN) if (win == (uint32_t)GEN_WIN_WIDE) return f(std::integral_constant<int, GEN_WIN_WIDE>());
+    if (win == (uint32_t)GEN_WIN) f(std::integral_constant<int, GEN_WIN>()); else f(std::integral_constant<int, GEN_WIN_HALF>());
+}
+
+// HIP-event timing of a sample of the launches: the start / stop events are attached to the kernel's own dispatch packet
+// (hipExtLaunchKernelGGL), so their difference is the dispatch's begin-to-end time, the figure rocprofv3 --kernel-trace reports; no extra
+// packets enter the stream.  Events are resolved after the chunk's synchronisation so that timing never stalls the queue.
+struct HostSampler;
+enum EvKind { EV_GEN, EV_EVAL, EV_EVAL2, EV_SYNC };      // generator launch, evaluation launch, second kernel of a split evaluation (the first's sample), sync launch
+struct EvSample { int kind; HostSampler *owner; uint64_t ord; };      // (owner, ord: a one-chain session's sampler and the batch step the launch belongs to)
+struct EventPool {
+    std::vector<rt_event_pair> ev; std::vector<EvSample> rec; size_t used = 0;
+    void create(size_t n) { if (ev.empty()) { ev.resize(n); rec.resize(n); for (auto &e : ev) rt_event_create(e); } }
+    ~EventPool() { for (auto &e : ev) rt_event_destroy(e); }
+    bool room(size_t n) const { return used + n <= ev.size(); }
+    int take(int kind, HostSampler *owner = nullptr, uint64_t ord = 0) { if (!room(1)) return -1; rec[used] = {kind, owner, ord}; return (int)used++; }
+    template <class F> void drain(F f) { for (size_t i = 0; i < used; ++i) f(rec[i], rt_event_ms(ev[i])); used = 0; }
+};
+#define LAUNCH_MAYBE_TIMED(stream, pool, slot, KERNEL, grid, block, ...) do { if ((slot) >= 0) RT_LAUNCH_TIMED(KERNEL, grid, block, stream, (pool).ev[slot], __VA_ARGS__); \
+    else RT_LAUNCH(KERNEL, grid, block, stream, __VA_ARGS__); } while (0)
+
+// A dependent kernel pair costs ~3.5 us per launch on the host and leaves a ~5 us bubble on the GPU when it is
+// launched call by call; replayed from a captured graph the same pair leaves ~1.6 us per kernel boundary.
+static const uint32_t GRAPH_PAIRS = 64;
+static_assert(GRAPH_PAIRS % 2u == 0u, "a replay must leave the chained launch's parity as it found it");
+// The captured runs of GRAPH_PAIRS batch steps of a one-chain sampler or of one side of a batch: the two-launch form, and the chained form
+// once per starting parity (consecutive chained launches alternate the parity they carry as a kernel argument).  A one-chain sampler's
+// kernels take their state through SamplerDev, so its graphs serve while the record they were captured with (`key`, rekey) stays the
+// sampler's; a batch's kernels take the address of its records' array, and its graphs are not keyed.
+struct GraphCache {
+    rt_graph pair, chain[2]; bool pairValid = false, chainValid[2] = {false, false};
+    SamplerDev key{};
+    void drop() { rt_graph_destroy(pair); rt_graph_destroy(chain[0]); rt_graph_destroy(chain[1]); pairValid = chainValid[0] = chainValid[1] = false; }
+    void rekey(const SamplerDev &d) { if (memcmp(&key, &d, sizeof(SamplerDev)) != 0) { drop(); memcpy(&key, &d, sizeof(SamplerDev)); } }
+    // replays the run of the given form (chained: the one starting at `parity`), captured first from GRAPH_PAIRS calls of `step` if it is
+    // missing (the caller undoes what the captured calls did to its launch counters)
+    template <class Step> void replay(rt_stream_t stream, bool chained, uint32_t parity, Step step)
+    {
+        rt_graph &g = chained ? chain[parity] : pair; bool &valid = chained ? chainValid[parity] : pairValid;
+        if (!valid) { rt_capture_begin(stream); for (uint32_t b = 0; b < GRAPH_PAIRS; ++b) step(); rt_capture_end(stream, g); valid = true; }
+        rt_graph_launch(g, stream);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 struct HostSampler {
     SamplerDev d;                 // device pointers + constants (passed by value to the kernels)
@@ -202,18 +251,15 @@ struct HostSampler {
     float dataSparsity = 0.f;     // DenseNormalModel::dataSparsity
     SamplerDev *dRecord = nullptr; SamplerDev recordHeld;   // `d` in device memory (the generator reads it through a pointer) and what that copy holds
     bool recordValid = false;
-    float stepsPerBatch = 0.f;
+    float stepsPerBatch = 0.f;    // proposals per batch in the last update (chunk-size predictor)
     uint32_t genWin = GEN_WIN;    // lanes of the generator launch (gen_window_for)
     float anneal = 1.f;           // annealing temperature of the next update
-    rt_graph graph;               // GRAPH_PAIRS (generate, evaluate) pairs, replayed while the kernel parameters stay the same
-    SamplerDev graphKey; bool graphValid = false;    // proposals per batch in the last update (chunk-size predictor)
-    // chained launch (chain_kernel.h): one launch per batch; consecutive launches alternate the parity they carry as a kernel argument, so
-    // a captured run of launches exists once per starting parity
+    GraphCache graphs;
+    // chained launch (chain_kernel.h): one launch per batch; consecutive launches alternate the parity they carry as a kernel argument
     bool chain = false; uint32_t chainParity = 0;
     uint32_t chainParityStart = 0;      // parity of the current update's first chained launch (which copy a given launch of the update evaluated)
     bool chainOff = false; uint32_t chainRecoveries = 0;      // a hand-over inside a chained launch never arrived: the batch was completed by chain_recover, the sampler keeps two launches per batch from then on
     unsigned long long *chainGrans = nullptr;      // [queueCap][CHAIN_GRAN_STRIDE] the decisions' granules (the split form's per-slice totals keep SamplerDev::grans)
-    rt_graph chainGraph[2]; bool chainGraphValid[2] = {false, false};
     size_t traceCap = 0;
     char name = 'A';
     // perf accounting
@@ -249,7 +295,7 @@ struct cogaps_session {
     unsigned statUpdates = 0;
     std::vector<float> chisqHist; std::vector<uint32_t> atomHistA, atomHistP;
     uint64_t totalUpdates = 0; double samplerSeconds = 0; double syncMs = 0; uint64_t syncTimed = 0, syncBytes = 0;
-    bool timing = false; bool evInit = false;
+    bool timing = false;
     bool noGraph = getenv("COGAPS_NO_GRAPH") != nullptr;     // diagnostics: every launch as a plain call (counter collection tools)
     bool noChain = getenv("COGAPS_NO_CHAIN") != nullptr;     // A/B and tests: two launches per batch (gen_kernel, eval_kernel<EVAL_FUSED>) where the chained launch would serve
     // The split evaluation inside the chained launch (EVAL_CHAIN_SPLIT) is built, tested on the hardware and NOT the default: measured on the
@@ -260,7 +306,7 @@ struct cogaps_session {
     bool testWideWindow = getenv("COGAPS_TEST_WIDE_WINDOW") != nullptr;      // tests: the sparse model's chained launch at GEN_WIN_WIDE from the first update on (otherwise once batches exceed 0.9 * GEN_WIN)
     bool forceChain = getenv("COGAPS_FORCE_CHAIN") != nullptr;      // tests: the chained launch also where the device shows fewer compute units than the launch has workgroups (they then run in turns, the generator last)
     unsigned computeUnits = 0;      // of the session's device: the chained launch wants all its workgroups resident at once, one per compute unit
-    std::vector<rt_event_pair> evPool; std::vector<int> evKind; std::vector<HostSampler *> evOwner; std::vector<uint64_t> evOrd; size_t evUsed = 0;
+    EventPool ev;
     GenScalars *hGs = nullptr;    // pinned staging
     bool poisoned = false;        // a device error ended an update half way (capacity, a hand-over inside a launch that never arrived): the chain's state is not a state of the chain
 };
@@ -428,9 +474,12 @@ static void seed_take(cogaps_session *s, uint64_t *dst, size_t n)
     for (size_t i = k; i < n; ++i) dst[i] = s->seeder.next();
     if (s->seedHead == s->seedFifo.size()) { s->seedFifo.clear(); s->seedHead = 0; }
 }
-// look ahead until `target` outputs are waiting (called while the GPU works through a chunk of launches)
-static void seed_top_up(cogaps_session *s, size_t target)
+// look ahead while the GPU works through a chunk of launches: the seeds of the next update, the other sampler's (about one per atom it
+// holds; Poisson spread + margin)
+static void seed_top_up(cogaps_session *s, const HostSampler &next)
 {
+    const uint32_t na = std::max(next.nAtoms, 10u);
+    const size_t target = (size_t)na + (size_t)(6.0 * sqrt((double)na)) + 64u;
     size_t avail = s->seedFifo.size() - s->seedHead;
     if (avail >= target) return;
     if (s->seedHead) { s->seedFifo.erase(s->seedFifo.begin(), s->seedFifo.begin() + (ptrdiff_t)s->seedHead); s->seedHead = 0; }
@@ -458,32 +507,24 @@ static void grow_atoms(cogaps_session *s, HostSampler &h, uint32_t need)
     build_death_prob_table(s, d);
 }
 
-// HIP-event timing of a sample of the launches (every 8th): the start / stop events are attached to the kernel's
-// own dispatch packet (hipExtLaunchKernelGGL), so their difference is the dispatch's begin-to-end time, the
-// figure rocprofv3 --kernel-trace reports; no extra packets enter the stream.  Events are resolved after the
-// chunk's synchronisation so that timing never stalls the queue.
+// A one-chain session times every 8th generator / evaluation launch (and every sync launch) of its plain launches
 static int timing_slot(cogaps_session *s, HostSampler &h, int kind, uint64_t ordinal)
 {
-    if (!s->timing || (kind != 4 && (ordinal % 8) != 0) || s->evUsed >= s->evPool.size()) return -1;
-    const int i = (int)s->evUsed++;
-    s->evKind[i] = kind; s->evOwner[i] = &h; s->evOrd[i] = h.updLaunches;
-    return i;
+    if (!s->timing || (kind != EV_SYNC && (ordinal % 8) != 0)) return -1;
+    return s->ev.take(kind, &h, h.updLaunches);
 }
 // `realBatches` = batches the current update has generated so far: pair number k processed a batch iff k < realBatches
 static void timing_resolve(cogaps_session *s, uint64_t realBatches)
 {
-    for (size_t i = 0; i < s->evUsed; ++i) {
-        const float ms = rt_event_ms(s->evPool[i]);
-        HostSampler *h = s->evOwner[i];
-        const bool real = s->evOrd[i] < realBatches;
-        if (s->evKind[i] == 0) { if (real) { h->genMs += ms; h->genTimed++; } else { h->genNoopMs += ms; h->genNoopTimed++; } }
-        else if (s->evKind[i] == 1) { if (real) { h->evalMs += ms; h->evalTimed++; } else { h->evalNoopMs += ms; h->evalNoopTimed++; } }
-        else if (s->evKind[i] == 4) { s->syncMs += ms; s->syncTimed++; }     // sync (AP transpose / lookup tables): every launch is timed
-        else { if (real) h->evalMs += ms; else h->evalNoopMs += ms; }      // second kernel of a split evaluation: same sample as the first
-    }
-    s->evUsed = 0;
+    s->ev.drain([&](const EvSample &e, float ms) {
+        HostSampler *h = e.owner;
+        const bool real = e.ord < realBatches;
+        if (e.kind == EV_GEN) { if (real) { h->genMs += ms; h->genTimed++; } else { h->genNoopMs += ms; h->genNoopTimed++; } }
+        else if (e.kind == EV_EVAL) { if (real) { h->evalMs += ms; h->evalTimed++; } else { h->evalNoopMs += ms; h->evalNoopTimed++; } }
+        else if (e.kind == EV_SYNC) { s->syncMs += ms; s->syncTimed++; }     // sync (AP transpose / lookup tables): every launch is timed
+        else { if (real) h->evalMs += ms; else h->evalNoopMs += ms; }
+    });
 }
-#define LAUNCH_MAYBE_TIMED(slot, KERNEL, grid, block, ...) do { if ((slot) >= 0) RT_LAUNCH_TIMED(KERNEL, grid, block, s->stream, s->evPool[slot], __VA_ARGS__); else RT_LAUNCH(KERNEL, grid, block, s->stream, __VA_ARGS__); } while (0)
 // The generator reads the sampler's record from device memory (gen_populate.h: a by-value SamplerDev made the compiler open the kernel
 // with seven serial scalar-cache misses).  The copy is refreshed, on the session's stream, whenever the host's record changed.
 static void sync_record(cogaps_session *s, HostSampler &h)
@@ -533,7 +574,7 @@ static void split_geometry(const HostSampler &h, uint32_t &bs, uint32_t &slices)
 }
 static void launch_chain(cogaps_session *s, HostSampler &h)
 {
-    const int slot = timing_slot(s, h, 1, h.evalLaunches);
+    const int slot = timing_slot(s, h, EV_EVAL, h.evalLaunches);
     const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
     const uint32_t parity = h.chainParity; h.chainParity ^= 1u;
     if (h.d.sparse) {
@@ -546,65 +587,67 @@ static void launch_chain(cogaps_session *s, HostSampler &h)
 #else
         const uint32_t grid = std::min<uint32_t>(h.d.queueCap, s->computeUnits >= 256u ? 255u : CHAIN_EVAL_GRID) + 1u;
 #endif
-        const bool wide = h.d.Wn > cogaps_sparse_width(h.d.N), big = h.genWin == (uint32_t)GEN_WIN;
-        if (GEN_WIN_WIDE != GEN_WIN && h.genWin == (uint32_t)GEN_WIN_WIDE) {
-            if (wide) LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN_WIDE, true>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-            else LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN_WIDE, false>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-        }
-        else if (big && wide) LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN, true>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-        else if (big) LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN, false>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-        else if (wide) LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN_HALF, true>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-        else LAUNCH_MAYBE_TIMED(slot, (chain_sparse_kernel<GEN_WIN_HALF, false>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-    } else if (h.d.redW > 1024u) {
-        // split evaluation: the evaluation workgroups are a multiple of the slices per proposal (chain_kernel.h)
-        uint32_t bs, slices; split_geometry(h, bs, slices);
-        const uint32_t groups = std::max<uint32_t>(1u, std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID / slices));
-        const uint32_t grid = groups * slices + 1u;
-        if (h.genWin == (uint32_t)GEN_WIN) LAUNCH_MAYBE_TIMED(slot, (chain_kernel<GEN_WIN, true>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
-        else LAUNCH_MAYBE_TIMED(slot, (chain_kernel<GEN_WIN_HALF, true>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
-#if defined(COGAPS_EMUL)
-        RT_LAUNCH(chain_updates_kernel, 5, bs, s->stream, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);      // (test-only emulator: the updates behind the launch)
-#endif
+        const bool wide = h.d.Wn > cogaps_sparse_width(h.d.N);
+        by_window<true>(h.genWin, [&](auto W) {
+            constexpr int WIN = decltype(W)::value;
+            if (wide) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_sparse_kernel<WIN, true>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
+            else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_sparse_kernel<WIN, false>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
+        });
     } else {
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID) + 1u;
-        if (h.genWin == (uint32_t)GEN_WIN) LAUNCH_MAYBE_TIMED(slot, (chain_kernel<GEN_WIN, false>), grid, h.d.redW, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, 1u, rec);
-        else LAUNCH_MAYBE_TIMED(slot, (chain_kernel<GEN_WIN_HALF, false>), grid, h.d.redW, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, 1u, rec);
+        // the fused evaluation, or the split one (data vectors of more than 4096 elements): then the evaluation workgroups are a multiple of
+        // the slices per proposal (chain_kernel.h)
+        const bool split = h.d.redW > 1024u;
+        uint32_t bs = h.d.redW, slices = 1u;
+        if (split) split_geometry(h, bs, slices);
+        const uint32_t groups = split ? std::max<uint32_t>(1u, std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID / slices)) : std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID);
+        const uint32_t grid = groups * slices + 1u;
+        // (one kernel per window dispatch: the kernels are instantiated, and laid out in the code object, in the order they appear here)
+        if (split) by_window(h.genWin, [&](auto W) {
+            constexpr int WIN = decltype(W)::value;
+            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_kernel<WIN, true>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
+        });
+        else by_window(h.genWin, [&](auto W) {
+            constexpr int WIN = decltype(W)::value;
+            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_kernel<WIN, false>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
+        });
+#if defined(COGAPS_EMUL)
+        if (split) RT_LAUNCH(chain_updates_kernel, 5, bs, s->stream, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);      // (test-only emulator: the updates behind the launch)
+#endif
     }
     h.evalLaunches++;      // (one launch per batch: counted with the evaluation launches, as its time is)
 }
 static void launch_gen(cogaps_session *s, HostSampler &h)
 {
-    const int slot = timing_slot(s, h, 0, h.genLaunches);
+    const int slot = timing_slot(s, h, EV_GEN, h.genLaunches);
     const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
-    if (split_one_launch(h)) {
-        const uint32_t grid = 1u + apply_grid();
-        if (h.genWin == (uint32_t)GEN_WIN) LAUNCH_MAYBE_TIMED(slot, gen_apply_kernel<GEN_WIN>, grid, GEN_WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
-        else LAUNCH_MAYBE_TIMED(slot, gen_apply_kernel<GEN_WIN_HALF>, grid, GEN_WIN_HALF + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
-        h.genLaunches++;
-        return;
-    }
-    if (h.genWin == (uint32_t)GEN_WIN) LAUNCH_MAYBE_TIMED(slot, gen_kernel<GEN_WIN>, 1, GEN_WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
-    else LAUNCH_MAYBE_TIMED(slot, gen_kernel<GEN_WIN_HALF>, 1, GEN_WIN_HALF + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
+    if (split_one_launch(h)) by_window(h.genWin, [&](auto W) {      // (the one-launch split evaluation's A*P updates: further workgroups of this launch)
+        constexpr int WIN = decltype(W)::value;
+        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, gen_apply_kernel<WIN>, 1u + apply_grid(), WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
+    });
+    else by_window(h.genWin, [&](auto W) {
+        constexpr int WIN = decltype(W)::value;
+        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, gen_kernel<WIN>, 1, WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
+    });
     h.genLaunches++;
 }
 static void launch_eval(cogaps_session *s, HostSampler &h)
 {
-    const int slot = timing_slot(s, h, 1, h.evalLaunches);
+    const int slot = timing_slot(s, h, EV_EVAL, h.evalLaunches);
     const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;      // (kept current by sync_record, as for the generator)
     if (h.d.seq) {
         // verification mode: one workgroup per proposal whatever the vector length, sums in the reference's order
-        if (h.d.sparse) LAUNCH_MAYBE_TIMED(slot, eval_sparse_seq_kernel, std::min<uint32_t>(h.d.queueCap, SEQ_SPARSE_GRID), cogaps_sparse_width(h.d.N), h.d);
-        else LAUNCH_MAYBE_TIMED(slot, eval_kernel<EVAL_SEQ>, std::min<uint32_t>(h.d.queueCap, 512u), EVAL_SEQ_BS, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
+        if (h.d.sparse) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_seq_kernel, std::min<uint32_t>(h.d.queueCap, SEQ_SPARSE_GRID), cogaps_sparse_width(h.d.N), h.d);
+        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_SEQ>, std::min<uint32_t>(h.d.queueCap, 512u), EVAL_SEQ_BS, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
     } else if (h.d.sparse) {
         const uint32_t grid = std::min<uint32_t>(h.d.queueCap, 1024u);
         const uint32_t W = cogaps_sparse_width(h.d.N);
-        if (h.d.Wn > W) LAUNCH_MAYBE_TIMED(slot, eval_sparse_kernel_wide, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);      // several rounds of flag words per vector
-        else LAUNCH_MAYBE_TIMED(slot, eval_sparse_kernel, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);
+        if (h.d.Wn > W) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_kernel_wide, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);      // several rounds of flag words per vector
+        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_kernel, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);
     } else if (h.d.redW <= 1024u) {
         // one workgroup of W threads per proposal
         static const uint32_t fusedGrid = dev_env("COGAPS_FUSED_GRID") ? (uint32_t)atoi(dev_env("COGAPS_FUSED_GRID")) : 512u;      // dev builds: A/B of the launch size
         const uint32_t grid = std::min<uint32_t>(h.d.queueCap, fusedGrid);
-        LAUNCH_MAYBE_TIMED(slot, eval_kernel<EVAL_FUSED>, grid, h.d.redW, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
+        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_FUSED>, grid, h.d.redW, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
     } else {
         // long data vectors: `slices` workgroups of `bs` threads per proposal, alpha kernel then apply kernel
         // (512 threads fill the machine a little better than 1024; at most 16 slices fit the partials record)
@@ -614,22 +657,16 @@ static void launch_eval(cogaps_session *s, HostSampler &h)
         if (split_one_launch(h)) {
             // one launch: the slices' totals reach the proposal's last slice workgroup inside it (eval_kernel.h, EVAL_DECIDE); the A*P updates
             // follow beside the next generator launch (launch_gen)
-            LAUNCH_MAYBE_TIMED(slot, eval_kernel<EVAL_DECIDE>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
+            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_DECIDE>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
         } else {
-            int slot2 = -1;
-            if (slot >= 0 && s->evUsed < s->evPool.size()) { slot2 = (int)s->evUsed++; s->evKind[slot2] = 3; s->evOwner[slot2] = &h; s->evOrd[slot2] = h.updLaunches; }
-            LAUNCH_MAYBE_TIMED(slot, eval_kernel<EVAL_ALPHA>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
-            LAUNCH_MAYBE_TIMED(slot2, eval_kernel<EVAL_APPLY>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
+            const int slot2 = slot >= 0 ? s->ev.take(EV_EVAL2, &h, h.updLaunches) : -1;
+            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_ALPHA>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
+            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot2, eval_kernel<EVAL_APPLY>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
         }
     }
     h.evalLaunches++;
 }
 
-// A dependent kernel pair costs ~3.5 us per launch on the host and leaves a ~5 us bubble on the GPU when it is
-// launched call by call; replayed from a captured graph the same pair leaves ~1.6 us per kernel boundary.  The
-// kernels take their whole state through SamplerDev (by value), so one graph serves until a pointer in it
-// changes (atom arrays regrown, seed buffer reallocated).
-static const uint32_t GRAPH_PAIRS = 64;
 static bool chain_eligible(const cogaps_session *s, const HostSampler &h)
 {
     // (a device with fewer compute units than the launch has workgroups -- a partitioned GPU -- would run them in turns, the generator
@@ -655,40 +692,12 @@ static void launch_pair(cogaps_session *s, HostSampler &h)
 {
     if (h.chain) launch_chain(s, h); else { launch_gen(s, h); launch_eval(s, h); }
 }
-static void drop_graphs(HostSampler &h)
+// the generator window for the coming update (stepsPerBatch = 0: none measured yet) or the next one; the captured launches carry the window
+static void retune_window(cogaps_session *s, HostSampler &h, float stepsPerBatch)
 {
-    if (h.graphValid) { rt_graph_destroy(h.graph); h.graphValid = false; }
-    for (int k = 0; k < 2; ++k) if (h.chainGraphValid[k]) { rt_graph_destroy(h.chainGraph[k]); h.chainGraphValid[k] = false; }
-}
-// the captured run of GRAPH_PAIRS batch steps that starts at the sampler's current parity (an even number of launches: the parity after
-// a replay is the parity before it)
-static rt_graph &ensure_chain_graph(cogaps_session *s, HostSampler &h)
-{
-    static_assert(GRAPH_PAIRS % 2u == 0u, "a replay must leave the parity as it found it");
-    if ((h.chainGraphValid[0] || h.chainGraphValid[1]) && memcmp(&h.graphKey, &h.d, sizeof(SamplerDev)) != 0) drop_graphs(h);
-    const uint32_t k = h.chainParity;
-    if (!h.chainGraphValid[k]) {
-        const bool timing = s->timing; s->timing = false;
-        const uint64_t g0 = h.genLaunches, e0 = h.evalLaunches;
-        rt_capture_begin(s->stream);
-        for (uint32_t b = 0; b < GRAPH_PAIRS; ++b) launch_chain(s, h);
-        rt_capture_end(s->stream, h.chainGraph[k]);
-        h.genLaunches = g0; h.evalLaunches = e0; s->timing = timing;
-        memcpy(&h.graphKey, &h.d, sizeof(SamplerDev)); h.chainGraphValid[k] = true;
-    }
-    return h.chainGraph[k];
-}
-static void ensure_graph(cogaps_session *s, HostSampler &h)
-{
-    if (h.graphValid && memcmp(&h.graphKey, &h.d, sizeof(SamplerDev)) == 0) return;
-    drop_graphs(h);
-    const bool timing = s->timing; s->timing = false;              // no event records inside a capture
-    const uint64_t g0 = h.genLaunches, e0 = h.evalLaunches;
-    rt_capture_begin(s->stream);
-    for (uint32_t b = 0; b < GRAPH_PAIRS; ++b) { launch_gen(s, h); launch_eval(s, h); }
-    rt_capture_end(s->stream, h.graph);
-    h.genLaunches = g0; h.evalLaunches = e0; s->timing = timing;
-    memcpy(&h.graphKey, &h.d, sizeof(SamplerDev)); h.graphValid = true;
+    const bool wideOk = h.chain && h.d.sparse != 0u;      // (the wide window: the chained sparse launch only; tests take it from the first update on)
+    const uint32_t win = wideOk && s->testWideWindow ? (uint32_t)GEN_WIN_WIDE : gen_window_for(h.genWin, stepsPerBatch, wideOk);
+    if (win != h.genWin) { h.genWin = win; h.graphs.drop(); }
 }
 
 // Launch clock of the chained launches (gaps_state.h): the ring holds {entry of the first workgroup, end of the generator workgroup} of
@@ -741,8 +750,43 @@ static bool chain_recover(cogaps_session *s, HostSampler &h, uint32_t nSteps)
     read_gs(s, h);
     if (s->hGs->error) return false;      // (a decision is still missing: the update cannot be completed)
     h.chain = false; h.chainOff = true; h.chainRecoveries++;
-    if (h.genWin != gen_window_for(h.genWin, 0.f, false)) { h.genWin = gen_window_for(h.genWin, 0.f, false); drop_graphs(h); }      // (the wide window exists for the chained sparse launch only)
+    retune_window(s, h, 0.f);      // (the wide window exists for the chained sparse launch only)
     return true;
+}
+
+// Arms sampler h for an update of n proposals: room for the atoms it can add, exactly n seeder outputs in the seed buffer
+// (ProposalQueue.cpp:12-15; a failed attempt rolls the seeder back, Random.cpp:244-248) and its scalars `g` (as read back) reset for the
+// update; the caller uploads them.  Returns the predicted proposals per batch: the previous update of this sampler is the best predictor.
+static float begin_update(cogaps_session *s, HostSampler &h, GenScalars &g, uint32_t n, uint32_t traceCap)
+{
+    grow_atoms(s, h, g.nAtoms + n + 1024u);
+    if (h.seedCap < (size_t)n + 1) { rt_free(h.seeds); h.seedCap = (size_t)n * 5 / 4 + 1024; h.seeds = dalloc<uint64_t>(h.seedCap); }
+    if (h.hSeedCap < (size_t)n + 1) { rt_free_host(h.hSeeds); h.hSeedCap = (size_t)n * 5 / 4 + 1024; h.hSeeds = (uint64_t *)rt_malloc_host(h.hSeedCap * 8); }
+    seed_take(s, h.hSeeds, n);
+    rt_h2d(h.seeds, h.hSeeds, (size_t)n * 8, s->stream);
+    h.d.seeds = h.seeds;
+    g.annealTemp = h.anneal;
+    g.nSteps = n; g.nDone = 0; g.nBatches = 0; g.updateFlushed = 0; g.qlen = 0;
+    g.traceOn = traceCap ? 1u : 0u; g.traceCount = 0; g.traceCap = traceCap; g.traceBatchCount = 0;
+    h.updLaunches = 0;
+    return h.stepsPerBatch > 1.f ? h.stepsPerBatch : (g.avgQueue > 1.f ? g.avgQueue : 1.f);
+}
+// the outcome of an update of n proposals, as the statistics and the sampler's next update read it
+static void end_update(HostSampler &h, const GenScalars &g, uint32_t n)
+{
+    h.nAtoms = g.nAtoms; h.avgQueue = g.avgQueue; h.batches += g.nBatches;
+    if (g.nBatches >= 8u) h.stepsPerBatch = (float)n / (float)g.nBatches;
+}
+// Batch steps to enqueue before the next progress read-back, for C chains stepped together (g, nSteps, avgq: one per chain; done: the
+// chains whose update is over, or null): what the slowest unfinished chain still needs.  A step enqueued past the end of an update is a
+// wasted launch (two), a read-back one short pipeline bubble: the first chunk takes slightly fewer steps than the estimate says, the
+// later ones converge on the tail.
+static uint32_t chunk_size(uint32_t C, const GenScalars *g, const uint32_t *nSteps, const float *avgq, const char *done, bool first)
+{
+    uint32_t chunk = 0;
+    for (uint32_t c = 0; c < C; ++c)
+        if (!done || !done[c]) chunk = std::max(chunk, (uint32_t)((double)(nSteps[c] - g[c].nDone) / avgq[c] * (first ? 0.97 : 1.0)) + (first ? 0u : 2u));
+    return std::min(std::max(chunk, 6u), 4096u);
 }
 
 // AsynchronousGibbsSampler::update (AsynchronousGibbsSampler.h:88-122): batches of generate + evaluate
@@ -750,32 +794,18 @@ static bool chain_recover(cogaps_session *s, HostSampler &h, uint32_t nSteps)
 // evaluate) pairs are enqueued in chunks and the generator's progress word is read back per chunk;
 // pairs enqueued past the end are no-ops (the generator flushes the last erase cache and reports
 // qlen = 0).
-static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, bool trace, uint32_t traceCap)
+static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, uint32_t traceCap)
 {
     SamplerDev &d = h.d;
     if (s->poisoned) return fail("this session was ended by a device error in an earlier update; its chain cannot be continued");
     UpdateInFlight inFlight(s->p.device);
     read_gs(s, h);
-    GenScalars g = *s->hGs;
-    grow_atoms(s, h, g.nAtoms + nSteps + 1024u);
-    // seed stream for this update: exactly nSteps seeder outputs are consumed (ProposalQueue.cpp:12-15;
-    // a failed attempt rolls the seeder back, Random.cpp:244-248)
-    if (h.seedCap < (size_t)nSteps + 1) { rt_free(h.seeds); h.seedCap = (size_t)nSteps * 5 / 4 + 1024; h.seeds = dalloc<uint64_t>(h.seedCap); }
-    if (h.hSeedCap < (size_t)nSteps + 1) { rt_free_host(h.hSeeds); h.hSeedCap = (size_t)nSteps * 5 / 4 + 1024; h.hSeeds = (uint64_t *)rt_malloc_host(h.hSeedCap * 8); }
-    seed_take(s, h.hSeeds, nSteps);
-    rt_h2d(h.seeds, h.hSeeds, (size_t)nSteps * 8, s->stream);
-    d.seeds = h.seeds;
-    if (trace) {
-        if (h.traceCap < traceCap) {
-            rt_free(d.trace); rt_free(d.traceBatchNproc); rt_free(d.traceBatchQlen);
-            d.trace = dalloc<PropRec>(traceCap); d.traceBatchNproc = dalloc<uint32_t>(traceCap); d.traceBatchQlen = dalloc<uint32_t>(traceCap);
-            h.traceCap = traceCap;
-        }
+    if (h.traceCap < traceCap) {
+        rt_free(d.trace); rt_free(d.traceBatchNproc); rt_free(d.traceBatchQlen);
+        d.trace = dalloc<PropRec>(traceCap); d.traceBatchNproc = dalloc<uint32_t>(traceCap); d.traceBatchQlen = dalloc<uint32_t>(traceCap);
+        h.traceCap = traceCap;
     }
-    g.annealTemp = h.anneal;
-    g.nSteps = nSteps; g.nDone = 0; g.nBatches = 0; g.updateFlushed = 0; g.qlen = 0;
-    g.traceOn = trace ? 1u : 0u; g.traceCount = 0; g.traceCap = trace ? traceCap : 0; g.traceBatchCount = 0;
-    *s->hGs = g;
+    float avgq = begin_update(s, h, *s->hGs, nSteps, traceCap);
     rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream);
     const ChainSlot emptySlots[2] = {{0u, 0u}, {0u, 0u}};
     rt_h2d(d.chainSlots, emptySlots, sizeof(emptySlots), s->stream);      // (chained launch: both parities start from an empty queue)
@@ -783,29 +813,15 @@ static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, bool t
     if (nSteps == 0) return 0;
     sync_record(s, h);
     h.chain = chain_eligible(s, h);
-    {   // the wide window: the chained sparse launch only (gen_window_for); tests take it from the first update on
-        const bool wideOk = h.chain && h.d.sparse != 0u;
-        uint32_t win = gen_window_for(h.genWin, 0.f, wideOk);
-        if (wideOk && s->testWideWindow) win = (uint32_t)GEN_WIN_WIDE;
-        if (win != h.genWin) { h.genWin = win; drop_graphs(h); }
-    }
+    retune_window(s, h, 0.f);
     h.chainParityStart = h.chainParity;
-    h.updLaunches = 0;
-    h.clockSeen = g.batchEpoch;      // (launch clock: the batches of this update carry the tags behind this one)
-    // proposals per batch: the previous update of this sampler is the best predictor
-    float avgq = h.stepsPerBatch > 1.f ? h.stepsPerBatch : (g.avgQueue > 1.f ? g.avgQueue : 1.f);
+    h.clockSeen = s->hGs->batchEpoch;      // (launch clock: the batches of this update carry the tags behind this one)
     bool firstChunk = true, topped = false;
     for (;;) {
-        const uint32_t remaining = nSteps - s->hGs->nDone;
-        // a pair enqueued past the end of the update is two wasted launches, a progress read-back is one short
-        // pipeline bubble: enqueue slightly fewer pairs than the estimate says and converge on the tail
-        uint32_t chunk = (uint32_t)((double)remaining / avgq * (firstChunk ? 0.97 : 1.0)) + (firstChunk ? 0u : 2u);
-        if (chunk < 6u) chunk = 6u;
-        if (chunk > 4096u) chunk = 4096u;
+        uint32_t plain = chunk_size(1, s->hGs, &nSteps, &avgq, nullptr, firstChunk);
         firstChunk = false;
-        uint32_t plain = chunk;
-        if (rt_graphs_supported() && !s->noGraph && !trace && plain >= GRAPH_PAIRS) {
-            if (!h.chain) ensure_graph(s, h);
+        if (rt_graphs_supported() && !s->noGraph && !traceCap && plain >= GRAPH_PAIRS) {
+            h.graphs.rekey(h.d);
             // HIP events cannot ride on replayed launches.  While timing is on, one replay of every chunk -- its position moves
             // through the chunk from update to update -- is issued as plain launches that carry events, so that the sample covers
             // the whole population of batches and not only the tail of each chunk (the remainder below).
@@ -814,12 +830,14 @@ static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, bool t
             const uint32_t timedRep = (s->timing && (rot & 3u) == 0u) ? (uint32_t)(((rot >> 2) * 7u) % nRep) : 0xFFFFFFFFu;
             for (uint32_t r = 0; plain >= GRAPH_PAIRS; plain -= GRAPH_PAIRS, ++r) {
                 if (r == timedRep) { for (uint32_t b = 0; b < GRAPH_PAIRS; ++b) { launch_pair(s, h); h.updLaunches++; } continue; }
-                rt_graph_launch(h.chain ? ensure_chain_graph(s, h) : h.graph, s->stream); if (!h.chain) h.genLaunches += GRAPH_PAIRS; h.evalLaunches += GRAPH_PAIRS; h.updLaunches += GRAPH_PAIRS;
+                const bool timing = s->timing; s->timing = false;      // (a capture's launches are neither timed nor counted)
+                const uint64_t g0 = h.genLaunches, e0 = h.evalLaunches;
+                h.graphs.replay(s->stream, h.chain, h.chainParity, [&] { launch_pair(s, h); });
+                s->timing = timing; h.genLaunches = g0 + (h.chain ? 0u : GRAPH_PAIRS); h.evalLaunches = e0 + GRAPH_PAIRS; h.updLaunches += GRAPH_PAIRS;
             }
         }
         for (uint32_t b = 0; b < plain; ++b) { launch_pair(s, h); h.updLaunches++; }
-        // while the GPU works: the seeds of the next update (the other sampler's, about one per atom it holds; Poisson spread + margin)
-        if (!topped) { HostSampler &o = (&h == &s->A) ? s->P : s->A; seed_top_up(s, (size_t)std::max(o.nAtoms, 10u) + (size_t)(6.0 * sqrt((double)std::max(o.nAtoms, 10u))) + 64u); topped = true; }
+        if (!topped) { seed_top_up(s, &h == &s->A ? s->P : s->A); topped = true; }
         read_gs(s, h);
         timing_resolve(s, s->hGs->nBatches);
         if (h.chain) clock_collect(s, h, s->hGs->batchEpoch, s->hGs->updateFlushed != 0);
@@ -828,11 +846,8 @@ static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, bool t
         if (s->hGs->updateFlushed) break;
         if (s->hGs->nBatches > 0) avgq = std::max(1.f, (float)s->hGs->nDone / (float)s->hGs->nBatches);
     }
-    h.nAtoms = s->hGs->nAtoms; h.avgQueue = s->hGs->avgQueue; h.batches += s->hGs->nBatches;
-    if (s->hGs->nBatches >= 8u) h.stepsPerBatch = (float)nSteps / (float)s->hGs->nBatches;
-    uint32_t win = gen_window_for(h.genWin, h.stepsPerBatch, h.chain && h.d.sparse != 0u);
-    if (h.chain && h.d.sparse != 0u && s->testWideWindow) win = (uint32_t)GEN_WIN_WIDE;
-    if (win != h.genWin) { h.genWin = win; drop_graphs(h); }      // (the captured launches carry the window)
+    end_update(h, *s->hGs, nSteps);
+    retune_window(s, h, h.stepsPerBatch);
     return 0;
 }
 
@@ -845,9 +860,9 @@ static void do_sync(cogaps_session *s, HostSampler &dst, HostSampler &src)
         return;
     }
     const uint32_t tilesX = (src.d.N + TR_TILE - 1) / TR_TILE, tilesY = (src.d.M + TR_TILE - 1) / TR_TILE;
-    const int slot = timing_slot(s, dst, 4, 0);
+    const int slot = timing_slot(s, dst, EV_SYNC, 0);
     if (slot >= 0) s->syncBytes += 8ull * src.d.M * src.d.N;         // algorithmic traffic of a sync: M x N floats read and written
-    LAUNCH_MAYBE_TIMED(slot, transpose_kernel, tilesX * tilesY, 256, (const float *)src.d.AP, dst.d.AP, src.d.M, src.d.N, src.d.Npad, dst.d.Npad, tilesX);
+    LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, transpose_kernel, tilesX * tilesY, 256, (const float *)src.d.AP, dst.d.AP, src.d.M, src.d.N, src.d.Npad, dst.d.Npad, tilesX);
 }
 
 static float chisq_of(cogaps_session *s, HostSampler &h)
@@ -1049,13 +1064,11 @@ cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t
 void cogaps_session_destroy(cogaps_session *s)
 {
     if (!s) return;
-    rt_graph_destroy(s->A.graph); rt_graph_destroy(s->P.graph);
-    for (int k = 0; k < 2; ++k) { rt_graph_destroy(s->A.chainGraph[k]); rt_graph_destroy(s->P.chainGraph[k]); }
+    s->A.graphs.drop(); s->P.graphs.drop();
     free_sampler(s->A); free_sampler(s->P);
     rt_free(s->dErf); rt_free(s->dErfinv); rt_free(s->dQgamma); rt_free(s->dLcgMul); rt_free(s->dLcgInc);
     rt_free(s->Asum); rt_free(s->Asq); rt_free(s->Psum); rt_free(s->Psq); rt_free(s->pump);
     rt_free_host(s->hGs);
-    for (auto &e : s->evPool) rt_event_destroy(e);
     if (s->ownsStream) rt_stream_destroy(s->stream);
     delete s;
 }
@@ -1083,7 +1096,7 @@ int cogaps_session_update(cogaps_session *s, char which, uint32_t nSteps, cogaps
     HostSampler &h = pick(s, which);
     const bool tr = trace != nullptr && traceCap > 0;
     const uint32_t cap = tr ? std::max(traceCap, batchCap) : 0;
-    if (run_update(s, h, nSteps, tr, cap)) return 1;
+    if (run_update(s, h, nSteps, cap)) return 1;
     if (tr) {
         const uint32_t n = std::min(s->hGs->traceCount, cap), nb = std::min(s->hGs->traceBatchCount, cap);
         std::vector<PropRec> rec(n);
@@ -1127,8 +1140,8 @@ int cogaps_session_iterate(cogaps_session *s, uint32_t nA, uint32_t nP, int samp
 {
     SESSION_TRY
     const char f = s->p.whichMatrixFixed;
-    if (f != 'A') { if (run_update(s, s->A, nA, false, 0)) return 1; if (f != 'P') do_sync(s, s->P, s->A); }
-    if (f != 'P') { if (run_update(s, s->P, nP, false, 0)) return 1; if (f != 'A') do_sync(s, s->A, s->P); }
+    if (f != 'A') { if (run_update(s, s->A, nA, 0)) return 1; if (f != 'P') do_sync(s, s->P, s->A); }
+    if (f != 'P') { if (run_update(s, s->P, nP, 0)) return 1; if (f != 'A') do_sync(s, s->A, s->P); }
     iterate_tail(s, nA, nP, sampling);
     SESSION_END
 }
@@ -1216,16 +1229,15 @@ struct cogaps_batch {
     rt_stream_t stream = rt_stream_t();
     SamplerDev *dev[2] = {nullptr, nullptr};            // [0] the A samplers' records, [1] the P samplers'
     std::vector<SamplerDev> host[2];                    // what the device arrays hold
-    rt_graph graph[2]; bool graphValid[2] = {false, false};
+    GraphCache graphs[2];
     // round 6: a side whose evaluation is the fused one steps as ONE chained launch for all chains (chain_kernel_multi) where every workgroup
-    // of it is resident at once; the captured run of launches exists per starting parity, as for the one-chain form
+    // of it is resident at once
     bool chain[2] = {false, false}; uint32_t chainParity[2] = {0, 0}; uint32_t chainWg[2] = {0, 0};
-    rt_graph chainGraph[2][2]; bool chainGraphValid[2][2] = {{false, false}, {false, false}};
     GenScalars *hGs = nullptr;                          // pinned, [C]
     bool sparse = false; char fixed = 'N';
     uint64_t launches[2] = {0, 0};
     // HIP-event samples of the plain-launch remainder of each chunk
-    bool timing = false; std::vector<rt_event_pair> ev; std::vector<int> evKind; std::vector<uint64_t> evOrd; size_t evUsed = 0;
+    bool timing = false; EventPool ev;
     double genMs[2] = {0, 0}, evalMs[2] = {0, 0}; uint64_t genTimed[2] = {0, 0}, evalTimed[2] = {0, 0};
     uint64_t ord = 0;
     uint32_t genWin[2] = {GEN_WIN, GEN_WIN};           // per side, from the chain with the longest batches
@@ -1269,23 +1281,25 @@ static void multi_launch_pair(cogaps_batch *b, int w, const MultiGeom &g, int sl
 {
     const uint32_t C = (uint32_t)b->ss.size();
     const SamplerDev CG_CONSTANT *arr = (const SamplerDev CG_CONSTANT *)b->dev[w];
-#define MLAUNCH(slot, KERNEL, grid, block, ...) do { if ((slot) >= 0) RT_LAUNCH_TIMED(KERNEL, grid, block, b->stream, b->ev[slot], __VA_ARGS__); else RT_LAUNCH(KERNEL, grid, block, b->stream, __VA_ARGS__); } while (0)
     if (b->chain[w]) {
         const uint32_t parity = b->chainParity[w]; b->chainParity[w] ^= 1u;
-        if (b->genWin[w] == (uint32_t)GEN_WIN) MLAUNCH(slotEval, chain_kernel_multi<GEN_WIN>, C * b->chainWg[w], g.block, arr, parity, b->chainWg[w]);
-        else MLAUNCH(slotEval, chain_kernel_multi<GEN_WIN_HALF>, C * b->chainWg[w], g.block, arr, parity, b->chainWg[w]);
+        by_window(b->genWin[w], [&](auto W) {
+            constexpr int WIN = decltype(W)::value;
+            LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, chain_kernel_multi<WIN>, C * b->chainWg[w], g.block, arr, parity, b->chainWg[w]);
+        });
         b->launches[w]++;
         return;
     }
-    if (b->genWin[w] == (uint32_t)GEN_WIN) MLAUNCH(slotGen, gen_kernel_multi<GEN_WIN>, C, GEN_WIN + 64, arr);
-    else MLAUNCH(slotGen, gen_kernel_multi<GEN_WIN_HALF>, C, GEN_WIN_HALF + 64, arr);
-    if (b->sparse) MLAUNCH(slotEval, eval_sparse_kernel_multi, C * g.wgPerChain, g.block, arr, g.wgPerChain);
-    else if (g.fused) MLAUNCH(slotEval, eval_kernel_multi<EVAL_FUSED>, C * g.wgPerChain, g.block, arr, 1u, g.wgPerChain);
+    by_window(b->genWin[w], [&](auto W) {
+        constexpr int WIN = decltype(W)::value;
+        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotGen, gen_kernel_multi<WIN>, C, WIN + 64, arr);
+    });
+    if (b->sparse) LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_sparse_kernel_multi, C * g.wgPerChain, g.block, arr, g.wgPerChain);
+    else if (g.fused) LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_kernel_multi<EVAL_FUSED>, C * g.wgPerChain, g.block, arr, 1u, g.wgPerChain);
     else {
-        MLAUNCH(slotEval, eval_kernel_multi<EVAL_ALPHA>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
-        MLAUNCH(slotEval2, eval_kernel_multi<EVAL_APPLY>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
+        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_kernel_multi<EVAL_ALPHA>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
+        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval2, eval_kernel_multi<EVAL_APPLY>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
     }
-#undef MLAUNCH
     b->launches[w]++;
 }
 
@@ -1293,33 +1307,19 @@ static void multi_launch_pair(cogaps_batch *b, int w, const MultiGeom &g, int sl
 static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps)
 {
     const uint32_t C = (uint32_t)b->ss.size();
-    for (uint32_t c = 0; c < C; ++c)
-        if (b->ss[c]->poisoned) return fail("chain " + std::to_string(c) + " of this batch was ended by a device error in an earlier update; the batch cannot be continued");
     UpdateInFlight inFlight(b->ss[0]->p.device);      // (a one-chain session stepped beside the batch on the same GPU keeps two launches per batch meanwhile)
     rt_alloc_scope allocOn(b->stream);
     for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
     rt_sync(b->stream);
     std::vector<float> avgq(C); std::vector<char> done(C, 0);
     for (uint32_t c = 0; c < C; ++c) {
-        cogaps_session *s = b->ss[c]; HostSampler &h = bpick(b, c, w);
-        GenScalars &g = b->hGs[c];
-        grow_atoms(s, h, g.nAtoms + nSteps[c] + 1024u);
-        const uint32_t n = nSteps[c];
-        if (h.seedCap < (size_t)n + 1) { rt_free(h.seeds); h.seedCap = (size_t)n * 5 / 4 + 1024; h.seeds = dalloc<uint64_t>(h.seedCap); }
-        if (h.hSeedCap < (size_t)n + 1) { rt_free_host(h.hSeeds); h.hSeedCap = (size_t)n * 5 / 4 + 1024; h.hSeeds = (uint64_t *)rt_malloc_host(h.hSeedCap * 8); }
-        seed_take(s, h.hSeeds, n);
-        rt_h2d(h.seeds, h.hSeeds, (size_t)n * 8, b->stream);
-        h.d.seeds = h.seeds;
-        g.annealTemp = h.anneal;
-        g.nSteps = n; g.nDone = 0; g.nBatches = 0; g.updateFlushed = 0; g.qlen = 0;
-        g.traceOn = 0; g.traceCount = 0; g.traceCap = 0; g.traceBatchCount = 0;
+        HostSampler &h = bpick(b, c, w); GenScalars &g = b->hGs[c];
+        avgq[c] = begin_update(b->ss[c], h, g, nSteps[c], 0);
         // update(0) -- a Poisson draw of 0 has probability e^-10 while a chain holds at most 10 atoms -- is a no-op in the reference
         // (AsynchronousGibbsSampler.h:94: the loop body never runs): the chain is done before the first launch and the lock-stepped
         // batch never waits for it (its generator workgroup sees nDone >= nSteps and leaves at once)
-        if (n == 0) { g.updateFlushed = 1; done[c] = 1; }
+        if (nSteps[c] == 0) { g.updateFlushed = 1; done[c] = 1; }
         rt_h2d(h.d.gs, &g, sizeof(GenScalars), b->stream);
-        avgq[c] = h.stepsPerBatch > 1.f ? h.stepsPerBatch : (g.avgQueue > 1.f ? g.avgQueue : 1.f);
-        h.updLaunches = 0;
     }
     if (std::all_of(done.begin(), done.end(), [](char d) { return d != 0; })) { rt_sync(b->stream); return 0; }
     // the records the kernels read: re-uploaded when a pointer in one of them changed (atom tables regrown, seed buffer moved);
@@ -1339,62 +1339,29 @@ static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> 
     }
     bool first = true, topped = false;
     for (;;) {
-        // pairs to enqueue: what the slowest unfinished chain still needs (launches past the end of a chain's update are no-ops for it)
-        uint32_t chunk = 0;
-        for (uint32_t c = 0; c < C; ++c) if (!done[c]) {
-            const uint32_t remaining = nSteps[c] - b->hGs[c].nDone;
-            chunk = std::max(chunk, (uint32_t)((double)remaining / avgq[c] * (first ? 0.97 : 1.0)) + (first ? 0u : 2u));
-        }
-        chunk = std::min(std::max(chunk, 6u), 4096u);
+        uint32_t plain = chunk_size(C, b->hGs, nSteps.data(), avgq.data(), done.data(), first);
         first = false;
-        uint32_t plain = chunk;
-        const bool noGraph = b->ss[0]->noGraph;
-        if (rt_graphs_supported() && !noGraph && plain >= GRAPH_PAIRS && b->chain[w]) {
-            // (an even number of launches per replay: the parity behind a replay is the parity before it)
+        if (rt_graphs_supported() && !b->ss[0]->noGraph)
             for (; plain >= GRAPH_PAIRS; plain -= GRAPH_PAIRS) {
-                const uint32_t k = b->chainParity[w];
-                if (!b->chainGraphValid[w][k]) {
-                    const uint64_t l0 = b->launches[w];
-                    rt_capture_begin(b->stream);
-                    for (uint32_t i = 0; i < GRAPH_PAIRS; ++i) multi_launch_pair(b, w, geo, -1, -1, -1);
-                    rt_capture_end(b->stream, b->chainGraph[w][k]);
-                    b->launches[w] = l0; b->chainGraphValid[w][k] = true;
-                }
-                rt_graph_launch(b->chainGraph[w][k], b->stream); b->launches[w] += GRAPH_PAIRS; b->ord += GRAPH_PAIRS;
+                const uint64_t l0 = b->launches[w];      // (the captured launches are not counted)
+                b->graphs[w].replay(b->stream, b->chain[w], b->chainParity[w], [&] { multi_launch_pair(b, w, geo, -1, -1, -1); });
+                b->launches[w] = l0 + GRAPH_PAIRS; b->ord += GRAPH_PAIRS;
             }
-        } else if (rt_graphs_supported() && !noGraph && plain >= GRAPH_PAIRS) {
-            if (!b->graphValid[w]) {
-                const uint64_t l0 = b->launches[w];
-                rt_capture_begin(b->stream);
-                for (uint32_t k = 0; k < GRAPH_PAIRS; ++k) multi_launch_pair(b, w, geo, -1, -1, -1);
-                rt_capture_end(b->stream, b->graph[w]);
-                b->launches[w] = l0; b->graphValid[w] = true;
-            }
-            for (; plain >= GRAPH_PAIRS; plain -= GRAPH_PAIRS) { rt_graph_launch(b->graph[w], b->stream); b->launches[w] += GRAPH_PAIRS; b->ord += GRAPH_PAIRS; }
-        }
         for (uint32_t k = 0; k < plain; ++k) {
             int sg = -1, se = -1, se2 = -1;
-            if (b->timing && (b->ord % 4u) == 0u && b->evUsed + 3 <= b->ev.size()) {
-                if (b->chain[w]) { se = (int)b->evUsed++; b->evKind[se] = 1; }      // (one launch per step: timed as the evaluation launch, as the one-chain form's is)
-                else {
-                    sg = (int)b->evUsed++; b->evKind[sg] = 0; se = (int)b->evUsed++; b->evKind[se] = 1;
-                    if (!geo.fused) { se2 = (int)b->evUsed++; b->evKind[se2] = 2; }
-                }
+            if (b->timing && (b->ord % 4u) == 0u && b->ev.room(3)) {
+                if (b->chain[w]) se = b->ev.take(EV_EVAL);      // (one launch per step: timed as the evaluation launch, as the one-chain form's is)
+                else { sg = b->ev.take(EV_GEN); se = b->ev.take(EV_EVAL); if (!geo.fused) se2 = b->ev.take(EV_EVAL2); }
             }
             multi_launch_pair(b, w, geo, sg, se, se2);
             b->ord++;
         }
-        if (!topped) {      // while the GPU works: every chain's seeds for its next update (the other sampler's)
-            for (uint32_t c = 0; c < C; ++c) { const uint32_t na = std::max(bpick(b, c, 1 - w).nAtoms, 10u); seed_top_up(b->ss[c], (size_t)na + (size_t)(6.0 * sqrt((double)na)) + 64u); }
-            topped = true;
-        }
+        if (!topped) { for (uint32_t c = 0; c < C; ++c) seed_top_up(b->ss[c], bpick(b, c, 1 - w)); topped = true; }
         for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
         rt_sync(b->stream);
-        for (size_t i = 0; i < b->evUsed; ++i) {          // (sampled launches near the end of a chunk: most chains still have work there)
-            const float ms = rt_event_ms(b->ev[i]);
-            if (b->evKind[i] == 0) { b->genMs[w] += ms; b->genTimed[w]++; } else { b->evalMs[w] += ms; if (b->evKind[i] == 1) b->evalTimed[w]++; }
-        }
-        b->evUsed = 0;
+        b->ev.drain([&](const EvSample &e, float ms) {          // (sampled launches near the end of a chunk: most chains still have work there)
+            if (e.kind == EV_GEN) { b->genMs[w] += ms; b->genTimed[w]++; } else { b->evalMs[w] += ms; if (e.kind == EV_EVAL) b->evalTimed[w]++; }
+        });
         bool all = true;
         for (uint32_t c = 0; c < C; ++c) {
             const GenScalars &g = b->hGs[c];
@@ -1404,18 +1371,10 @@ static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> 
         }
         if (all) break;
     }
-    for (uint32_t c = 0; c < C; ++c) {
-        HostSampler &h = bpick(b, c, w); const GenScalars &g = b->hGs[c];
-        h.nAtoms = g.nAtoms; h.avgQueue = g.avgQueue; h.batches += g.nBatches;
-        if (g.nBatches >= 8u) h.stepsPerBatch = (float)nSteps[c] / (float)g.nBatches;
-    }
-    float spb = 0.f; for (uint32_t c = 0; c < C; ++c) spb = std::max(spb, bpick(b, c, w).stepsPerBatch);
+    float spb = 0.f;
+    for (uint32_t c = 0; c < C; ++c) { end_update(bpick(b, c, w), b->hGs[c], nSteps[c]); spb = std::max(spb, bpick(b, c, w).stepsPerBatch); }
     const uint32_t win = gen_window_for(b->genWin[w], spb);
-    if (win != b->genWin[w]) {
-        b->genWin[w] = win;
-        if (b->graphValid[w]) { rt_graph_destroy(b->graph[w]); b->graphValid[w] = false; }
-        for (int k = 0; k < 2; ++k) if (b->chainGraphValid[w][k]) { rt_graph_destroy(b->chainGraph[w][k]); b->chainGraphValid[w][k] = false; }
-    }
+    if (win != b->genWin[w]) { b->genWin[w] = win; b->graphs[w].drop(); }
     return 0;
 }
 
@@ -1448,7 +1407,7 @@ cogaps_batch *cogaps_batch_create(cogaps_session **sessions, uint32_t n)
         for (int w = 0; w < 2; ++w) { b->dev[w] = dalloc<SamplerDev>(n); b->host[w].resize(n); memset(b->host[w].data(), 0, sizeof(SamplerDev) * n); }
         for (cogaps_session *s : b->ss) rt_sync(s->stream);
         for (cogaps_session *s : b->ss) {      // from here on the sessions run on the batch's stream, one after the other (nothing below throws)
-            drop_graphs(s->A); drop_graphs(s->P);
+            s->A.graphs.drop(); s->P.graphs.drop();
             rt_stream_destroy(s->stream); s->stream = b->stream; s->ownsStream = false; s->A.chain = false; s->P.chain = false;      // (the batched launches keep two launches per step: cogaps_session_chained reports what runs)
         }
         return b;
@@ -1469,8 +1428,7 @@ void cogaps_batch_destroy(cogaps_batch *b)
     if (!b) return;
     try { rt_sync(b->stream); } catch (...) { }
     for (cogaps_session *s : b->ss) { try { s->stream = rt_stream_create(); s->ownsStream = true; } catch (...) { } }      // the sessions outlive the batch
-    for (int w = 0; w < 2; ++w) { rt_graph_destroy(b->graph[w]); rt_free(b->dev[w]); for (int k = 0; k < 2; ++k) if (b->chainGraphValid[w][k]) rt_graph_destroy(b->chainGraph[w][k]); }
-    for (auto &e : b->ev) rt_event_destroy(e);
+    for (int w = 0; w < 2; ++w) { b->graphs[w].drop(); rt_free(b->dev[w]); }
     rt_free_host(b->hGs);
     rt_stream_destroy(b->stream);
     delete b;
@@ -1512,7 +1470,7 @@ int cogaps_batch_run_iterations(cogaps_batch *b, int phase, uint32_t firstIter, 
 int cogaps_batch_set_timing(cogaps_batch *b, int on)
 {
     try {
-        if (on && b->ev.empty()) { b->ev.resize(1536); b->evKind.resize(1536); for (auto &e : b->ev) rt_event_create(e); }
+        if (on) b->ev.create(1536);
         if (on && !b->timing) for (int w = 0; w < 2; ++w) { b->genMs[w] = b->evalMs[w] = 0; b->genTimed[w] = b->evalTimed[w] = 0; }
         b->timing = on != 0;
         return 0;
@@ -1734,11 +1692,7 @@ extern "C" int cogaps_debug_eval_timeline(unsigned long long *out, int n)
 int cogaps_session_set_timing(cogaps_session *s, int on)
 {
     SESSION_TRY
-    if (on && !s->evInit) {
-        s->evPool.resize(2048); s->evKind.resize(2048); s->evOwner.resize(2048); s->evOrd.resize(2048);
-        for (auto &e : s->evPool) rt_event_create(e);
-        s->evInit = true;
-    }
+    if (on) s->ev.create(2048);
     if (on && !s->timing) {      // a new window: the sampled times are scaled to the batches processed from here on
         for (HostSampler *h : {&s->A, &s->P}) {
             h->batchesAtTimingOn = h->batches;
@@ -1781,38 +1735,48 @@ int cogaps_session_perf_sampler(cogaps_session *s, char which, cogaps_perf *out)
     SESSION_END
 }
 
-int cogaps_session_launch_clock(cogaps_session *s, char which, double *meanUs, double *percentilesUs, uint64_t *launches)
+// the mean and the 10 / 50 / 75 / 90 / 99th percentiles of n launch times kept as a histogram of 0.1 us bins
+static int report_hist(const std::vector<uint64_t> &hist, double sumUs, uint64_t n, double *meanUs, double *percentilesUs, uint64_t *launches)
 {
-    SESSION_TRY
     if (!meanUs || !percentilesUs || !launches) return fail("null argument");
-    HostSampler &h = pick(s, which);
-    *launches = h.clockN; *meanUs = h.clockN ? h.clockSumUs / (double)h.clockN : 0.0;
+    *launches = n; *meanUs = n ? sumUs / (double)n : 0.0;
     static const double q[5] = {0.10, 0.50, 0.75, 0.90, 0.99};
     for (int k = 0; k < 5; ++k) {
         percentilesUs[k] = 0.0;
-        if (!h.clockN) continue;
-        const uint64_t want = (uint64_t)(q[k] * (double)h.clockN); uint64_t acc = 0;
-        for (size_t b = 0; b < h.clockHist.size(); ++b) { acc += h.clockHist[b]; if (acc > want) { percentilesUs[k] = 0.1 * ((double)b + 0.5); break; } }
+        if (!n) continue;
+        const uint64_t want = (uint64_t)(q[k] * (double)n); uint64_t acc = 0;
+        for (size_t b = 0; b < hist.size(); ++b) { acc += hist[b]; if (acc > want) { percentilesUs[k] = 0.1 * ((double)b + 0.5); break; } }
     }
+    return 0;
+}
+int cogaps_session_launch_clock(cogaps_session *s, char which, double *meanUs, double *percentilesUs, uint64_t *launches)
+{
+    SESSION_TRY
+    const HostSampler &h = pick(s, which);
+    return report_hist(h.clockHist, h.clockSumUs, h.clockN, meanUs, percentilesUs, launches);
     SESSION_END
 }
 int cogaps_session_launch_period(cogaps_session *s, char which, double *meanUs, double *percentilesUs, uint64_t *launches)
 {
     SESSION_TRY
-    if (!meanUs || !percentilesUs || !launches) return fail("null argument");
-    HostSampler &h = pick(s, which);
-    *launches = h.periodN; *meanUs = h.periodN ? h.periodSumUs / (double)h.periodN : 0.0;
-    static const double q[5] = {0.10, 0.50, 0.75, 0.90, 0.99};
-    for (int k = 0; k < 5; ++k) {
-        percentilesUs[k] = 0.0;
-        if (!h.periodN) continue;
-        const uint64_t want = (uint64_t)(q[k] * (double)h.periodN); uint64_t acc = 0;
-        for (size_t b = 0; b < h.periodHist.size(); ++b) { acc += h.periodHist[b]; if (acc > want) { percentilesUs[k] = 0.1 * ((double)b + 0.5); break; } }
-    }
+    const HostSampler &h = pick(s, which);
+    return report_hist(h.periodHist, h.periodSumUs, h.periodN, meanUs, percentilesUs, launches);
     SESSION_END
 }
-int cogaps_session_chain_recoveries(cogaps_session *s, char which, uint32_t *n) { *n = pick(s, which).chainRecoveries; return 0; }
-int cogaps_session_generator_window(cogaps_session *s, char which, uint32_t *attempts) { *attempts = pick(s, which).genWin; return 0; }
+int cogaps_session_chain_recoveries(cogaps_session *s, char which, uint32_t *n)
+{
+    SESSION_TRY
+    if (!n) return fail("null argument");
+    *n = pick(s, which).chainRecoveries;
+    SESSION_END
+}
+int cogaps_session_generator_window(cogaps_session *s, char which, uint32_t *attempts)
+{
+    SESSION_TRY
+    if (!attempts) return fail("null argument");
+    *attempts = pick(s, which).genWin;
+    SESSION_END
+}
 int cogaps_session_chained(cogaps_session *s, char which, int *chained)
 {
     SESSION_TRY

@@ -236,7 +236,9 @@ int cogaps_session_perf_sampler(cogaps_session *s, char which, cogaps_perf *out)
  * decisions the evaluation workgroups have left by then (chain_recover_kernel), and the sampler goes on -- same chain, same bits -- with
  * two launches per batch for the rest of the session.  cogaps_session_chain_recoveries counts such events (0 in every run so far).  Only if
  * a decision is still missing then (the split evaluation's chained form, COGAPS_CHAIN_SPLIT: its deciding workgroups wait as well) does the
- * update end with an error (GAPS_ERR_SPIN) and the session refuse further steps. */
+ * update end with an error (GAPS_ERR_SPIN) and the session refuse further steps.  This recovery serves one-chain sessions only: in a batch
+ * (cogaps_batch_*, whose chained launch is chain_kernel_multi) a wait that runs out ends the update with the error GAPS_ERR_SPIN, and the
+ * batch refuses further steps. */
 int cogaps_session_chained(cogaps_session *s, char which, int *chained);
 int cogaps_session_chain_recoveries(cogaps_session *s, char which, uint32_t *n);
 /* Attempts per round of the sampler's generator launches as of its last update (the library's instantiations: 128, 256, and 448 for the sparse
