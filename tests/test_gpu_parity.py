@@ -888,14 +888,14 @@ def test_sccogaps_every_shard_against_the_oracle(hip_lib):
 
 def test_configs4_shard_invariants(hip_lib):
     """BASELINE configs[4]'s per-GPU shard: 50000 genes x 12500 cells, 95 % zeros, sparseOptimization, K = 50 (cf. `bench.py --sparse
-    --genes 50000 --samples 12500`).  Too large for the oracle in a test; size-independent properties instead: the same seed twice
+    --genes 50000 --samples 12500`), 16 iterations.  Size-independent properties, which hold whatever the lane order: the same seed twice
     gives the same bits; the HybridMatrix row and column copies agree within epsilon and the flag words mark exactly the column
     copy's non-zeros; the row copy equals the atoms summed per bin; atoms sorted and linked; the sparse chi2 equals the dense
-    formula with the model's uncertainty (0.1 on zeros, 0.1 d elsewhere) evaluated from A, P in float64 on a sample of columns"""
-    import bench
+    formula with the model's uncertainty (0.1 on zeros, 0.1 d elsewhere) evaluated from A, P in float64.  The same chain is compared
+    with the oracle bit for bit by test_configs4_shard_shape_stepwise (proposal traces and state, up to past the A sampler's switch
+    to the wide generator window) and test_benchmarked_sparse_chain_end_to_end_against_the_golden (all 200 iterations)."""
     from cogaps_amd import _capi
-    data = bench.synthetic_dense(50000, 12500)
-    data *= (np.random.Generator(np.random.MT19937(777)).random(data.shape) >= 0.95)
+    data = pu.configs4_shard()
     runs = []
     for _ in range(2):
         S = _capi.Session(data, lib=hip_lib, nPatterns=50, nIterations=40, seed=42, outputFrequency=10, sparseOptimization=True)
@@ -923,13 +923,76 @@ def test_configs4_shard_invariants(hip_lib):
     part = (((d - ap) / sig) ** 2).sum()
     # chi2 of the whole matrix from the library vs the same formula on the sampled columns scaled up: same order of magnitude only
     # (the columns differ); the exact check is per sampled column against a second, closed-form evaluation
-    full = 0.0
-    for c0 in range(0, 12500, 500):
-        dd = data[:, c0:c0 + 500].astype(np.float64)
-        aa = rA.astype(np.float64) @ rP[c0:c0 + 500].astype(np.float64).T
-        full += (((dd - aa) / np.where(dd > 0, 0.1 * dd, 0.1)) ** 2).sum()
+    full = pu.sparse_chisq_f64(data, rA, rP)
     assert abs(chi - full) < 2e-3 * full and part > 0
     last.close()
+
+
+C4_KW = dict(nPatterns=50, nIterations=100, seed=42, outputFrequency=10, sparseOptimization=True)
+
+
+def test_configs4_shard_shape_stepwise(hip_lib):
+    """BASELINE configs[4]'s per-GPU shard -- 50000 x 12500, 95 % zeros, sparseOptimization, K = 50, the chain `bench.py --sparse
+    --genes 50000 --samples 12500` times -- from iteration 0 against the 16-thread lane-order oracle, so that a failure is located:
+    Poisson step counts and both atom counts every iteration; the per-proposal traces (type, rows, columns, positions, PCG states, atom
+    indices, batch sizes) of the first three iterations and of the iterations around the A sampler's switch from 256 to 448 attempts
+    (chain_sparse_kernel<448, false>: seven attempt waves, the attempt lanes carrying the queue behind the helper wave's 64 slots); the
+    full state (atoms, both HybridMatrix copies, chi2) just before the switch, three iterations after it and at the end, six iterations
+    after the A sampler's window first reads 448.  The P sampler runs the wide form (chain_sparse_kernel<256, true>: 782 flag words of
+    its 50000-element vectors folded onto 256 lanes) throughout.  Traced updates launch without graph capture, the others replay
+    captured graphs, as the bench does.
+    As measured on the MI355X (~85 s): the A window reads 448 after iteration 42 (the update of iteration 43 is the first at 448
+    attempts); the P window goes 256 -> 128 after iteration 6 and back to 256 after iteration 38; 49 iterations, 4.58 M proposals, 2.46 M
+    of them compared one by one by trace (iterations 0-2, 33-44), all of them through the state after iterations 42, 45 and 48."""
+    import pyoracle as po
+    from cogaps_amd import _capi
+    data = pu.configs4_shard()
+    S = _capi.Session(data, lib=hip_lib, **C4_KW)
+    assert (hip_lib.cogaps_reduction_width(12500), hip_lib.cogaps_reduction_width(50000)) == (4096, 16384)
+    O = po.Session(data, omp=True, maxThreads=min(16, os.cpu_count() or 1), math_mode=po.MATH_PORTABLE, redW_A=4096, redW_P=16384, redG=4, **C4_KW)
+    switch, traced_its, winsP, props, traced, checked = None, [], [], 0, 0, []
+    last_q = 0.0
+    it = 0
+    while switch is None or it <= switch + 6:
+        assert it < 100, "the A sampler never switched to the wide generator window in the equilibration phase: the path under test was not taken"
+        t = min(1.0, 2.0 * it / 100)
+        S.set_annealing(t), O.set_annealing(t)
+        nA, nP = S.draw_steps()
+        assert (nA, nP) == O.draw_steps(), "Poisson step counts differ at iteration %d" % it
+        # traced: the first iterations; once the A sampler's batches near the switch threshold (0.9 x 256 proposals), the narrow window's
+        # last updates; the first two at 448 attempts
+        trace = it < 3 or (switch is None and last_q > 0.75 * 256) or (switch is not None and it <= switch + 2)
+        b0 = S.perf("A")
+        if trace:
+            for w, n, other in (("A", nA, "P"), ("P", nP, "A")):
+                pu.assert_trace_equal(S.update(w, n, n + 256), O.update(w, n, n + 256), "iteration %d, sampler %s" % (it, w))
+                S.sync(other), O.sync(other)
+            traced_its.append(it)
+            traced += nA + nP
+        else:
+            S.iterate(nA, nP), O.iterate(nA, nP)
+        b1 = S.perf("A")
+        last_q = (b1["proposalsQueued"] - b0["proposalsQueued"]) / max(1, b1["batches"] - b0["batches"])
+        props += nA + nP
+        for w in "AP":
+            assert S.natoms(w) == O.natoms(w), "atom counts of sampler %s differ after iteration %d" % (w, it)
+        if trace and it >= 2:
+            assert S.chained("A") == 1 and S.chained("P") == 1, "iteration %d: the traced updates did not run as chained launches" % it
+        winsP.append(S.generator_window("P"))
+        if switch is None and S.generator_window("A") == 448:
+            switch = it
+        if switch is not None and it in (switch, switch + 3):
+            pu.assert_state_equal(S, O, "iteration %d (A window %d)" % (it, S.generator_window("A")), ap=False)
+            checked.append(it)
+        it += 1
+    pu.assert_state_equal(S, O, "iteration %d" % (it - 1), ap=False)
+    checked.append(it - 1)
+    assert S.generator_window("A") == 448 and S.chained("A") == 1 and S.chained("P") == 1
+    assert switch in traced_its and switch + 1 in traced_its, "the updates on either side of the switch were not traced: %s" % traced_its
+    assert set(winsP) == {128, 256}, "the P sampler's window did not move between 128 and 256 attempts: %s" % sorted(set(winsP))
+    print("configs[4] shard stepwise: %d iterations, %d proposals (%d of them compared by trace, iterations %s); A window 448 from the "
+          "update of iteration %d on; P windows after each iteration %s; state compared after iterations %s" % (it, props, traced, traced_its, switch + 1, winsP, checked))
+    S.close(), O.close()
 
 
 def test_current_device_as_the_first_runtime_call():
@@ -1038,6 +1101,62 @@ def test_benchmarked_chain_end_to_end_against_the_golden(hip_lib):
     r = S.finish()
     S.close()
     assert r["totalUpdates"] == int(g["totalUpdates"]) == 52906603
+    for f in ("atomsA", "atomsP", "chisq"):
+        assert np.array_equal(r[f], g[f]), f
+    assert r["averageQueueLengthA"] == float(g["avgQueueA"]) and r["averageQueueLengthP"] == float(g["avgQueueP"]) and r["meanChiSq"] == float(g["meanChiSq"])
+    for f in ("Amean", "Pmean", "Asd", "Psd"):
+        flat = r[f].ravel()
+        assert np.array_equal(flat[g["sample_idx_" + f]], g["sample_" + f]), f + " (sample)"
+        assert sha(r[f]) == str(g["sha256_" + f]), f
+
+
+def test_benchmarked_sparse_chain_end_to_end_against_the_golden(hip_lib):
+    """The sparse chain `bench.py --sparse --genes 50000 --samples 12500` times -- BASELINE configs[4]'s per-GPU shard, 95 % zeros,
+    sparseOptimization, K = 50, seed 42, 100 + 100 iterations -- stepped as bench.py's run_steps does (run_iterations one schedule step
+    at a time: captured graphs replayed) against tests/golden/c4shard_k50_s42_i100_sparse_lane.npz (the lane-order oracle's run,
+    tools/make_golden_c3.py --sparse): the proposals of EVERY schedule step and both domain sizes after it, the atom / chi2 histories,
+    totalUpdates, the queue lengths, meanChiSq, the four statistics matrices (sha256 + 4096 entries each to locate a mismatch) and the
+    final chain state (atoms, both HybridMatrix copies) -- all bit for bit.  The launch forms are the bench's: chained on both sides,
+    the A sampler switching from 256 to 448 attempts mid-run (graphs dropped and captured again) and the P sampler on the wide
+    evaluation.  Last, chi2 of the final state in float64 over the whole matrix, through neither float32 implementation.
+    As measured on the MI355X (~37 s): the A window goes 256 -> 128 after schedule step 6, -> 256 after step 22 and -> 448 after step 42,
+    where it stays; the P window 256 -> 128 after step 6 and back to 256 after step 38.  The chain is 145 155 168 proposals."""
+    import hashlib
+    from cogaps_amd import _capi
+    g = np.load(os.path.join(GOLDEN, "c4shard_k50_s42_i100_sparse_lane.npz"))
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    data = pu.configs4_shard()
+    assert sha(data) == str(g["sha256_input"]), "the input differs from the golden's (bench.synthetic_dense or numpy's MT19937 streams changed): not a kernel mismatch"
+    assert (hip_lib.cogaps_reduction_width(12500), hip_lib.cogaps_reduction_width(50000)) == (int(g["redW_A"]), int(g["redW_P"])) == (4096, 16384)
+    S = _capi.Session(data, lib=hip_lib, **C4_KW)
+    win0 = S.generator_window("A")
+    winsA, winsP = [], []
+    k = 0
+    for phase in (1, 2):
+        for it in range(100):
+            upd = S.run_iterations(phase, it, 1)
+            assert upd == int(g["stepsA"][k]) + int(g["stepsP"][k]), "proposals of schedule step %d" % k
+            for w in "AP":
+                assert S.natoms(w) == int(g["natoms" + w][k]), "atoms of sampler %s after schedule step %d" % (w, k)
+            winsA.append(S.generator_window("A")), winsP.append(S.generator_window("P"))
+            k += 1
+    for w in "AP":
+        a = S.atoms(w)
+        assert sha(a["pos"]) == str(g["sha256_atoms_pos_" + w]) and sha(a["mass"]) == str(g["sha256_atoms_mass_" + w]), "final atoms " + w
+        assert sha(S.matrix(w)) == str(g["sha256_matrix_" + w]), "final factor matrix (HybridMatrix column copy) " + w
+        assert sha(S.rows(w)) == str(g["sha256_rows_" + w]), "final factor matrix (HybridMatrix row copy) " + w
+        assert S.check_domain(w) == 0
+    assert S.chained("A") == 1 and S.chained("P") == 1 and winsA[-1] == 448
+    switch = winsA.index(448)
+    assert win0 < 448 and winsA[0] < 448 and switch > 0, "the A sampler did not begin below 448 attempts: the switch was not tested"
+    moves = lambda ws: [(k, w) for k, w in enumerate(ws) if k == 0 or w != ws[k - 1]]
+    print("configs[4] shard golden: window after schedule step -- A %s, P %s" % (moves(winsA), moves(winsP)))
+    full = pu.sparse_chisq_f64(data, S.rows("A"), S.rows("P"))
+    chi = S.chisq("P")
+    assert abs(chi - full) < 2e-3 * full, (chi, full)
+    r = S.finish()
+    S.close()
+    assert r["totalUpdates"] == int(g["totalUpdates"]) == 145155168
     for f in ("atomsA", "atomsP", "chisq"):
         assert np.array_equal(r[f], g[f]), f
     assert r["averageQueueLengthA"] == float(g["avgQueueA"]) and r["averageQueueLengthP"] == float(g["avgQueueP"]) and r["meanChiSq"] == float(g["meanChiSq"])
