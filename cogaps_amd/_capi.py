@@ -61,6 +61,13 @@ class CogapsPerfC(C.Structure):
     ]
 
 
+class CogapsSparseMatrixC(C.Structure):
+    _fields_ = [
+        ("nrow", C.c_uint32), ("ncol", C.c_uint32), ("majorIsRow", C.c_int32),
+        ("indptr", C.c_void_p), ("indices", C.c_void_p), ("values", C.c_void_p), ("onDevice", C.c_int32),
+    ]
+
+
 TRACE_DTYPE = np.dtype([
     ("pos", "<u8"), ("rng_state", "<u8"), ("atom1", "<u4"), ("atom2", "<u4"),
     ("r1", "<u4"), ("c1", "<u4"), ("r2", "<u4"), ("c2", "<u4"), ("type", "<u4"), ("batch", "<u4"),
@@ -78,6 +85,7 @@ EXPORTS = [
     "cogaps_session_finish", "cogaps_session_set_timing", "cogaps_session_perf",
     "cogaps_session_perf_sampler", "cogaps_session_chained", "cogaps_session_chain_recoveries", "cogaps_session_generator_window", "cogaps_session_launch_clock", "cogaps_session_launch_period", "cogaps_session_get_rows", "cogaps_sparse_width", "cogaps_reduction_width", "cogaps_session_debug_prof", "cogaps_session_debug_replay",
     "cogaps_run_from_file", "cogaps_read_matrix_file", "cogaps_read_matrix_file_subset", "cogaps_matrix_free", "cogaps_file_info", "cogaps_debug_math", "cogaps_current_device", "cogaps_device_memory",
+    "cogaps_session_create_sparse", "cogaps_run_sparse", "cogaps_session_device_bytes", "cogaps_session_sparse_build_ms", "cogaps_session_debug_sparse_data",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -123,6 +131,12 @@ def bind(L):
     L.cogaps_source_hash.restype = C.c_char_p
     L.cogaps_session_create.restype = vp
     L.cogaps_session_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CogapsParamsC), vp, C.c_int]
+    L.cogaps_session_create_sparse.restype = vp
+    L.cogaps_session_create_sparse.argtypes = [C.POINTER(CogapsSparseMatrixC), C.POINTER(CogapsParamsC)]
+    L.cogaps_run_sparse.argtypes = [C.POINTER(CogapsSparseMatrixC), C.POINTER(CogapsParamsC), C.POINTER(CogapsResultC)]
+    L.cogaps_session_device_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cogaps_session_sparse_build_ms.argtypes = [vp, fp]
+    L.cogaps_session_debug_sparse_data.argtypes = [vp, C.c_char, u32p, u32p, fp, fp, vp, vp, vp, vp]
     L.cogaps_session_destroy.argtypes = [vp]
     L.cogaps_session_destroy.restype = None
     L.cogaps_session_set_annealing.argtypes = [vp, C.c_float]
@@ -288,18 +302,101 @@ def result_to_dict(L, r):
     return out
 
 
+def is_sparse(data):
+    """whether `data` is a scipy.sparse matrix (scipy is imported only if the process can import it; without it nothing is sparse)"""
+    try:
+        import scipy.sparse as sp
+    except ImportError:
+        return False
+    return sp.issparse(data)
+
+
+class SparseMatrix:
+    """A matrix in compressed-sparse form as cogaps_sparse_matrix takes it (include/cogaps_hip.h): CSR or CSC, indptr uint64,
+    indices uint32, values float32 -- from a scipy.sparse matrix (canonicalised: duplicates summed, indices sorted; anything but CSC
+    becomes CSR), or from three device-resident arrays (on_device=True: the integers are addresses, e.g. torch's data_ptr())."""
+
+    def __init__(self, shape, major_is_row, indptr, indices, values, on_device=False):
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.major_is_row, self.on_device = bool(major_is_row), bool(on_device)
+        self.indptr, self.indices, self.values = indptr, indices, values
+
+    @classmethod
+    def from_scipy(cls, m):
+        m = m.copy() if m.format == "csc" else m.tocsr(copy=True)
+        m.sum_duplicates()
+        m.sort_indices()
+        return cls(m.shape, m.format == "csr", np.ascontiguousarray(m.indptr, dtype=np.uint64), np.ascontiguousarray(m.indices, dtype=np.uint32),
+                   np.ascontiguousarray(m.data, dtype=np.float32))
+
+    def c_struct(self):
+        addr = (lambda a: int(a)) if self.on_device else (lambda a: a.ctypes.data)
+        return CogapsSparseMatrixC(self.shape[0], self.shape[1], int(self.major_is_row), addr(self.indptr), addr(self.indices), addr(self.values), int(self.on_device))
+
+
+def _sparse_input(data, unc, kw):
+    """the SparseMatrix to hand to the library's compressed-sparse entry, or None for the dense entry.  A scipy.sparse matrix goes in
+    compressed form when the run uses the sparse model; the dense model takes it densified (the caller does: toarray())."""
+    if isinstance(data, SparseMatrix):
+        if unc is not None:
+            raise ValueError("the sparse model takes no uncertainty matrix")
+        return data
+    if is_sparse(data) and kw.get("sparseOptimization", False):
+        if unc is not None:
+            raise ValueError("the sparse model takes no uncertainty matrix")
+        return SparseMatrix.from_scipy(data)
+    return None
+
+
+def _dense(a):
+    return np.ascontiguousarray(a.toarray() if is_sparse(a) else a, dtype=np.float32)
+
+
 class Session:
-    """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h)."""
+    """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h).  `data`: a dense matrix, a scipy.sparse matrix
+    (with sparseOptimization=True it reaches the library in compressed form, cogaps_session_create_sparse; otherwise densified) or a
+    SparseMatrix."""
 
     def __init__(self, data, unc=None, lib=None, **kw):
         self.L = lib if lib is not None else load()
-        self.d = np.ascontiguousarray(data, dtype=np.float32)
-        self.u = None if unc is None else np.ascontiguousarray(unc, dtype=np.float32)
         self.p = make_params(self.L, **kw)
+        self.sp = _sparse_input(data, unc, kw)
+        if self.sp is not None:
+            self.d = self.u = None
+            m = self.sp.c_struct()
+            self.h = self.L.cogaps_session_create_sparse(C.byref(m), C.byref(self.p))
+            if not self.h:
+                raise _error(self.L, "cogaps_session_create_sparse: ")
+            self.sp = None      # the library copied what it needs
+            return
+        self.d = _dense(data)
+        self.u = None if unc is None else _dense(unc)
         self.h = self.L.cogaps_session_create(self.d.ctypes.data, self.d.shape[0], self.d.shape[1], C.byref(self.p),
                                               None if self.u is None else self.u.ctypes.data, 0)
         if not self.h:
             raise _error(self.L, "cogaps_session_create: ")
+
+    def device_bytes(self):
+        """bytes of device memory the session holds (its own allocations)"""
+        v = C.c_uint64(0)
+        self._ck(self.L.cogaps_session_device_bytes(self.h, C.byref(v)))
+        return int(v.value)
+
+    def sparse_build_ms(self):
+        """HIP-event time of the ordered sums at the creation of a session from a compressed-sparse matrix (0 otherwise)"""
+        v = C.c_float(0)
+        self._ck(self.L.cogaps_session_sparse_build_ms(self.h, C.byref(v)))
+        return float(v.value)
+
+    def debug_sparse_data(self, which):
+        """the sparse model's data structures of sampler `which`: flags / prefix [M][Wn], ptr [M + 1], vals, lambda, maxGibbsMass"""
+        wn, nv, lam, mg = C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float()
+        self._ck(self.L.cogaps_session_debug_sparse_data(self.h, which.encode(), C.byref(wn), C.byref(nv), C.byref(lam), C.byref(mg), None, None, None, None))
+        m = self.dims(which)[0]
+        fl, pre = np.zeros((m, wn.value), dtype=np.uint64), np.zeros((m, wn.value), dtype=np.uint32)
+        ptr, vals = np.zeros(m + 1, dtype=np.uint32), np.zeros(nv.value, dtype=np.float32)
+        self._ck(self.L.cogaps_session_debug_sparse_data(self.h, which.encode(), None, None, None, None, fl.ctypes.data, pre.ctypes.data, ptr.ctypes.data, vals.ctypes.data))
+        return {"flags": fl, "prefix": pre, "ptr": ptr, "vals": vals, "lambda": lam.value, "maxGibbsMass": mg.value}
 
     def _ck(self, rc):
         if rc:
@@ -518,10 +615,16 @@ def run_from_file(path, unc_path=None, lib=None, **kw):
 def run(data, unc=None, lib=None, **kw):
     """cogaps_run: one full equilibration + sampling run."""
     L = lib if lib is not None else load()
-    d = np.ascontiguousarray(data, dtype=np.float32)
-    u = None if unc is None else np.ascontiguousarray(unc, dtype=np.float32)
     p = make_params(L, **kw)
     r = CogapsResultC()
+    sp = _sparse_input(data, unc, kw)
+    if sp is not None:
+        m = sp.c_struct()
+        if L.cogaps_run_sparse(C.byref(m), C.byref(p), C.byref(r)):
+            raise _error(L, "cogaps_run_sparse: ")
+        return result_to_dict(L, r)
+    d = _dense(data)
+    u = None if unc is None else _dense(unc)
     rc = L.cogaps_run(_fp(d), d.shape[0], d.shape[1], C.byref(p), None if u is None else _fp(u), C.byref(r))
     if rc:
         raise _error(L, "cogaps_run: ")

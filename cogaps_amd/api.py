@@ -1,7 +1,7 @@
 """CoGAPS() -- the reference's user entry point (R/CoGAPS.R:90-155) over the HIP library.
 
-Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData) or a path to a
-.mtx/.csv/.tsv file.  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
+Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData), a scipy.sparse matrix
+(with sparseOptimization=True it is never densified) or a path to a .mtx/.csv/.tsv file.  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
 `distributed` = "genome-wide" / "single-cell" dispatches to cogaps_amd.distributed (GWCoGAPS / scCoGAPS).
 """
 import warnings
@@ -24,9 +24,10 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
         raise ValueError("snapshotPhase must be either equilibration, sampling, or all")
     if params.distributed is not None and nThreads > 1:
         warnings.warn("can't run multi-threaded and distributed CoGAPS at the same time, ignoring nThreads")
-    if np.isnan(data).any():
+    values = data.data if _capi.is_sparse(data) else data        # a scipy.sparse matrix: its stored entries (the rest are zeros)
+    if np.isnan(values).any():
         raise ValueError("NA values in data")
-    if (data < 0).any() or (uncertainty is not None and (uncertainty < 0).any()):
+    if (values < 0).any() or (uncertainty is not None and (uncertainty < 0).any()):
         raise ValueError("negative values in data and/or uncertainty matrix")
     if data.shape[0] <= params.nPatterns or data.shape[1] <= params.nPatterns:
         raise ValueError("nPatterns must be less than dimensions of data")
@@ -48,7 +49,12 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
     params.validate()
     if isinstance(data, str):
         data = read_matrix(data)
-    data = np.ascontiguousarray(data, dtype=np.float32)
+    if _capi.is_sparse(data):
+        # a scipy.sparse matrix reaches the sparse model in compressed form (never densified: cogaps_session_create_sparse); the dense
+        # model takes a dense matrix
+        data = data.astype(np.float32) if params.sparseOptimization else np.ascontiguousarray(data.toarray(), dtype=np.float32)
+    else:
+        data = np.ascontiguousarray(data, dtype=np.float32)
     unc = None if uncertainty is None else np.ascontiguousarray(read_matrix(uncertainty) if isinstance(uncertainty, str) else uncertainty, dtype=np.float32)
     check_inputs(data, unc, params, snapshotPhase, nSnapshots, checkpointInFile, nThreads)
     if not asynchronousUpdates:

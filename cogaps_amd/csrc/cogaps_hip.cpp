@@ -15,6 +15,7 @@
 #include "chain_kernel.h"
 #include "aux_kernels.h"
 #include "sparse_kernels.h"
+#include "sparse_build.h"
 
 #include <math.h>
 #include <cmath>
@@ -308,6 +309,9 @@ struct cogaps_session {
     unsigned computeUnits = 0;      // of the session's device: the chained launch wants all its workgroups resident at once, one per compute unit
     EventPool ev;
     GenScalars *hGs = nullptr;    // pinned staging
+    std::atomic<uint64_t> deviceBytes{0};      // device memory the session holds (rt_owner_scope; cogaps_session_device_bytes)
+    float orderedSumMs = 0.f;     // ... and what the ordered sums of the packed values took at its creation (HIP events)
+    bool sparseInput = false;     // created from a compressed-sparse matrix: no dense D / S2 / Sraw exist, meanChiSq reads the packed data
     bool poisoned = false;        // a device error ended an update half way (capacity, a hand-over inside a launch that never arrived): the chain's state is not a state of the chain
 };
 
@@ -338,6 +342,47 @@ static void free_sampler(HostSampler &h)
     rt_free((void *)d.dflags); rt_free((void *)d.dprefix); rt_free((void *)d.dptr); rt_free((void *)d.dvals); rt_free(d.rows); rt_free(d.mflags); rt_free(d.Z1); rt_free(d.Z2);
 }
 
+static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha);
+// dimensions of a sampler over nS data vectors of nG elements
+static void sampler_dims(cogaps_session *s, HostSampler &h, char name, uint32_t nG, uint32_t nS)
+{
+    const cogaps_params &p = s->p;
+    SamplerDev &d = h.d; memset(&d, 0, sizeof(d)); h.name = name;
+    d.N = nG; d.M = nS; d.K = p.nPatterns;
+    d.seq = p.reductionMode == COGAPS_REDUCE_SEQ ? 1u : 0u; d.mathMode = (uint32_t)p.mathMode;
+    d.Npad = (d.N + 3u) & ~3u; d.Mpad = (d.M + 3u) & ~3u;
+    d.redW = cogaps_reduction_width(d.N);
+    if (p.useSparseOptimization) {
+        if (d.K > SP_KMAX) throw std::runtime_error("useSparseOptimization supports at most 512 patterns");
+        d.Wn = d.N / 64u + 1u;
+    }
+}
+// the DenseNormalModel constructor's constants (DenseNormalModel.h:66-88) from the data's ordered sum and its count of entries > 0
+static void sampler_model(HostSampler &h, float alpha, float maxGibbsMass, float sum, unsigned nnz)
+{
+    SamplerDev &d = h.d;
+    const float meanD = sum / (float)nnz;
+    h.dataSparsity = 1.f - (float)(uint32_t)nnz / (float)(d.M * d.N);       // gaps::sparsity, MatrixMath.cpp:6-21 (unsigned count, float product of the dimensions)
+    d.alpha = alpha;
+    d.lambda = alpha * sqrtf((float)(uint64_t)d.K / meanD);
+    d.maxGibbsMass = maxGibbsMass / d.lambda;
+    d.unitBytes = 4u * d.N;
+}
+// the sparse model beside its packed data (dflags, dprefix, dptr, dvals: the caller's): the HybridMatrix copies and the lookup tables
+static void sampler_sparse_model(HostSampler &h)
+{
+    SamplerDev &d = h.d;
+    d.sparse = 1; d.beta = 100.f; d.unitBytes = 1u;
+    d.Mw = d.M / 64u + 1u; d.Kpad = (d.K + 3u) & ~3u; d.spW = cogaps_sparse_width(d.N);
+    d.rows = dalloc<float>((size_t)d.M * d.Kpad);
+    d.mflags = dalloc<unsigned long long>((size_t)d.K * d.Mw);
+    d.Z1 = dalloc<float>(d.K); d.Z2 = dalloc<float>((size_t)d.K * d.K);
+    if (d.seq) {
+        if (d.Wn > (uint32_t)SP_SEQ_WORDS) throw std::runtime_error("reductionMode SEQ with the sparse model supports data vectors of up to 262080 elements");
+        d.seqScratch = dalloc<float>((size_t)SEQ_SPARSE_GRID * 3u * d.Npad);
+    }
+}
+
 // Matrix(mat, genesInCols, subsetGenes, indices) (data_structures/Matrix.cpp:30-69) laid out as
 // [vector j][element i] + the DenseNormalModel constructor (DenseNormalModel.h:66-88)
 static void build_sampler(cogaps_session *s, HostSampler &h, char name, const float *data, uint32_t nrow, uint32_t ncol, const float *unc,
@@ -348,22 +393,14 @@ static void build_sampler(cogaps_session *s, HostSampler &h, char name, const fl
     const uint32_t *indices = s->subset.data(); const uint32_t nIdx = (uint32_t)s->subset.size();
     const uint32_t nG = (subsetData && subsetGenes) ? nIdx : (genesInCols ? ncol : nrow);
     const uint32_t nS = (subsetData && !subsetGenes) ? nIdx : (genesInCols ? nrow : ncol);
-    SamplerDev &d = h.d; memset(&d, 0, sizeof(d)); h.name = name;
-    const bool sparse = p.useSparseOptimization != 0;
-    d.N = nG; d.M = nS; d.K = p.nPatterns;
-    d.seq = p.reductionMode == COGAPS_REDUCE_SEQ ? 1u : 0u; d.mathMode = (uint32_t)p.mathMode;
-    d.Npad = (d.N + 3u) & ~3u; d.Mpad = (d.M + 3u) & ~3u;
-    d.redW = cogaps_reduction_width(d.N);
+    SamplerDev &d = h.d; const bool sparse = p.useSparseOptimization != 0;
+    sampler_dims(s, h, name, nG, nS);
     const size_t tot = (size_t)d.M * d.Npad;
     // With the default uncertainty the evaluation kernel recomputes S*S = max(0.1 D, 0.1)^2 from the D value it loads anyway
     // (bit-identical: the same three fp32 operations as the fill below): no S2 array, one row less per proposal from HBM.
     // (COGAPS_READ_S: diagnostics, keeps the array and the loads.)
     const bool defaultS = !sparse && unc == nullptr && !dev_env("COGAPS_READ_S");
     float *dD = dalloc<float>(tot), *dS2 = defaultS ? nullptr : dalloc<float>(tot); h.Sraw = dalloc<float>(tot);
-    if (sparse) {
-        if (d.K > SP_KMAX) throw std::runtime_error("useSparseOptimization supports at most 512 patterns");
-        d.Wn = d.N / 64u + 1u;
-    }
     // The vectors are staged through the host in blocks of at most 16 M elements (pad: D = 0, S = S2 = 1) -- never three dense
     // host copies of the matrix (BASELINE configs[4]'s shard is 2.5 GB per copy).  The sums run over the vectors in order, as
     // gaps::nonZeroMean does (MatrixMath.cpp:39-55).
@@ -399,32 +436,27 @@ static void build_sampler(cogaps_session *s, HostSampler &h, char name, const fl
         rt_h2d(dD + off, D.data(), cnt * 4, s->stream); if (dS2) rt_h2d(dS2 + off, S2.data(), cnt * 4, s->stream); rt_h2d(h.Sraw + off, SR.data(), cnt * 4, s->stream);
         rt_sync(s->stream);                                                     // the staging buffers are reused by the next block
     }
-    const float meanD = sum / (float)nnz;
-    h.dataSparsity = 1.f - (float)(uint32_t)nnz / (float)(d.M * d.N);       // gaps::sparsity, MatrixMath.cpp:6-21 (unsigned count, float product of the dimensions)
-    d.alpha = alpha;
-    d.lambda = alpha * sqrtf((float)(uint64_t)d.K / meanD);
-    d.maxGibbsMass = maxGibbsMass / d.lambda;
+    sampler_model(h, alpha, maxGibbsMass, sum, nnz);
     d.D = dD; d.S2 = dS2; d.defaultS = defaultS ? 1u : 0u;
-    d.unitBytes = 4u * d.N;
     if (!sparse) d.AP = dalloc<float>(tot);
     else {
         // SparseMatrix (flag words + packed values per vector) and the HybridMatrix copies; D / Sraw stay for meanChiSq
-        d.sparse = 1; d.beta = 100.f; d.unitBytes = 1u;
-        d.Mw = d.M / 64u + 1u; d.Kpad = (d.K + 3u) & ~3u; d.spW = cogaps_sparse_width(d.N);
         ptr[d.M] = (uint32_t)vals.size();
         unsigned long long *dfl = dalloc<unsigned long long>(fl.size()); uint32_t *dpre = dalloc<uint32_t>(pre.size()), *dptr = dalloc<uint32_t>(ptr.size()); float *dv = dalloc<float>(vals.size() + 1);
         rt_h2d(dfl, fl.data(), fl.size() * 8, s->stream); rt_h2d(dpre, pre.data(), pre.size() * 4, s->stream); rt_h2d(dptr, ptr.data(), ptr.size() * 4, s->stream);
         if (!vals.empty()) rt_h2d(dv, vals.data(), vals.size() * 4, s->stream);
         rt_sync(s->stream);
         d.dflags = dfl; d.dprefix = dpre; d.dptr = dptr; d.dvals = dv;
-        d.rows = dalloc<float>((size_t)d.M * d.Kpad);
-        d.mflags = dalloc<unsigned long long>((size_t)d.K * d.Mw);
-        d.Z1 = dalloc<float>(d.K); d.Z2 = dalloc<float>((size_t)d.K * d.K);
-        if (d.seq) {
-            if (d.Wn > (uint32_t)SP_SEQ_WORDS) throw std::runtime_error("reductionMode SEQ with the sparse model supports data vectors of up to 262080 elements");
-            d.seqScratch = dalloc<float>((size_t)SEQ_SPARSE_GRID * 3u * d.Npad);
-        }
+        sampler_sparse_model(h);
     }
+    sampler_domain(s, h, alpha);
+}
+
+// the sampler's own state behind its data: the matrix, the atomic domain, the proposal queue (the seed of the queue's generator is
+// the session seeder's next output: A's sampler first, then P's)
+static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha)
+{
+    SamplerDev &d = h.d;
     d.mat = dalloc<float>((size_t)d.K * d.Mpad);
     d.colPos = dalloc<uint32_t>(d.K);
     d.luts.erf = s->dErf; d.luts.erfinv = s->dErfinv; d.luts.qgamma = s->dQgamma;
@@ -460,6 +492,75 @@ static void build_sampler(cogaps_session *s, HostSampler &h, char name, const fl
     h.partial = dalloc<float>(d.M);
 }
 
+// Both samplers of a session from a compressed-sparse matrix (sparse_build.h): the packed structures build_sampler makes from the dense
+// form of the same matrix, built on the device.  No nrow x ncol array exists on either side: d.D, d.S2 and h.Sraw stay null.
+static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
+{
+    const cogaps_params &p = s->p;
+    const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
+    const uint32_t nGenes = p.transposeData ? m.ncol : m.nrow, nSamples = p.transposeData ? m.nrow : m.ncol;
+    // the caller's three arrays on the device: uploaded once (temporaries: released below, not the session's), or used where they are
+    uint64_t nnz = 0;
+    if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, s->stream); rt_sync(s->stream); } else nnz = m.indptr[nMajor];
+    if (nnz >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+    if (nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
+    struct Temps { void *p[4] = {nullptr, nullptr, nullptr, nullptr}; ~Temps() { for (void *q : p) rt_free(q); } } tmp;
+    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz; in.indptr = m.indptr; in.indices = m.indices; in.values = m.values;
+    uint32_t *err;
+    {
+        rt_owner_scope notTheSessions(nullptr);
+        if (!m.onDevice) {
+            uint64_t *ip = dalloc<uint64_t>((size_t)nMajor + 1); tmp.p[0] = ip; uint32_t *ix = dalloc<uint32_t>(nnz + 1); tmp.p[1] = ix; float *vv = dalloc<float>(nnz + 1); tmp.p[2] = vv;
+            rt_h2d(ip, m.indptr, ((size_t)nMajor + 1) * 8, s->stream);
+            if (nnz) { rt_h2d(ix, m.indices, nnz * 4, s->stream); rt_h2d(vv, m.values, nnz * 4, s->stream); }
+            in.indptr = ip; in.indices = ix; in.values = vv;
+        }
+        err = dalloc<uint32_t>(4); tmp.p[3] = err;      // the error word, the two ordered sums
+    }
+    // sampler A: vectors = genes, elements = samples; P the other way round (GapsRunner.cpp:402-406).  Genes are the data's rows unless
+    // transposeData; the sampler whose vector axis is the input's minor axis takes its entries transposed (SpbSide::swap)
+    sampler_dims(s, s->A, 'A', nSamples, nGenes); sampler_dims(s, s->P, 'P', nGenes, nSamples);
+    const bool genesAreRows = !p.transposeData;
+    SpbSide side[2];
+    HostSampler *hs[2] = {&s->A, &s->P};
+    for (int w = 0; w < 2; ++w) {
+        SamplerDev &d = hs[w]->d; SpbSide &sd = side[w];
+        const bool vectorsAreRows = (w == 0) == genesAreRows;
+        sd.M = d.M; sd.Wn = d.Wn; sd.swap = vectorsAreRows == (m.majorIsRow != 0) ? 0u : 1u; sd.vals = nullptr;
+        sd.flags = dalloc<unsigned long long>((size_t)d.M * d.Wn); sd.prefix = dalloc<uint32_t>((size_t)d.M * d.Wn); sd.ptr = dalloc<uint32_t>((size_t)d.M + 1);
+        d.dflags = sd.flags; d.dprefix = sd.prefix; d.dptr = sd.ptr;      // (the session's from here on: free_sampler releases them if anything below throws)
+    }
+    const uint32_t sliceGrid = (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
+    RT_LAUNCH(spb_validate_count_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1], err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, s->stream); rt_sync(s->stream);
+    if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
+    if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
+    if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
+    uint32_t kept[2] = {0, 0};
+    for (int w = 0; w < 2; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, s->stream); }
+    rt_sync(s->stream);
+    if (kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
+    for (int w = 0; w < 2; ++w) {
+        side[w].vals = dalloc<float>((size_t)kept[w] + 1); hs[w]->d.dvals = side[w].vals;
+        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    }
+    RT_LAUNCH(spb_scatter_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1]);
+    // gaps::nonZeroMean (MatrixMath.cpp:39-55): each sampler's sum in the order of its own vectors
+    float *sums = (float *)(err + 1);
+    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);      // (its time is reported: cogaps_session_sparse_build_ms)
+    RT_LAUNCH(spb_ordered_sum_kernel, 2, 256, s->stream, (const float *)side[0].vals, (const float *)side[1].vals, kept[0], sums);
+    rt_event_stop(ev, s->stream);
+    float sum[2] = {0.f, 0.f}; rt_d2h(sum, sums, 8, s->stream); rt_sync(s->stream);
+    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
+    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
+    for (int w = 0; w < 2; ++w) {      // (the seeder's outputs: A's queue, then P's -- sampler_domain)
+        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum[w], kept[w]);
+        sampler_sparse_model(*hs[w]);
+        sampler_domain(s, *hs[w], alpha[w]);
+    }
+    s->sparseInput = true;
+}
+
 static void read_gs(cogaps_session *s, HostSampler &h)
 {
     rt_d2h(s->hGs, h.d.gs, sizeof(GenScalars), s->stream);
@@ -491,7 +592,7 @@ static void grow_atoms(cogaps_session *s, HostSampler &h, uint32_t need)
 {
     SamplerDev &d = h.d;
     if (need <= d.atomCap) return;
-    rt_alloc_scope allocOn(s->stream);
+    rt_alloc_scope allocOn(s->stream); rt_owner_scope owner(&s->deviceBytes);
     uint32_t cap = d.atomCap;
     while (cap < need) cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 2, 0x7FFFFFF0ull);
     auto regrow = [&](auto *&ptr, size_t elt) {
@@ -759,6 +860,7 @@ static bool chain_recover(cogaps_session *s, HostSampler &h, uint32_t nSteps)
 // update; the caller uploads them.  Returns the predicted proposals per batch: the previous update of this sampler is the best predictor.
 static float begin_update(cogaps_session *s, HostSampler &h, GenScalars &g, uint32_t n, uint32_t traceCap)
 {
+    rt_owner_scope owner(&s->deviceBytes);      // (a batch steps its sessions from its own scope)
     grow_atoms(s, h, g.nAtoms + n + 1024u);
     if (h.seedCap < (size_t)n + 1) { rt_free(h.seeds); h.seedCap = (size_t)n * 5 / 4 + 1024; h.seeds = dalloc<uint64_t>(h.seedCap); }
     if (h.hSeedCap < (size_t)n + 1) { rt_free_host(h.hSeeds); h.hSeedCap = (size_t)n * 5 / 4 + 1024; h.hSeeds = (uint64_t *)rt_malloc_host(h.hSeedCap * 8); }
@@ -947,11 +1049,23 @@ const char *cogaps_build_report(void)
 int cogaps_checkpoints_enabled(void) { return 0; }
 int cogaps_compiled_with_openmp(void) { return 0; }
 
-cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, int data_on_device)
+} // extern "C"
+
+// cogaps_session_create (sp == nullptr: the dense matrix `data`) and cogaps_session_create_sparse (sp: the compressed one)
+static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, int data_on_device,
+                                      const cogaps_sparse_matrix *sp)
 {
     cogaps_session *s = nullptr;
     try {
+        if (!params) { fail("null argument"); return nullptr; }
         const cogaps_params &p = *params;
+        if (sp) {
+            nrow = sp->nrow; ncol = sp->ncol;
+            if (!p.useSparseOptimization) { fail("a compressed-sparse matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
+            if (p.subsetData) { fail("subsetData is not supported with a compressed-sparse matrix: pass the rows / columns of the subset"); return nullptr; }
+            if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a compressed-sparse matrix"); return nullptr; }
+            if (!sp->indptr) { fail("null argument: indptr"); return nullptr; }
+        } else if (!data) { fail("null argument: data"); return nullptr; }
         // The reference's distributed caller forces asynchronousUpdates = FALSE on its workers (R/DistributedCogaps.R:28-29) -- there to keep
         // BiocParallel workers single-threaded, not for the sampler's sake.  Documented deviation: a
         // distributed worker call (runningDistributed, i.e. subsetDim > 0 in cogaps_cpp, Cogaps.cpp:82) runs the asynchronous sampler anyway,
@@ -980,7 +1094,7 @@ cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t
         if (p.printMessages) { printf("Loading Data..."); fflush(stdout); }                  // GapsRunner.cpp:399
         if (p.subsetData && p.dataIndicesSubset) s->subset.assign(p.dataIndicesSubset, p.dataIndicesSubset + p.nSubset);
         s->stream = rt_stream_create();
-        rt_alloc_scope allocOn(s->stream);
+        rt_alloc_scope allocOn(s->stream); rt_owner_scope owner(&s->deviceBytes);
         std::vector<float> hostData, hostUnc;
         if (data_on_device) {          // device-resident input: stage through the host once, outside any timed region
             hostData.resize((size_t)nrow * ncol); rt_d2h(hostData.data(), data, hostData.size() * 4, s->stream);
@@ -1000,8 +1114,11 @@ cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t
         rt_sync(s->stream);
         // samplers: A on the transposed data with the subset flag flipped (GapsRunner.cpp:402-406);
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
+        if (sp) build_samplers_sparse_input(s, *sp);
+        else {
         build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
         build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
+        }
         s->nGenes = s->A.d.M; s->nSamples = s->P.d.M; s->K = p.nPatterns;
         if (s->A.d.N != s->P.d.M || s->P.d.N != s->A.d.M) throw std::runtime_error("internal: sampler dimensions do not mirror");
         s->A.d.other = s->P.d.mat; s->A.d.otherColPos = s->P.d.colPos;
@@ -1061,6 +1178,31 @@ cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t
     }
 }
 
+extern "C" {
+
+cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, int data_on_device)
+{
+    return session_create(data, nrow, ncol, params, unc, data_on_device, nullptr);
+}
+cogaps_session *cogaps_session_create_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params)
+{
+    if (!m) { fail("null argument"); return nullptr; }
+    return session_create(nullptr, 0, 0, params, nullptr, 0, m);
+}
+int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes)
+{
+    if (!s || !bytes) return fail("null argument");
+    *bytes = s->deviceBytes.load();
+    return 0;
+}
+
+int cogaps_session_sparse_build_ms(cogaps_session *s, float *orderedSumMs)
+{
+    if (!s || !orderedSumMs) return fail("null argument");
+    *orderedSumMs = s->orderedSumMs;
+    return 0;
+}
+
 void cogaps_session_destroy(cogaps_session *s)
 {
     if (!s) return;
@@ -1074,7 +1216,7 @@ void cogaps_session_destroy(cogaps_session *s)
 }
 
 // (the HIP current device belongs to the calling host thread: a session used from another thread than its creator's selects its GPU again)
-#define SESSION_TRY try { rt_set_device(s->p.device); rt_alloc_scope allocOn_(s->stream);      // allocations made on behalf of a session fill on its stream
+#define SESSION_TRY try { rt_set_device(s->p.device); rt_alloc_scope allocOn_(s->stream); rt_owner_scope owner_(&s->deviceBytes);      // allocations made on behalf of a session fill on its stream
 #define SESSION_END } catch (const std::exception &e) { return fail_exc(e); } return 0;
 
 static HostSampler &pick(cogaps_session *s, char w) { return w == 'A' ? s->A : s->P; }
@@ -1602,7 +1744,8 @@ int cogaps_session_finish(cogaps_session *s, cogaps_result *out)
             RT_LAUNCH(mean_chisq_seq_kernel, 1, 256, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
             rt_d2h(&out->meanChiSq, s->P.partial, 4, s->stream); rt_sync(s->stream);
         } else {
-        LAUNCH_V(mean_chisq_rows_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
+        if (s->sparseInput) LAUNCH_V(mean_chisq_rows_packed_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);      // (no dense D / Sraw: sparse_build.h)
+        else LAUNCH_V(mean_chisq_rows_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
         std::vector<float> part(s->P.d.M);
         rt_d2h(part.data(), s->P.partial, (size_t)s->P.d.M * 4, s->stream); rt_sync(s->stream);
         float c = 0.f; for (uint32_t j = 0; j < s->P.d.M; ++j) c += part[j];
@@ -1788,6 +1931,38 @@ int cogaps_session_chained(cogaps_session *s, char which, int *chained)
 int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)
 {
     cogaps_session *s = cogaps_session_create(data, nrow, ncol, params, unc, 0);
+    if (!s) return 1;
+    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_finish(s, out);
+    cogaps_session_destroy(s);
+    return rc;
+}
+
+int cogaps_session_debug_sparse_data(cogaps_session *s, char which, uint32_t *Wn, uint32_t *nVals, float *lambda, float *maxGibbsMass,
+                                     uint64_t *flags, uint32_t *prefix, uint32_t *ptr, float *vals)
+{
+    if (!s) return fail("null argument");
+    SESSION_TRY
+    const SamplerDev &d = pick(s, which).d;
+    if (!d.sparse) return fail("the session does not run the sparse model");
+    uint32_t n = 0; rt_d2h(&n, d.dptr + d.M, 4, s->stream); rt_sync(s->stream);
+    if (Wn) *Wn = d.Wn;
+    if (nVals) *nVals = n;
+    if (lambda) *lambda = d.lambda;
+    if (maxGibbsMass) *maxGibbsMass = d.maxGibbsMass;
+    if (flags) rt_d2h(flags, d.dflags, (size_t)d.M * d.Wn * 8, s->stream);
+    if (prefix) rt_d2h(prefix, d.dprefix, (size_t)d.M * d.Wn * 4, s->stream);
+    if (ptr) rt_d2h(ptr, d.dptr, ((size_t)d.M + 1) * 4, s->stream);
+    if (vals && n) rt_d2h(vals, d.dvals, (size_t)n * 4, s->stream);
+    rt_sync(s->stream);
+    SESSION_END
+}
+
+int cogaps_run_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params, cogaps_result *out)
+{
+    if (!out) return fail("null argument");
+    cogaps_session *s = cogaps_session_create_sparse(m, params);
     if (!s) return 1;
     int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
     if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);

@@ -9,6 +9,9 @@
 #include <string.h>
 #include <string>
 #include <stdexcept>
+#include <atomic>
+#include <mutex>
+#include <unordered_map>
 
 // device memory exhausted (hipErrorOutOfMemory): its own type, so that the C ABI can report it as a code (cogaps_last_error_code) and a
 // caller can retry with fewer sessions in flight without reading message texts
@@ -17,10 +20,10 @@ struct rt_out_of_memory : std::runtime_error { explicit rt_out_of_memory(const s
 #if defined(COGAPS_EMUL)
 
 typedef int rt_stream_t;
-inline void *rt_malloc(size_t n) { void *p = calloc(n ? n : 1, 1); if (!p) throw rt_out_of_memory("out of memory"); return p; }
+inline void *rt_malloc_raw(size_t n) { void *p = calloc(n ? n : 1, 1); if (!p) throw rt_out_of_memory("out of memory"); return p; }
 struct rt_alloc_scope { explicit rt_alloc_scope(rt_stream_t) {} };
-inline void rt_free(void *p) { free(p); }
-inline void *rt_malloc_host(size_t n) { return rt_malloc(n); }
+inline void rt_free_raw(void *p) { free(p); }
+inline void *rt_malloc_host(size_t n) { return rt_malloc_raw(n); }
 inline void rt_free_host(void *p) { free(p); }
 inline void rt_h2d(void *d, const void *h, size_t n, rt_stream_t) { memcpy(d, h, n); }
 inline void rt_d2h(void *h, const void *d, size_t n, rt_stream_t) { memcpy(h, d, n); }
@@ -65,7 +68,7 @@ struct rt_alloc_scope {
     explicit rt_alloc_scope(hipStream_t s) : prev(rt_alloc_stream_slot()) { rt_alloc_stream_slot() = s; }
     ~rt_alloc_scope() { rt_alloc_stream_slot() = prev; }
 };
-inline void *rt_malloc(size_t n)
+inline void *rt_malloc_raw(size_t n)
 {
     void *p = nullptr; RT_CHECK(hipMalloc(&p, n ? n : 1));
     hipStream_t f = rt_alloc_stream_slot();
@@ -75,7 +78,7 @@ inline void *rt_malloc(size_t n)
     if (temp) (void)hipStreamDestroy(f);
     return p;
 }
-inline void rt_free(void *p) { if (p) (void)hipFree(p); }
+inline void rt_free_raw(void *p) { if (p) (void)hipFree(p); }
 inline void *rt_malloc_host(size_t n) { void *p = nullptr; RT_CHECK(hipHostMalloc(&p, n ? n : 1, hipHostMallocDefault)); return p; }
 inline void rt_free_host(void *p) { if (p) (void)hipHostFree(p); }
 inline void rt_h2d(void *d, const void *h, size_t n, rt_stream_t s) { RT_CHECK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); }
@@ -109,3 +112,34 @@ inline void rt_graph_destroy(rt_graph &gr) { if (gr.e) (void)hipGraphExecDestroy
 inline const char *rt_platform_name() { return "HIP gfx950"; }
 
 #endif
+
+// Device memory with an owner (cogaps_session_device_bytes): an allocation made while the calling thread has announced a byte counter
+// (rt_owner_scope: a session's) adds its size to that counter, its release takes it off again -- whichever thread releases it.  Sizes are
+// the requested ones.  The counter must outlive the allocations it owns (a session frees its memory before it goes).
+struct rt_alloc_book { std::mutex m; std::unordered_map<void *, std::pair<size_t, std::atomic<uint64_t> *>> live; };
+inline rt_alloc_book &rt_book() { static rt_alloc_book b; return b; }
+inline std::atomic<uint64_t> *&rt_owner_slot() { static thread_local std::atomic<uint64_t> *o = nullptr; return o; }
+struct rt_owner_scope {
+    std::atomic<uint64_t> *prev;
+    explicit rt_owner_scope(std::atomic<uint64_t> *o) : prev(rt_owner_slot()) { rt_owner_slot() = o; }
+    ~rt_owner_scope() { rt_owner_slot() = prev; }
+};
+inline void *rt_malloc(size_t n)
+{
+    void *p = rt_malloc_raw(n);
+    if (std::atomic<uint64_t> *o = rt_owner_slot()) {
+        std::lock_guard<std::mutex> g(rt_book().m);
+        rt_book().live[p] = {n, o}; o->fetch_add(n);
+    }
+    return p;
+}
+inline void rt_free(void *p)
+{
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> g(rt_book().m);
+        auto it = rt_book().live.find(p);
+        if (it != rt_book().live.end()) { it->second.second->fetch_sub(it->second.first); rt_book().live.erase(it); }
+    }
+    rt_free_raw(p);
+}

@@ -1,0 +1,168 @@
+// sparse_build.h -- the sparse model's data structures built on the device from a compressed-sparse matrix (CSR or CSC), and
+// meanChiSq from them: what build_sampler (cogaps_hip.cpp) builds on the host from a dense matrix, bit for bit, without an
+// nrow x ncol array anywhere.
+//
+// A sampler holds its data as [vector j][element i]: dflags [M][Wn] (bit i of vector j: the entry is > 0), dprefix [M][Wn] (packed
+// values of the vector before each flag word), dptr [M + 1] (first packed value of each vector), dvals (the values > 0, vector by
+// vector, ascending element index).  For one sampler the input's major axis is the vector axis, for the other the element axis
+// (SpbSide::swap); both are built by the same three passes, none of which depends on the order in which the entries arrive:
+//   1. spb_validate_count_kernel: checks the input, counts the kept entries per vector into dptr, sets the flag bits (64-bit atomic OR)
+//   2. spb_scan_kernel: dptr = exclusive scan of the counts; spb_prefix_kernel: dprefix = popcount scan over each vector's flag words
+//   3. spb_scatter_kernel: every kept entry computes its own slot dptr[j] + dprefix[j][i >> 6] + popcount(flags below bit i)
+// and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order -- the sum build_sampler forms
+// over the dense elements in (j, i) order (zeros add nothing), which feeds lambda.
+#pragma once
+#include "gaps_state.h"
+#include "eval_kernel.h"
+#include "aux_kernels.h"
+
+// what the validation found (the largest code wins; 0 = well formed)
+#define SPB_ERR_ORDER 1u        // indices not strictly ascending inside a major slice (a duplicate included)
+#define SPB_ERR_RANGE 2u        // an index >= nMinor
+#define SPB_ERR_INDPTR 3u       // indptr does not start at 0, decreases, or runs past indptr[nMajor]
+
+struct SpbIn {
+    const uint64_t *indptr; const uint32_t *indices; const float *values;
+    uint32_t nMajor, nMinor; uint64_t nnz;
+};
+struct SpbSide {
+    unsigned long long *flags; uint32_t *prefix, *ptr; float *vals;
+    uint32_t M, Wn, swap;      // swap: the vector index is the entry's minor index (0: its major index)
+};
+#define SPB_WAVES 4      // major slices (or vectors) per workgroup: one wave each
+
+CG_DEVICE void spb_slice(const SpbIn &in, uint32_t m, uint64_t &b, uint64_t &e)
+{
+    b = e = 0;
+    if (m < in.nMajor) { b = in.indptr[m]; e = in.indptr[m + 1]; }
+}
+CG_DEVICE void spb_place(const SpbSide &s, uint32_t major, uint32_t minor, uint32_t &vec, uint32_t &el)
+{
+    vec = s.swap ? minor : major; el = s.swap ? major : minor;
+}
+
+// One wave per major slice: the slice's bounds, every index against nMinor and against its predecessor; the entries > 0 are counted
+// per major slice (one store per wave) and per minor index (one integer atomic each: the indices of a slice differ), and set their bit
+// in both samplers' flag words.  Nothing is read outside [0, nnz) and nothing written outside the two samplers' arrays whatever the
+// input holds; what is written for a malformed input is never used (the host reads *err first).
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_validate_count_kernel(SpbIn in, SpbSide a, SpbSide b, uint32_t *err)
+{
+    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    uint64_t lo, hi; spb_slice(in, m, lo, hi);
+    if (m == 0u && m < in.nMajor && lo != 0ull) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); }
+    if (lo > hi || hi > in.nnz) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); hi = lo = 0; }
+    uint32_t kept = 0;
+    for (uint64_t k = lo + lane; k < hi; k += 64u) {
+        const uint32_t idx = in.indices[k];
+        if (idx >= in.nMinor) { cg_atomic_max_u32(err, SPB_ERR_RANGE); continue; }
+        if (k > lo && in.indices[k - 1] >= idx) cg_atomic_max_u32(err, SPB_ERR_ORDER);
+        if (!(in.values[k] > 0.f)) continue;                              // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
+        ++kept;
+        uint32_t vec, el;
+        spb_place(a, m, idx, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
+        spb_place(b, m, idx, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
+        cg_atomic_add_u32((a.swap ? a.ptr : b.ptr) + idx, 1u);
+    }
+    kept = cg_wave_sum_u32(kept);
+    if (lane == 0u && m < in.nMajor) (a.swap ? b.ptr : a.ptr)[m] = kept;
+}
+
+// cnt[0 .. n) -> their exclusive prefix sums, cnt[n] = the total.  One workgroup of 1024 threads: a contiguous run of the array per
+// thread, the runs' sums scanned through LDS (n is a matrix dimension: at most a few 10^5).
+#define SPB_SCAN_BS 1024
+CG_KERNEL void CG_LAUNCH_BOUNDS(SPB_SCAN_BS) spb_scan_kernel(uint32_t *cnt, uint32_t n)
+{
+    CG_SHARED uint32_t run[SPB_SCAN_BS];
+    const uint32_t t = cg_tid(), per = (n + (uint32_t)SPB_SCAN_BS - 1u) / (uint32_t)SPB_SCAN_BS;
+    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; ++i) sum += cnt[i];
+    run[t] = sum; cg_sync();
+    for (uint32_t off = 1; off < (uint32_t)SPB_SCAN_BS; off <<= 1) {      // inclusive scan of the runs' sums
+        const uint32_t o = t >= off ? run[t - off] : 0u;
+        cg_sync();
+        run[t] += o; cg_sync();
+    }
+    uint32_t acc = run[t] - sum;
+    for (uint32_t i = lo; i < hi; ++i) { const uint32_t c = cnt[i]; cnt[i] = acc; acc += c; }
+    if (t == (uint32_t)SPB_SCAN_BS - 1u) cnt[n] = run[t];
+}
+
+// dprefix[j][w] = entries of vector j below flag word w -- all Wn words, the word past the last element (Wn = N/64 + 1) included, as
+// build_sampler fills them.  One wave per vector, 64 words per round.
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_prefix_kernel(SpbSide s)
+{
+    const uint32_t lane = cg_tid() & 63u, j = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    const bool live = j < s.M;
+    uint32_t carry = 0;
+    for (uint32_t w0 = 0; w0 < s.Wn; w0 += 64u) {
+        const uint32_t w = w0 + lane; const bool on = live && w < s.Wn;
+        const uint32_t pc = on ? (uint32_t)cg_popc64(s.flags[(size_t)j * s.Wn + w]) : 0u;
+        uint32_t total; const uint32_t before = cg_wave_excl_scan_u32(pc, total);
+        if (on) s.prefix[(size_t)j * s.Wn + w] = carry + before;
+        carry += total;
+    }
+}
+
+CG_DEVICE void spb_store(const SpbSide &s, uint32_t major, uint32_t minor, float v)
+{
+    uint32_t vec, el; spb_place(s, major, minor, vec, el);
+    const size_t w = (size_t)vec * s.Wn + (el >> 6);
+    s.vals[s.ptr[vec] + s.prefix[w] + (uint32_t)cg_popc64(s.flags[w] & ((1ull << (el & 63u)) - 1ull))] = v;
+}
+// every kept entry to its slot in both samplers' packed values (validated input only: the slots are then distinct and below ptr[M])
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_scatter_kernel(SpbIn in, SpbSide a, SpbSide b)
+{
+    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    uint64_t lo, hi; spb_slice(in, m, lo, hi);
+    for (uint64_t k = lo + lane; k < hi; k += 64u) {
+        const float v = in.values[k];
+        if (!(v > 0.f)) continue;
+        const uint32_t idx = in.indices[k];
+        spb_store(a, m, idx, v); spb_store(b, m, idx, v);
+    }
+}
+
+// out[0], out[1] = 0 + v[0] + v[1] + ... of sampler a's and sampler b's packed values, one accumulator each (seq_sum): workgroup 0
+// and workgroup 1.  The order of the additions is the result; a tree or an atomic sum would give other bits.
+CG_KERNEL void CG_LAUNCH_BOUNDS(256) spb_ordered_sum_kernel(const float *va, const float *vb, uint32_t n, float *out)
+{
+    CG_SHARED float lds[SEQ_CHUNK];
+    const float *v = cg_bid() == 0u ? va : vb;
+    const float c = seq_sum(0.f, (uint64_t)n, lds, [&](uint64_t e) { return v[e]; });
+    if (cg_tid() == 0) out[cg_bid()] = c;
+}
+
+// GapsStatistics::meanChiSq per-vector partials (aux_kernels.h, mean_chisq_rows_kernel) with the data taken from the P sampler's packed
+// form: d = the packed value where the flag bit is set, 0 elsewhere, sd = max(0.1 d, 0.1) -- the three fp32 operations that fill Sraw
+// in build_sampler.  Same lanes, chunks, slots and finish as the dense-input kernel: the partials are the same bits.
+template <int V>
+CG_KERNEL void CG_LAUNCH_BOUNDS(1024) mean_chisq_rows_packed_kernel(SamplerDev P, const float *Asum, const float *Psum, uint32_t AMpad, float n2, float *partial)
+{
+    CG_SHARED float lds[16 * V];
+    const uint32_t j = cg_bid(), t = cg_tid(), BS = cg_bdim(), W = (uint32_t)V * BS, nq = P.Npad >> 2;
+    const unsigned long long *fl = P.dflags + (size_t)j * P.Wn; const uint32_t *pre = P.dprefix + (size_t)j * P.Wn;
+    const float *vals = P.dvals + P.dptr[j];
+    float tot[1] = {0.f};
+    for (int slot = 0; slot < V; ++slot) {
+        float acc = 0.f;
+        for (uint32_t c = (uint32_t)slot * BS + t; c < nq; c += W) {
+            const unsigned long long word = fl[c >> 4]; const uint32_t base = pre[c >> 4];      // (the chunk's four elements share a flag word)
+            for (uint32_t e = 0; e < 4; ++e) {
+                const uint32_t i = 4 * c + e;
+                if (i < P.N) {
+                    const unsigned long long bit = 1ull << (i & 63u);
+                    const float d = (word & bit) ? vals[base + (uint32_t)cg_popc64(word & (bit - 1ull))] : 0.f;
+                    const float sd = gm_max(d * 0.1f, 0.1f);
+                    float m = 0.f;
+                    for (uint32_t k = 0; k < P.K; ++k) m = m + Asum[(size_t)k * AMpad + i] * Psum[(size_t)k * P.Mpad + j];
+                    m = m / n2;
+                    acc = acc + ((d - m) * (d - m)) / (sd * sd);
+                }
+            }
+        }
+        eval_vpark<V>(acc, slot, lds, tot);
+    }
+    if (BS > 64u) { cg_sync(); eval_vfinish<1, V>(lds, tot); }
+    if (t == 0) partial[j] = tot[0];
+}

@@ -292,6 +292,12 @@ def _run_shards(spec, ids, in_flight, run_fn, shape_of=None):
         # HBM; the sparse model keeps the dense data and uncertainty for meanChiSq plus the packed vectors: counted as 5
         g0_, s0_, sparse0, unc0 = shape_of(ids[0])
         per_shard = (5 if sparse0 else (13 if unc0 else 10)) * 4 * max(g_ * s_ for g_, s_, _, _ in (shape_of(i) for i in ids)) + (64 << 20)
+        nnz_of = getattr(shape_of, "nnz", None)
+        if sparse0 and nnz_of is not None:
+            # compressed-sparse input: no dense copy exists.  Per stored entry 4 bytes of packed values in each sampler and, while the
+            # session is created, the 8 bytes of the uploaded index / value pair; per matrix element 1/8 byte of flag words and 1/16 byte
+            # of prefix counts in each sampler
+            per_shard = max(16 * nnz_of(i) + (3 * shape_of(i)[0] * shape_of(i)[1]) // 8 for i in ids) + (64 << 20)
         device = spec.device if hasattr(spec, "device") else -1
         free_bytes, _ = _capi.device_memory(device)
         in_flight = max(1, min(in_flight, int(0.85 * free_bytes // per_shard)))
@@ -350,6 +356,8 @@ def _run_shards(spec, ids, in_flight, run_fn, shape_of=None):
 class _Source:
     """Where the shards of a distributed run come from.  `data` is
       * a 2-D array: shard i = its rows / columns sets[i] (in the order given, Matrix(mat, ...), Matrix.cpp:30-69);
+      * a scipy.sparse matrix: the same rows / columns, cut with scipy; with the sparse model (`sparse_model`) the shard stays in
+        compressed form all the way into the library, otherwise it is densified shard by shard;
       * a path to a .mtx / .csv / .tsv / .gct file: every rank reads only ITS shards' rows / columns of the file with the library's
         reader (cogaps_read_matrix_file_subset) -- as the reference's workers do (Matrix(path, ...), Matrix.cpp:70-134), which sorts
         the indices first: the sets are sorted to match;
@@ -357,9 +365,13 @@ class _Source:
         `indices` (rows of the data when the partitioned dimension is the rows, else columns), with `shape` = dimensions of the whole.
     No rank ever materialises the whole matrix unless the caller hands it over as an array."""
 
-    def __init__(self, data, uncertainty, shape, subset_rows):
+    def __init__(self, data, uncertainty, shape, subset_rows, sparse_model=False):
         self.data, self.unc, self.subset_rows = data, uncertainty, subset_rows
         self.kind = "path" if isinstance(data, (str, bytes)) else ("loader" if callable(data) else "array")
+        self.sparse = self.kind == "array" and _capi.is_sparse(data)
+        self.sparse_model = bool(sparse_model)
+        if self.sparse:
+            self.data = data.tocsr() if subset_rows else data.tocsc()      # the form whose major slices the shards are
         if self.kind == "array":
             self.shape = tuple(data.shape)
         elif self.kind == "path":
@@ -377,7 +389,15 @@ class _Source:
     def has_unc(self):
         return self.unc is not None
 
+    def shard_nnz(self, idx1):
+        """stored entries of the shard with the 1-based indices idx1 (compressed-sparse data only)"""
+        return int(np.diff(self.data.indptr)[np.asarray(idx1, dtype=np.int64) - 1].sum())
+
     def shard(self, i, idx1):
+        if self.sparse:
+            idx = np.asarray(idx1, dtype=np.int64) - 1
+            m = self.data[idx, :] if self.subset_rows else self.data[:, idx]
+            return (m if self.sparse_model else np.ascontiguousarray(m.toarray(), dtype=np.float32)), None
         if self.kind == "array":
             idx = idx1 - 1
             cut = (lambda m: np.ascontiguousarray(m[idx, :] if self.subset_rows else m[:, idx], dtype=np.float32))
@@ -401,7 +421,9 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
     shardsInFlight = max(1, int(shardsInFlight))
     genome_wide = params.distributed == "genome-wide"
     subset_rows = bool(transposeData) != genome_wide          # xor, SubsetData.R:87-88
-    src = _Source(data, uncertainty, shape, subset_rows)
+    src = _Source(data, uncertainty, shape, subset_rows, sparse_model=params.sparseOptimization)
+    if src.sparse and uncertainty is not None:
+        raise ValueError("a scipy.sparse data matrix takes no uncertainty matrix")
     total = src.shape[0] if subset_rows else src.shape[1]
     sets = create_sets(total, params, params.geneNames if genome_wide else params.sampleNames)
     if src.kind == "path":
@@ -432,6 +454,8 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         r, c = (len(sets[i]), src.shape[1]) if subset_rows else (src.shape[0], len(sets[i]))
         g_, s_ = (c, r) if transposeData else (r, c)
         return g_, s_, bool(params.sparseOptimization), src.has_unc()
+    if src.sparse and src.sparse_model:
+        shape_of.nnz = lambda i: src.shard_nnz(sets[i])
 
     def make_spec(n_patterns, fixed=None, which="N"):          # callInternalCoGAPS, DistributedCogaps.R:12-35
         def spec(i):

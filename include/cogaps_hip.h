@@ -181,6 +181,43 @@ cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t
                                       const cogaps_params *params, const float *uncertainty,
                                       int data_on_device);
 void cogaps_session_destroy(cogaps_session *s);
+
+/* A matrix in compressed-sparse form -- CSR (majorIsRow = 1) or CSC (0) -- as the input of the sparse model (useSparseOptimization = 1,
+ * the reference's SparseNormalModel).  A scipy.sparse csr_matrix / csc_matrix maps onto it directly, and so does R's dgCMatrix with
+ * majorIsRow = 0: @p -> indptr (widened to 64 bits), @i -> indices, @x -> values (as fp32), @Dim -> nrow, ncol.
+ *
+ * A session created from it is the session cogaps_session_create makes from the dense form of the same matrix, bit for bit: the flag
+ * words, prefix counts, pointers and packed values of both samplers and lambda / maxGibbsMass are built on the device
+ * (csrc/sparse_build.h) and no nrow x ncol array is allocated on the host or on the device.  With host pointers the three arrays are
+ * uploaded once; with onDevice = 1 nothing is copied to the host but indptr[nMajor].  The caller's arrays are not referenced after the
+ * call returns.  Stored entries that are not > 0 (zeros, negatives, NaN) are dropped, as the sparse model drops them from a dense matrix.
+ * Errors (NULL / 1, cogaps_last_error): useSparseOptimization = 0; subsetData (pass the subset's rows / columns instead); reductionMode
+ * COGAPS_REDUCE_SEQ (the verification mode takes dense input for now: a follow-up); indptr that does not start at 0, decreases or does
+ * not end at the number of stored entries; an index >= the minor dimension; indices not strictly ascending inside a row / column
+ * (duplicates included); 2^32 - 1 stored entries or more.  The input is validated on the device before anything is built from it.
+ * transposeData, whichMatrixFixed / fixedPatterns and everything else in cogaps_params work as for the dense entry points; such a session
+ * is an ordinary session (batches, traces, copy-outs, snapshots, PUMP). */
+typedef struct cogaps_sparse_matrix {
+    uint32_t nrow, ncol;        /* of the data as the caller sees it (genes x samples unless transposeData) */
+    int32_t  majorIsRow;        /* 1 = CSR, 0 = CSC */
+    const uint64_t *indptr;     /* [nMajor + 1] */
+    const uint32_t *indices;    /* [nnz] minor indices, strictly ascending inside each major slice */
+    const float    *values;     /* [nnz] */
+    int32_t  onDevice;          /* 0: host pointers, 1: device pointers of params->device */
+} cogaps_sparse_matrix;
+cogaps_session *cogaps_session_create_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params);
+/* cogaps_run for such a matrix (host or device pointers) */
+int cogaps_run_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params, cogaps_result *out);
+/* Bytes of device memory the session holds: the sum of its own allocations (as requested), counted as they are made and released -- not
+ * hipMemGetInfo, which is device-wide.  For every session, however it was created. */
+int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes);
+/* HIP-event time of the two ordered fp32 sums over the packed values at the creation of a session from a compressed-sparse matrix
+ * (the one serial pass of that path; 0 for a session created from a dense matrix) */
+int cogaps_session_sparse_build_ms(cogaps_session *s, float *orderedSumMs);
+/* test hook: the sparse model's data structures of sampler `which` -- flags / prefix [M][Wn], ptr [M + 1], vals [nVals] -- and the
+ * constants derived from the data; NULL skips an output (sizes first, then the arrays) */
+int cogaps_session_debug_sparse_data(cogaps_session *s, char which, uint32_t *Wn, uint32_t *nVals, float *lambda, float *maxGibbsMass,
+                                     uint64_t *flags, uint32_t *prefix, uint32_t *ptr, float *vals);
 /* annealing temperature of both samplers (runOnePhase sets min(1, 2*iter/nIter) while equilibrating) */
 int cogaps_session_set_annealing(cogaps_session *s, float temp);
 /* nA, nP ~ Poisson(max(nAtoms,10)) from the runner's generator (GapsRunner.cpp:294-295) */
