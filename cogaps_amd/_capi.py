@@ -68,6 +68,13 @@ class CogapsSparseMatrixC(C.Structure):
     ]
 
 
+class CogapsCooMatrixC(C.Structure):
+    _fields_ = [
+        ("nrow", C.c_uint32), ("ncol", C.c_uint32), ("nnz", C.c_uint64),
+        ("rows", C.c_void_p), ("cols", C.c_void_p), ("values", C.c_void_p), ("onDevice", C.c_int32),
+    ]
+
+
 TRACE_DTYPE = np.dtype([
     ("pos", "<u8"), ("rng_state", "<u8"), ("atom1", "<u4"), ("atom2", "<u4"),
     ("r1", "<u4"), ("c1", "<u4"), ("r2", "<u4"), ("c2", "<u4"), ("type", "<u4"), ("batch", "<u4"),
@@ -86,6 +93,7 @@ EXPORTS = [
     "cogaps_session_perf_sampler", "cogaps_session_chained", "cogaps_session_chain_recoveries", "cogaps_session_generator_window", "cogaps_session_launch_clock", "cogaps_session_launch_period", "cogaps_session_get_rows", "cogaps_sparse_width", "cogaps_reduction_width", "cogaps_session_debug_prof", "cogaps_session_debug_replay",
     "cogaps_run_from_file", "cogaps_read_matrix_file", "cogaps_read_matrix_file_subset", "cogaps_matrix_free", "cogaps_file_info", "cogaps_debug_math", "cogaps_current_device", "cogaps_device_memory",
     "cogaps_session_create_sparse", "cogaps_run_sparse", "cogaps_session_device_bytes", "cogaps_session_sparse_build_ms", "cogaps_session_debug_sparse_data",
+    "cogaps_session_create_coo", "cogaps_run_coo", "cogaps_read_mtx_triplets", "cogaps_triplets_free",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -134,6 +142,12 @@ def bind(L):
     L.cogaps_session_create_sparse.restype = vp
     L.cogaps_session_create_sparse.argtypes = [C.POINTER(CogapsSparseMatrixC), C.POINTER(CogapsParamsC)]
     L.cogaps_run_sparse.argtypes = [C.POINTER(CogapsSparseMatrixC), C.POINTER(CogapsParamsC), C.POINTER(CogapsResultC)]
+    L.cogaps_session_create_coo.restype = vp
+    L.cogaps_session_create_coo.argtypes = [C.POINTER(CogapsCooMatrixC), C.POINTER(CogapsParamsC)]
+    L.cogaps_run_coo.argtypes = [C.POINTER(CogapsCooMatrixC), C.POINTER(CogapsParamsC), C.POINTER(CogapsResultC)]
+    L.cogaps_read_mtx_triplets.argtypes = [C.c_char_p, C.c_int, u32p, C.c_uint32, u32p, u32p, C.POINTER(C.c_uint64), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(fp)]
+    L.cogaps_triplets_free.argtypes = [u32p, u32p, fp]
+    L.cogaps_triplets_free.restype = None
     L.cogaps_session_device_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cogaps_session_sparse_build_ms.argtypes = [vp, fp]
     L.cogaps_session_debug_sparse_data.argtypes = [vp, C.c_char, u32p, u32p, fp, fp, vp, vp, vp, vp]
@@ -334,10 +348,54 @@ class SparseMatrix:
         return CogapsSparseMatrixC(self.shape[0], self.shape[1], int(self.major_is_row), addr(self.indptr), addr(self.indices), addr(self.values), int(self.on_device))
 
 
+class CooMatrix:
+    """A matrix as unordered triplets as cogaps_coo_matrix takes it (include/cogaps_hip.h): rows / cols uint32 (0-based), values float32,
+    any order, repeats allowed -- the LATEST entry of a position decides it (a Matrix Market file read in file order; not scipy's
+    meaning of COO, which sums repeats: a scipy.sparse matrix goes through SparseMatrix.from_scipy).  on_device=True: the three are
+    addresses of device-resident arrays and `nnz` their length.  CoGAPS() applies its input checks (NA, negative values) to every
+    triplet value of a file, overwritten or not: a file whose earlier entry of a repeated position is negative is refused there,
+    while the dense read of the same file -- and cogaps_run_from_file -- never see that entry."""
+
+    def __init__(self, shape, rows, cols, values, on_device=False, nnz=None):
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.on_device = bool(on_device)
+        if not self.on_device:
+            rows, cols = np.ascontiguousarray(rows, dtype=np.uint32), np.ascontiguousarray(cols, dtype=np.uint32)
+            values = np.ascontiguousarray(values, dtype=np.float32)
+            if not (rows.ndim == cols.ndim == values.ndim == 1 and rows.size == cols.size == values.size):
+                raise ValueError("rows, cols and values must be one-dimensional and of one length")
+            nnz = values.size
+        elif nnz is None:
+            raise ValueError("device-resident triplets need nnz")
+        self.rows, self.cols, self.values, self.nnz = rows, cols, values, int(nnz)
+
+    def c_struct(self):
+        addr = (lambda a: int(a)) if self.on_device else (lambda a: a.ctypes.data)
+        return CogapsCooMatrixC(self.shape[0], self.shape[1], self.nnz, addr(self.rows), addr(self.cols), addr(self.values), int(self.on_device))
+
+    def toarray(self):
+        """the dense matrix the triplets denote (host-resident triplets; the last entry of a position decides)"""
+        d = np.zeros(self.shape, dtype=np.float32)
+        d[self.rows, self.cols] = self.values        # (numpy assigns repeated indices in order: the last one stays)
+        return d
+
+    def tocsr(self):
+        """scipy CSR of the matrix the triplets denote: repeats resolved (the last entry decides), entries not > 0 dropped"""
+        import scipy.sparse as sp
+        key = self.rows.astype(np.int64) * self.shape[1] + self.cols
+        order = np.argsort(key, kind="stable")
+        last = np.ones(order.size, dtype=bool)
+        last[:-1] = key[order][1:] != key[order][:-1]
+        keep = order[last]
+        keep = keep[self.values[keep] > 0]
+        return sp.csr_matrix((self.values[keep], (self.rows[keep], self.cols[keep])), shape=self.shape, dtype=np.float32)
+
+
 def _sparse_input(data, unc, kw):
-    """the SparseMatrix to hand to the library's compressed-sparse entry, or None for the dense entry.  A scipy.sparse matrix goes in
-    compressed form when the run uses the sparse model; the dense model takes it densified (the caller does: toarray())."""
-    if isinstance(data, SparseMatrix):
+    """the SparseMatrix / CooMatrix to hand to the library's compressed-sparse / triplet entry, or None for the dense entry.  A
+    scipy.sparse matrix goes in compressed form when the run uses the sparse model; the dense model takes it densified (the caller
+    does: toarray())."""
+    if isinstance(data, (SparseMatrix, CooMatrix)):
         if unc is not None:
             raise ValueError("the sparse model takes no uncertainty matrix")
         return data
@@ -354,8 +412,8 @@ def _dense(a):
 
 class Session:
     """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h).  `data`: a dense matrix, a scipy.sparse matrix
-    (with sparseOptimization=True it reaches the library in compressed form, cogaps_session_create_sparse; otherwise densified) or a
-    SparseMatrix."""
+    (with sparseOptimization=True it reaches the library in compressed form, cogaps_session_create_sparse; otherwise densified), a
+    SparseMatrix or a CooMatrix (cogaps_session_create_coo)."""
 
     def __init__(self, data, unc=None, lib=None, **kw):
         self.L = lib if lib is not None else load()
@@ -364,9 +422,10 @@ class Session:
         if self.sp is not None:
             self.d = self.u = None
             m = self.sp.c_struct()
-            self.h = self.L.cogaps_session_create_sparse(C.byref(m), C.byref(self.p))
+            name = "cogaps_session_create_coo" if isinstance(self.sp, CooMatrix) else "cogaps_session_create_sparse"
+            self.h = getattr(self.L, name)(C.byref(m), C.byref(self.p))
             if not self.h:
-                raise _error(self.L, "cogaps_session_create_sparse: ")
+                raise _error(self.L, name + ": ")
             self.sp = None      # the library copied what it needs
             return
         self.d = _dense(data)
@@ -589,6 +648,29 @@ def read_matrix_file(path, lib=None, rows=None, cols=None):
         L.cogaps_matrix_free(ptr)
 
 
+def read_mtx_triplets(path, lib=None, rows=None, cols=None):
+    """The library's triplet reader (csrc/file_reader.h): the .mtx file as a CooMatrix, its entries in file order, never densified.
+    Host only.  rows / cols (one of them): 1-based indices as for read_matrix_file -- the entries of that part of the file, renumbered.
+    CooMatrix.toarray() of the result is read_matrix_file of the same arguments."""
+    L = lib or load()
+    u32p, fp = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+    nr, nc, nnz, pr, pc, pv = C.c_uint32(), C.c_uint32(), C.c_uint64(), u32p(), u32p(), fp()
+    if rows is not None and cols is not None:
+        raise ValueError("rows or cols, not both")
+    idx = None if rows is None and cols is None else np.ascontiguousarray(rows if rows is not None else cols, dtype=np.uint32)
+    if idx is not None and idx.size == 0:
+        raise ValueError("empty subset")
+    if L.cogaps_read_mtx_triplets(os.fsencode(path), int(rows is not None), None if idx is None else idx.ctypes.data_as(u32p), 0 if idx is None else idx.size,
+                                  C.byref(nr), C.byref(nc), C.byref(nnz), C.byref(pr), C.byref(pc), C.byref(pv)):
+        raise _error(L)
+    try:
+        n = int(nnz.value)
+        take = lambda p, dt: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=dt)
+        return CooMatrix((nr.value, nc.value), take(pr, np.uint32), take(pc, np.uint32), take(pv, np.float32))
+    finally:
+        L.cogaps_triplets_free(pr, pc, pv)
+
+
 def file_info(path, lib=None):
     """getFileInfo_cpp: (nrow, ncol, rowNames, colNames)"""
     L = lib or load()
@@ -620,8 +702,9 @@ def run(data, unc=None, lib=None, **kw):
     sp = _sparse_input(data, unc, kw)
     if sp is not None:
         m = sp.c_struct()
-        if L.cogaps_run_sparse(C.byref(m), C.byref(p), C.byref(r)):
-            raise _error(L, "cogaps_run_sparse: ")
+        name = "cogaps_run_coo" if isinstance(sp, CooMatrix) else "cogaps_run_sparse"
+        if getattr(L, name)(C.byref(m), C.byref(p), C.byref(r)):
+            raise _error(L, name + ": ")
         return result_to_dict(L, r)
     d = _dense(data)
     u = None if unc is None else _dense(unc)

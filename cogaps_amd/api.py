@@ -1,7 +1,8 @@
 """CoGAPS() -- the reference's user entry point (R/CoGAPS.R:90-155) over the HIP library.
 
 Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData), a scipy.sparse matrix
-(with sparseOptimization=True it is never densified) or a path to a .mtx/.csv/.tsv file.  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
+(with sparseOptimization=True it is never densified) or a path to a .mtx/.csv/.tsv file (a .mtx file with sparseOptimization=True
+is read as triplets by the library and never densified either).  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
 `distributed` = "genome-wide" / "single-cell" dispatches to cogaps_amd.distributed (GWCoGAPS / scCoGAPS).
 """
 import warnings
@@ -24,7 +25,8 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
         raise ValueError("snapshotPhase must be either equilibration, sampling, or all")
     if params.distributed is not None and nThreads > 1:
         warnings.warn("can't run multi-threaded and distributed CoGAPS at the same time, ignoring nThreads")
-    values = data.data if _capi.is_sparse(data) else data        # a scipy.sparse matrix: its stored entries (the rest are zeros)
+    # a scipy.sparse matrix: its stored entries (the rest are zeros); triplets read from a file: their values
+    values = data.values if isinstance(data, _capi.CooMatrix) else data.data if _capi.is_sparse(data) else data
     if np.isnan(values).any():
         raise ValueError("NA values in data")
     if (values < 0).any() or (uncertainty is not None and (uncertainty < 0).any()):
@@ -47,9 +49,27 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
     for k, v in extra.items():                                   # parseExtraParams: named CogapsParams slots in ...
         params.setParam(k, v)
     params.validate()
-    if isinstance(data, str):
-        data = read_matrix(data)
-    if _capi.is_sparse(data):
+    path = data if isinstance(data, str) else None
+    subset = params.subsetIndices is not None and params.subsetDim > 0     # a distributed worker's call: the run takes these rows / columns only
+    subset_by_rows = (params.subsetDim == 1) != bool(transposeData)         # genes are the data's rows unless transposeData
+    if path is not None and params.sparseOptimization and path.lower().endswith(".mtx"):
+        # a Matrix Market file reaches the sparse model as triplets (the library's reader, cogaps_run_coo): never densified
+        # The reader takes a subset the way the reference's workers read theirs: sorted, a repeated index once.  The dense entry takes
+        # the indices in the order given.  The two agree for strictly ascending indices inside the matrix -- what a distributed caller
+        # sends; anything else keeps the dense read, its results and its messages.  The order of the indices is tested first, so that
+        # such a call parses the file once, densely; only an index past the matrix, an error in the end, costs both reads.
+        idx = np.asarray(params.subsetIndices, dtype=np.int64).ravel() if subset else None
+        if subset and not (idx.size and idx[0] >= 1 and (np.diff(idx) > 0).all()):
+            data = read_matrix(path)
+        else:
+            data = _capi.read_mtx_triplets(path)
+            if subset and idx[-1] > data.shape[0 if subset_by_rows else 1]:
+                data = read_matrix(path)
+    elif path is not None:
+        data = read_matrix(path)
+    if isinstance(data, _capi.CooMatrix):
+        pass
+    elif _capi.is_sparse(data):
         # a scipy.sparse matrix reaches the sparse model in compressed form (never densified: cogaps_session_create_sparse); the dense
         # model takes a dense matrix
         data = data.astype(np.float32) if params.sparseOptimization else np.ascontiguousarray(data.toarray(), dtype=np.float32)
@@ -61,16 +81,25 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
         raise ValueError("asynchronousUpdates=FALSE selects the reference's sequential sampler; this library is the asynchronous one")
     if params.distributed is not None:
         from .distributed import distributedCogaps
+        if isinstance(data, _capi.CooMatrix):
+            data = data.tocsr()                                  # the shard code cuts a scipy.sparse matrix (repeats resolved on the host: the last entry decides)
         # BPPARAM: the reference hands the subsets to that many BiocParallel workers (R/DistributedCogaps.R:60-63); here: shards in
         # flight per GPU, run as batches of lock-stepped chains (an int, or an object with a `workers` attribute; default 16 = two batches of eight)
         in_flight = 16 if BPPARAM is None else int(getattr(BPPARAM, "workers", BPPARAM))
         raw = distributedCogaps(data, params, unc, messages=messages, outputFrequency=outputFrequency, transposeData=transposeData, device=device,
                                 shardsInFlight=in_flight, nSnapshots=nSnapshots, snapshotPhase=snapshotPhase)
     else:
+        subset_kw = dict(subsetIndices=params.subsetIndices, subsetDim=params.subsetDim)
+        if subset and isinstance(data, _capi.CooMatrix):
+            # the whole file's triplets were checked above, as the whole matrix is for every other input; the run gets the subset's, taken
+            # by the reader (as cogaps_run_from_file does), and has no subset left to take.  That is a second parse of the file: a worker
+            # pays it for checks that see the whole matrix, as they do on every other route, and holds the subset's triplets only
+            data = _capi.read_mtx_triplets(path, **{"rows" if subset_by_rows else "cols": params.subsetIndices})
+            subset_kw = dict(runningDistributed=True)
         raw = _capi.run(data, unc=unc, nPatterns=params.nPatterns, nIterations=params.nIterations, seed=params.seed,
                         outputFrequency=outputFrequency, nThreads=nThreads, alphaA=params.alphaA, alphaP=params.alphaP,
                         maxGibbsMassA=params.maxGibbsMassA, maxGibbsMassP=params.maxGibbsMassP, transposeData=transposeData,
-                        subsetIndices=params.subsetIndices, subsetDim=params.subsetDim, whichMatrixFixed=params.whichMatrixFixed,
+                        whichMatrixFixed=params.whichMatrixFixed, **subset_kw,
                         fixedPatterns=params.fixedPatterns, sparseOptimization=params.sparseOptimization, messages=messages,
                         workerID=workerID, device=device, takePumpSamples=params.takePumpSamples,
                         nSnapshots=nSnapshots, snapshotPhase=snapshotPhase)

@@ -492,13 +492,61 @@ static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha)
     h.partial = dalloc<float>(d.M);
 }
 
+// side[w].ptr holds the kept entries per vector: their exclusive scan, the packed values' allocation, the prefix counts; returns the
+// number of kept entries
+static uint32_t spb_scan_and_allocate(cogaps_session *s, SpbSide *side, HostSampler **hs)
+{
+    uint32_t kept[2] = {0, 0};
+    for (int w = 0; w < 2; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, s->stream); }
+    rt_sync(s->stream);
+    if (kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
+    for (int w = 0; w < 2; ++w) {
+        side[w].vals = dalloc<float>((size_t)kept[w] + 1); hs[w]->d.dvals = side[w].vals;
+        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    }
+    return kept[0];
+}
+// the packed values are in place: each sampler's ordered sum (sums: two floats of device scratch), then the model and the atomic domain
+static void spb_models(cogaps_session *s, SpbSide *side, HostSampler **hs, uint32_t kept, float *sums)
+{
+    const cogaps_params &p = s->p;
+    // gaps::nonZeroMean (MatrixMath.cpp:39-55): each sampler's sum in the order of its own vectors
+    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);      // (its time is reported: cogaps_session_sparse_build_ms)
+    RT_LAUNCH(spb_ordered_sum_kernel, 2, 256, s->stream, (const float *)side[0].vals, (const float *)side[1].vals, kept, sums);
+    rt_event_stop(ev, s->stream);
+    float sum[2] = {0.f, 0.f}; rt_d2h(sum, sums, 8, s->stream); rt_sync(s->stream);
+    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
+    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
+    for (int w = 0; w < 2; ++w) {      // (the seeder's outputs: A's queue, then P's -- sampler_domain)
+        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum[w], kept);
+        sampler_sparse_model(*hs[w]);
+        sampler_domain(s, *hs[w], alpha[w]);
+    }
+    s->sparseInput = true;
+}
+// The two samplers' dimensions and their flag / prefix / pointer arrays (the session's from here on: free_sampler releases them if anything
+// later throws).  Sampler A: vectors = genes, elements = samples; P the other way round (GapsRunner.cpp:402-406).  Genes are the data's
+// rows unless transposeData; the sampler whose vector axis is the input's minor axis takes its entries transposed (SpbSide::swap)
+static void spb_sides(cogaps_session *s, uint32_t nrow, uint32_t ncol, bool majorIsRow, SpbSide *side, HostSampler **hs)
+{
+    const cogaps_params &p = s->p;
+    const uint32_t nGenes = p.transposeData ? ncol : nrow, nSamples = p.transposeData ? nrow : ncol;
+    sampler_dims(s, s->A, 'A', nSamples, nGenes); sampler_dims(s, s->P, 'P', nGenes, nSamples);
+    const bool genesAreRows = !p.transposeData;
+    for (int w = 0; w < 2; ++w) {
+        SamplerDev &d = hs[w]->d; SpbSide &sd = side[w];
+        const bool vectorsAreRows = (w == 0) == genesAreRows;
+        sd.M = d.M; sd.Wn = d.Wn; sd.swap = vectorsAreRows == majorIsRow ? 0u : 1u; sd.vals = nullptr;
+        sd.flags = dalloc<unsigned long long>((size_t)d.M * d.Wn); sd.prefix = dalloc<uint32_t>((size_t)d.M * d.Wn); sd.ptr = dalloc<uint32_t>((size_t)d.M + 1);
+        d.dflags = sd.flags; d.dprefix = sd.prefix; d.dptr = sd.ptr;
+    }
+}
+
 // Both samplers of a session from a compressed-sparse matrix (sparse_build.h): the packed structures build_sampler makes from the dense
 // form of the same matrix, built on the device.  No nrow x ncol array exists on either side: d.D, d.S2 and h.Sraw stay null.
 static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
 {
-    const cogaps_params &p = s->p;
     const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
-    const uint32_t nGenes = p.transposeData ? m.ncol : m.nrow, nSamples = p.transposeData ? m.nrow : m.ncol;
     // the caller's three arrays on the device: uploaded once (temporaries: released below, not the session's), or used where they are
     uint64_t nnz = 0;
     if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, s->stream); rt_sync(s->stream); } else nnz = m.indptr[nMajor];
@@ -517,48 +565,65 @@ static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_m
         }
         err = dalloc<uint32_t>(4); tmp.p[3] = err;      // the error word, the two ordered sums
     }
-    // sampler A: vectors = genes, elements = samples; P the other way round (GapsRunner.cpp:402-406).  Genes are the data's rows unless
-    // transposeData; the sampler whose vector axis is the input's minor axis takes its entries transposed (SpbSide::swap)
-    sampler_dims(s, s->A, 'A', nSamples, nGenes); sampler_dims(s, s->P, 'P', nGenes, nSamples);
-    const bool genesAreRows = !p.transposeData;
     SpbSide side[2];
     HostSampler *hs[2] = {&s->A, &s->P};
-    for (int w = 0; w < 2; ++w) {
-        SamplerDev &d = hs[w]->d; SpbSide &sd = side[w];
-        const bool vectorsAreRows = (w == 0) == genesAreRows;
-        sd.M = d.M; sd.Wn = d.Wn; sd.swap = vectorsAreRows == (m.majorIsRow != 0) ? 0u : 1u; sd.vals = nullptr;
-        sd.flags = dalloc<unsigned long long>((size_t)d.M * d.Wn); sd.prefix = dalloc<uint32_t>((size_t)d.M * d.Wn); sd.ptr = dalloc<uint32_t>((size_t)d.M + 1);
-        d.dflags = sd.flags; d.dprefix = sd.prefix; d.dptr = sd.ptr;      // (the session's from here on: free_sampler releases them if anything below throws)
-    }
+    spb_sides(s, m.nrow, m.ncol, m.majorIsRow != 0, side, hs);
     const uint32_t sliceGrid = (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
     RT_LAUNCH(spb_validate_count_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1], err);
     uint32_t code = 0; rt_d2h(&code, err, 4, s->stream); rt_sync(s->stream);
     if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
     if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
     if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
-    uint32_t kept[2] = {0, 0};
-    for (int w = 0; w < 2; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, s->stream); }
-    rt_sync(s->stream);
-    if (kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
-    for (int w = 0; w < 2; ++w) {
-        side[w].vals = dalloc<float>((size_t)kept[w] + 1); hs[w]->d.dvals = side[w].vals;
-        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
-    }
+    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
     RT_LAUNCH(spb_scatter_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1]);
-    // gaps::nonZeroMean (MatrixMath.cpp:39-55): each sampler's sum in the order of its own vectors
-    float *sums = (float *)(err + 1);
-    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);      // (its time is reported: cogaps_session_sparse_build_ms)
-    RT_LAUNCH(spb_ordered_sum_kernel, 2, 256, s->stream, (const float *)side[0].vals, (const float *)side[1].vals, kept[0], sums);
-    rt_event_stop(ev, s->stream);
-    float sum[2] = {0.f, 0.f}; rt_d2h(sum, sums, 8, s->stream); rt_sync(s->stream);
-    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
-    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
-    for (int w = 0; w < 2; ++w) {      // (the seeder's outputs: A's queue, then P's -- sampler_domain)
-        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum[w], kept[w]);
-        sampler_sparse_model(*hs[w]);
-        sampler_domain(s, *hs[w], alpha[w]);
+    spb_models(s, side, hs, kept, (float *)(err + 1));
+}
+
+// Both samplers of a session from unordered triplets (sparse_build.h, the passes of its second half): the session cogaps_session_create
+// makes from the matrix the triplets denote -- the latest entry of a position decides it.  The temporaries (the caller's arrays uploaded,
+// the present flags with their prefix counts and pointers, one winner index per present position, one keep bit per entry) are O(nnz + one
+// sampler's flag arrays); they are not the session's and are released before this returns.
+static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix &m)
+{
+    const uint64_t nnz = m.nnz;
+    struct Temps { void *p[9] = {}; ~Temps() { for (void *q : p) rt_free(q); } } tmp;
+    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz; in.rows = m.rows; in.cols = m.cols; in.values = m.values;
+    SpbSide side[2], pres;
+    HostSampler *hs[2] = {&s->A, &s->P};
+    spb_sides(s, m.nrow, m.ncol, true, side, hs);
+    pres = side[0]; pres.vals = nullptr;
+    uint32_t *err; unsigned long long *keep;
+    {
+        rt_owner_scope notTheSessions(nullptr);
+        if (!m.onDevice) {
+            uint32_t *r = dalloc<uint32_t>(nnz + 1); tmp.p[0] = r; uint32_t *c = dalloc<uint32_t>(nnz + 1); tmp.p[1] = c; float *v = dalloc<float>(nnz + 1); tmp.p[2] = v;
+            if (nnz) { rt_h2d(r, m.rows, nnz * 4, s->stream); rt_h2d(c, m.cols, nnz * 4, s->stream); rt_h2d(v, m.values, nnz * 4, s->stream); }
+            in.rows = r; in.cols = c; in.values = v;
+        }
+        err = dalloc<uint32_t>(4); tmp.p[3] = err;      // the error word, the two ordered sums
+        pres.flags = dalloc<unsigned long long>((size_t)pres.M * pres.Wn); tmp.p[4] = pres.flags;
+        pres.prefix = dalloc<uint32_t>((size_t)pres.M * pres.Wn); tmp.p[5] = pres.prefix;
+        pres.ptr = dalloc<uint32_t>((size_t)pres.M + 1); tmp.p[6] = pres.ptr;
+        keep = dalloc<unsigned long long>(nnz / 64 + 1); tmp.p[7] = keep;
     }
-    s->sparseInput = true;
+    // grid-stride over the entries: enough workgroups to fill the device, never more than the entries need (at least one)
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nnz + COO_BS - 1) / COO_BS, (uint64_t)s->computeUnits * 8u));
+    const uint32_t vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
+    RT_LAUNCH(coo_present_kernel, grid, COO_BS, s->stream, in, pres, err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, s->stream); rt_sync(s->stream);
+    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
+    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, s->stream, pres);
+    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, pres.ptr, pres.M);
+    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, s->stream, pres);
+    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, s->stream); rt_sync(s->stream);
+    uint32_t *winner;
+    { rt_owner_scope notTheSessions(nullptr); winner = dalloc<uint32_t>((size_t)nPresent + 1); tmp.p[8] = winner; }
+    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, s->stream, in, pres, winner);
+    RT_LAUNCH(coo_keep_kernel, grid, COO_BS, s->stream, in, pres, (const uint32_t *)winner, side[0], side[1], keep);
+    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
+    RT_LAUNCH(coo_scatter_kernel, grid, COO_BS, s->stream, in, side[0], side[1], (const unsigned long long *)keep);
+    spb_models(s, side, hs, kept, (float *)(err + 1));
 }
 
 static void read_gs(cogaps_session *s, HostSampler &h)
@@ -1051,9 +1116,10 @@ int cogaps_compiled_with_openmp(void) { return 0; }
 
 } // extern "C"
 
-// cogaps_session_create (sp == nullptr: the dense matrix `data`) and cogaps_session_create_sparse (sp: the compressed one)
+// cogaps_session_create (sp == coo == nullptr: the dense matrix `data`), cogaps_session_create_sparse (sp: the compressed one) and
+// cogaps_session_create_coo (coo: unordered triplets)
 static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, int data_on_device,
-                                      const cogaps_sparse_matrix *sp)
+                                      const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo = nullptr)
 {
     cogaps_session *s = nullptr;
     try {
@@ -1065,6 +1131,13 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
             if (p.subsetData) { fail("subsetData is not supported with a compressed-sparse matrix: pass the rows / columns of the subset"); return nullptr; }
             if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a compressed-sparse matrix"); return nullptr; }
             if (!sp->indptr) { fail("null argument: indptr"); return nullptr; }
+        } else if (coo) {
+            nrow = coo->nrow; ncol = coo->ncol;
+            if (!p.useSparseOptimization) { fail("a triplet matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
+            if (p.subsetData) { fail("subsetData is not supported with a triplet matrix: pass the entries of the subset"); return nullptr; }
+            if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a triplet matrix"); return nullptr; }
+            if (coo->nnz >= 0xFFFFFFFFull) { fail("triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)"); return nullptr; }
+            if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) { fail("null argument: rows / cols / values"); return nullptr; }
         } else if (!data) { fail("null argument: data"); return nullptr; }
         // The reference's distributed caller forces asynchronousUpdates = FALSE on its workers (R/DistributedCogaps.R:28-29) -- there to keep
         // BiocParallel workers single-threaded, not for the sampler's sake.  Documented deviation: a
@@ -1115,6 +1188,7 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // samplers: A on the transposed data with the subset flag flipped (GapsRunner.cpp:402-406);
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
         if (sp) build_samplers_sparse_input(s, *sp);
+        else if (coo) build_samplers_coo_input(s, *coo);
         else {
         build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
         build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
@@ -1188,6 +1262,11 @@ cogaps_session *cogaps_session_create_sparse(const cogaps_sparse_matrix *m, cons
 {
     if (!m) { fail("null argument"); return nullptr; }
     return session_create(nullptr, 0, 0, params, nullptr, 0, m);
+}
+cogaps_session *cogaps_session_create_coo(const cogaps_coo_matrix *m, const cogaps_params *params)
+{
+    if (!m) { fail("null argument"); return nullptr; }
+    return session_create(nullptr, 0, 0, params, nullptr, 0, nullptr, m);
 }
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes)
 {
@@ -1971,6 +2050,18 @@ int cogaps_run_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params
     return rc;
 }
 
+int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, cogaps_result *out)
+{
+    if (!out) return fail("null argument");
+    cogaps_session *s = cogaps_session_create_coo(m, params);
+    if (!s) return 1;
+    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_finish(s, out);
+    cogaps_session_destroy(s);
+    return rc;
+}
+
 // ---- the file entry point (gaps::run(const std::string&...), GapsRunner.h:24-29; cogaps_from_file_cpp, Cogaps.cpp:217-227) ----
 static int table_out(const cgio::Table &t, uint32_t *nrow, uint32_t *ncol, float **data)
 {
@@ -2000,6 +2091,26 @@ int cogaps_read_matrix_file_subset(const char *path, int byRows, const uint32_t 
 }
 
 void cogaps_matrix_free(float *data) { free(data); }
+
+// The .mtx file as triplets in file order (file_reader.h, read_mtx_triplets): what cogaps_read_matrix_file[_subset] gives, entry by
+// entry instead of densified -- D = 0; D[rows[k]][cols[k]] = values[k] in order reproduces it byte for byte.
+int cogaps_read_mtx_triplets(const char *path, int byRows, const uint32_t *indices, uint32_t nIndices,
+                             uint32_t *nrow, uint32_t *ncol, uint64_t *nnz, uint32_t **rows, uint32_t **cols, float **values)
+{
+    try {
+        if (!path || !nrow || !ncol || !nnz || !rows || !cols || !values) return fail("null argument");
+        if (indices && nIndices == 0) return fail("null argument or empty subset");
+        cgio::ReadOpts o; if (indices) o.sub = cgio::Subset(byRows != 0, indices, nIndices);
+        const cgio::Triplets t = cgio::read_mtx_triplets_file(path, o);
+        const size_t n = t.v.size(), bytes = std::max<size_t>(1, n) * 4;
+        uint32_t *r = (uint32_t *)malloc(bytes), *c = (uint32_t *)malloc(bytes); float *v = (float *)malloc(bytes);
+        if (!r || !c || !v) { free(r); free(c); free(v); return fail("out of memory"); }
+        memcpy(r, t.r.data(), n * 4); memcpy(c, t.c.data(), n * 4); memcpy(v, t.v.data(), n * 4);
+        *nrow = t.nrow; *ncol = t.ncol; *nnz = n; *rows = r; *cols = c; *values = v;
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+void cogaps_triplets_free(uint32_t *rows, uint32_t *cols, float *values) { free(rows); free(cols); free(values); }
 
 // getFileInfo_cpp (Cogaps.cpp:229-246): dimensions and the names the file carries, '\n'-joined into caller buffers
 // (a NULL buffer or zero capacity skips the names; *needed reports the bytes a complete copy takes, terminator included)
@@ -2033,8 +2144,18 @@ int cogaps_run_from_file(const char *dataPath, const cogaps_params *params, cons
             o.sub = cgio::Subset(byRows, p.dataIndicesSubset, p.nSubset);
             p.subsetData = 0; p.dataIndicesSubset = nullptr; p.nSubset = 0;
         }
-        cgio::Table d = cgio::read_matrix_file(dataPath, o), u;
         const bool haveUnc = uncertaintyPath && uncertaintyPath[0];
+        // A Matrix Market file for the sparse model (default reduction order, default uncertainty) goes in as triplets: the run of the
+        // dense read, bit for bit, without the nrow x ncol array on the host or the device.  (An empty matrix keeps the dense route's
+        // message.)
+        if (cgio::is_mtx_path(dataPath) && p.useSparseOptimization && p.reductionMode == COGAPS_REDUCE_LANES && !haveUnc && !p.subsetData) {
+            const cgio::Triplets t = cgio::read_mtx_triplets_file(dataPath, o);
+            if (t.nrow && t.ncol && t.v.size() < 0xFFFFFFFFull) {
+                cogaps_coo_matrix m; m.nrow = t.nrow; m.ncol = t.ncol; m.nnz = t.v.size(); m.rows = t.r.data(); m.cols = t.c.data(); m.values = t.v.data(); m.onDevice = 0;
+                return cogaps_run_coo(&m, &p, out);
+            }
+        }
+        cgio::Table d = cgio::read_matrix_file(dataPath, o), u;
         if (haveUnc) {
             u = cgio::read_matrix_file(uncertaintyPath, o);
             if (u.nrow != d.nrow || u.ncol != d.ncol || u.fileRows != d.fileRows || u.fileCols != d.fileCols) return fail("uncertainty matrix has different dimensions than the data");

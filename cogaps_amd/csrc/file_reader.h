@@ -99,15 +99,22 @@ inline void two_uints(const char *b, const char *e, uint32_t &a, uint32_t &c)
     a = (uint32_t)strtoul(t.c_str(), &end, 10); c = (uint32_t)strtoul(end, &end, 10);
 }
 
-inline Table read_mtx(const std::string &text, const ReadOpts &o = ReadOpts())                       // MtxParser.cpp:8-62
+// A Matrix Market file (MtxParser.cpp:8-62) in two steps.  mtx_size_line: the size line into t (and the subset's dimensions) -- lines
+// before it that hold a '%' are comments; returns where the entries start.  mtx_entries: put(row, col, value) -- 0-based, renumbered by
+// the subset -- for every entry line that is kept, in file order.  Blank lines and lines of fewer than three tokens are skipped, an
+// entry outside the stated dimensions is an error whether the subset keeps it or not, a value is parsed only when its entry is kept.
+inline size_t mtx_size_line(const std::string &text, const ReadOpts &o, Table &t)
 {
-    Table t; size_t pos = 0; const char *b, *e;
+    size_t pos = 0; const char *b, *e;
     do { if (!next_line(text, pos, b, e)) throw std::runtime_error("Invalid MTX file"); } while (std::string(b, e).find('%') != std::string::npos);
     two_uints(b, e, t.fileRows, t.fileCols);
     t.nrow = t.fileRows; t.ncol = t.fileCols;
     if (o.sub.active) { if (o.sub.byRows) t.nrow = (uint32_t)o.sub.idx.size(); else t.ncol = (uint32_t)o.sub.idx.size(); }
-    if (!o.values) return t;
-    t.v.assign((size_t)t.nrow * t.ncol, 0.f);
+    return pos;
+}
+template <class F> inline void mtx_entries(const std::string &text, size_t pos, const ReadOpts &o, const Table &t, F put)
+{
+    const char *b, *e;
     while (next_line(text, pos, b, e)) {
         if (blank(b, e)) continue;
         // "row col value", whitespace separated, 1-based
@@ -125,9 +132,31 @@ inline Table read_mtx(const std::string &text, const ReadOpts &o = ReadOpts())  
             if (k < 0) continue;
             if (o.sub.byRows) r = (uint32_t)k + 1u; else c = (uint32_t)k + 1u;
         }
-        t.v[(size_t)(r - 1) * t.ncol + (c - 1)] = parse_value(tok[2][0], tok[2][1]);
+        put(r - 1u, c - 1u, parse_value(tok[2][0], tok[2][1]));
     }
+}
+
+inline Table read_mtx(const std::string &text, const ReadOpts &o = ReadOpts())
+{
+    Table t; const size_t pos = mtx_size_line(text, o, t);
+    if (!o.values) return t;
+    t.v.assign((size_t)t.nrow * t.ncol, 0.f);
+    mtx_entries(text, pos, o, t, [&](uint32_t r, uint32_t c, float v) { t.v[(size_t)r * t.ncol + c] = v; });      // (a repeated position: the later entry overwrites)
     return t;
+}
+
+// The same file as triplets in file order, never densified: r, c 0-based (of the subset matrix with a Subset), v by parse_value.  A position
+// may repeat; the dense matrix is D = 0, then D[r[k]][c[k]] = v[k] for k = 0, 1, ... -- what read_mtx returns.
+struct Triplets {
+    uint32_t nrow = 0, ncol = 0, fileRows = 0, fileCols = 0;
+    std::vector<uint32_t> r, c; std::vector<float> v;
+};
+inline Triplets read_mtx_triplets(const std::string &text, const ReadOpts &o = ReadOpts())
+{
+    Table t; Triplets out; const size_t pos = mtx_size_line(text, o, t);
+    mtx_entries(text, pos, o, t, [&](uint32_t r, uint32_t c, float v) { out.r.push_back(r); out.c.push_back(c); out.v.push_back(v); });
+    out.nrow = t.nrow; out.ncol = t.ncol; out.fileRows = t.fileRows; out.fileCols = t.fileCols;
+    return out;
 }
 
 inline Table read_delimited(const std::string &text, char delim, bool gct, const ReadOpts &o = ReadOpts())          // CharacterDelimitedParser.cpp:56-147
@@ -195,6 +224,20 @@ inline Table read_matrix_file(const std::string &path, const ReadOpts &o = ReadO
     else if (ends_with(low, ".tsv")) t = read_delimited(slurp(path), '\t', false, o);
     else if (ends_with(low, ".gct")) t = read_delimited(slurp(path), '\t', true, o);
     else throw std::runtime_error("unsupported file extension (.csv, .tsv, .mtx, .gct): " + path);
+    return t;
+}
+
+inline bool is_mtx_path(const std::string &path)
+{
+    std::string low = path; for (char &c : low) if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+    return ends_with(low, ".mtx");
+}
+// read_matrix_file for a .mtx path with the triplet reader: the same errors, the subset-index check included
+inline Triplets read_mtx_triplets_file(const std::string &path, const ReadOpts &o = ReadOpts())
+{
+    if (!is_mtx_path(path)) throw std::runtime_error("not a Matrix Market file (.mtx): " + path);
+    Triplets t = read_mtx_triplets(slurp(path), o);
+    if (o.sub.active) for (uint32_t i : o.sub.idx) if (i < 1 || i > (o.sub.byRows ? t.fileRows : t.fileCols)) throw std::runtime_error("subset index outside the file's dimensions");
     return t;
 }
 

@@ -11,6 +11,7 @@
 
 #if defined(COGAPS_EMUL)
 #include "emul_runtime.h"   // tests/emul/
+inline uint32_t cg_load_l2_u32(const uint32_t *p) { return *p; }      // beside emul_runtime.h's cg_load_l2_u64: one thread, plain loads
 #else
 #include <hip/hip_runtime.h>
 
@@ -139,6 +140,7 @@ CG_DEVICE unsigned long long cg_ballot(bool p) { return __ballot(p); }
 CG_DEVICE int cg_popc64(unsigned long long x) { return __popcll(x); }
 // loads of words that other waves of the workgroup update with L2 atomics: bypass the CU's L1
 CG_DEVICE unsigned long long cg_load_l2_u64(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+CG_DEVICE uint32_t cg_load_l2_u32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // A hand-off between workgroups INSIDE a launch (eval_kernel.h, split evaluation): one naturally aligned 8-byte {data, tag} granule,
 // written through to the device-coherent level by one store (agent scope: `sc1`), read with cg_load_l2_u64 past the reader's
 // non-coherent caches.  The tag says the data is this batch's, so no flag, counter, fence or ordering between two stores is needed

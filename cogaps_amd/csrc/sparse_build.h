@@ -1,4 +1,5 @@
-// sparse_build.h -- the sparse model's data structures built on the device from a compressed-sparse matrix (CSR or CSC), and
+// sparse_build.h -- the sparse model's data structures built on the device from a compressed-sparse matrix (CSR or CSC) or from unordered
+// triplets (COO: further down), and
 // meanChiSq from them: what build_sampler (cogaps_hip.cpp) builds on the host from a dense matrix, bit for bit, without an
 // nrow x ncol array anywhere.
 //
@@ -104,12 +105,14 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_prefix_kernel(SpbSide s)
     }
 }
 
-CG_DEVICE void spb_store(const SpbSide &s, uint32_t major, uint32_t minor, float v)
+// the packed slot of a flagged position: entries of the vectors before it, of its vector's words before its own, of its word below its bit
+CG_DEVICE uint32_t spb_slot(const SpbSide &s, uint32_t major, uint32_t minor)
 {
     uint32_t vec, el; spb_place(s, major, minor, vec, el);
     const size_t w = (size_t)vec * s.Wn + (el >> 6);
-    s.vals[s.ptr[vec] + s.prefix[w] + (uint32_t)cg_popc64(s.flags[w] & ((1ull << (el & 63u)) - 1ull))] = v;
+    return s.ptr[vec] + s.prefix[w] + (uint32_t)cg_popc64(s.flags[w] & ((1ull << (el & 63u)) - 1ull));
 }
+CG_DEVICE void spb_store(const SpbSide &s, uint32_t major, uint32_t minor, float v) { s.vals[spb_slot(s, major, minor)] = v; }
 // every kept entry to its slot in both samplers' packed values (validated input only: the slots are then distinct and below ptr[M])
 CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_scatter_kernel(SpbIn in, SpbSide a, SpbSide b)
 {
@@ -131,6 +134,95 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(256) spb_ordered_sum_kernel(const float *va, con
     const float *v = cg_bid() == 0u ? va : vb;
     const float c = seq_sum(0.f, (uint64_t)n, lds, [&](uint64_t e) { return v[e]; });
     if (cg_tid() == 0) out[cg_bid()] = c;
+}
+
+// ---- unordered triplets (COO): rows[k], cols[k], values[k], k = 0 .. nnz-1, repeats allowed ----
+// The matrix they denote is D = 0; for k in input order: D[rows[k]][cols[k]] = values[k] -- the LATEST entry of a position decides it,
+// also when its value is not > 0 (the position is then absent).  Which entry is the latest depends on k alone, never on which wave ran
+// first:
+//   1. coo_present_kernel: checks every index, sets a PRESENT bit per entry -- whatever its value -- in a temporary flag array laid out
+//      like sampler A's (64-bit atomic OR: idempotent)
+//   2. spb_count_kernel, spb_scan_kernel, spb_prefix_kernel on that array: every present position gets a slot
+//   3. coo_winner_kernel: winner[slot] = max k over the position's entries (32-bit atomic max: commutative, so the order of arrival is
+//      immaterial)
+//   4. coo_keep_kernel: entry k is KEPT when winner[slot] == k and its value is > 0; the kept entries are distinct positions.  They set
+//      both samplers' flag bits, and one bit each in keep[] (a wave's ballot: one 64-bit store per 64 entries)
+//   5. spb_count_kernel, scan, prefix per sampler, then coo_scatter_kernel: every kept entry to its slot, as in the compressed build
+// Hot positions (many entries of one position, or of one flag word) meet at one address in passes 1 and 3; an entry first reads the word
+// (a relaxed device-scope atomic load: served where the atomics are carried out, no cache line of this compute unit involved) and leaves
+// the atomic out when it would change nothing (both words only ever grow, so an old value costs an atomic, never the result).
+struct CooIn {
+    const uint32_t *rows, *cols; const float *values;
+    uint32_t nrow, ncol; uint64_t nnz;
+};
+#define COO_BS 256       // entries per workgroup and round (grid-stride loops: the grid is sized to the device, not to nnz)
+
+// Every index against the dimensions; the present bit of every entry in range.  Nothing is read outside [0, nnz), nothing written outside
+// the temporary flag array whatever the input holds; the host reads *err before anything is built from it.
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_present_kernel(CooIn in, SpbSide t, uint32_t *err)
+{
+    for (uint64_t k = (uint64_t)cg_bid() * COO_BS + cg_tid(); k < in.nnz; k += (uint64_t)cg_gdim() * COO_BS) {
+        const uint32_t r = in.rows[k], c = in.cols[k];
+        if (r >= in.nrow || c >= in.ncol) { cg_atomic_max_u32(err, SPB_ERR_RANGE); continue; }
+        uint32_t vec, el; spb_place(t, r, c, vec, el);
+        unsigned long long *w = t.flags + (size_t)vec * t.Wn + (el >> 6); const unsigned long long bit = 1ull << (el & 63u);
+        if (!(cg_load_l2_u64(w) & bit)) cg_atomic_or_u64(w, bit);
+    }
+}
+
+// ptr[j] = set flag bits of vector j (what the compressed build counts entry by entry: here an entry may repeat).  One wave per vector.
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_count_kernel(SpbSide s)
+{
+    const uint32_t lane = cg_tid() & 63u, j = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    const bool live = j < s.M;
+    uint32_t n = 0;
+    for (uint32_t w0 = 0; w0 < s.Wn; w0 += 64u) {
+        const uint32_t w = w0 + lane;
+        if (live && w < s.Wn) n += (uint32_t)cg_popc64(s.flags[(size_t)j * s.Wn + w]);
+    }
+    n = cg_wave_sum_u32(n);
+    if (lane == 0u && live) s.ptr[j] = n;
+}
+
+// winner[slot of the entry's position] = the largest k among the position's entries (winner starts at 0; validated input only)
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_winner_kernel(CooIn in, SpbSide t, uint32_t *winner)
+{
+    for (uint64_t k = (uint64_t)cg_bid() * COO_BS + cg_tid(); k < in.nnz; k += (uint64_t)cg_gdim() * COO_BS) {
+        uint32_t *w = winner + spb_slot(t, in.rows[k], in.cols[k]);
+        if (cg_load_l2_u32(w) < (uint32_t)k) cg_atomic_max_u32(w, (uint32_t)k);
+    }
+}
+
+// The kept entries: their bit in both samplers' flag words and in keep[k >> 6] (bit k & 63).  A wave takes 64 consecutive entries from a
+// multiple of 64 on, so a keep word has one writer.
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_keep_kernel(CooIn in, SpbSide t, const uint32_t *winner, SpbSide a, SpbSide b, unsigned long long *keep)
+{
+    const uint32_t lane = cg_tid() & 63u;
+    for (uint64_t base = (uint64_t)cg_bid() * COO_BS + (cg_tid() - lane); base < in.nnz; base += (uint64_t)cg_gdim() * COO_BS) {
+        const uint64_t k = base + lane;
+        bool kept = false;
+        if (k < in.nnz) {
+            const uint32_t r = in.rows[k], c = in.cols[k];
+            kept = in.values[k] > 0.f && winner[spb_slot(t, r, c)] == (uint32_t)k;      // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
+            if (kept) {
+                uint32_t vec, el;
+                spb_place(a, r, c, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
+                spb_place(b, r, c, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
+            }
+        }
+        const unsigned long long mask = cg_ballot(kept);
+        if (lane == 0u) keep[base >> 6] = mask;
+    }
+}
+
+// every kept entry to its slot in both samplers' packed values (the kept entries are distinct positions: the slots are distinct)
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_scatter_kernel(CooIn in, SpbSide a, SpbSide b, const unsigned long long *keep)
+{
+    for (uint64_t k = (uint64_t)cg_bid() * COO_BS + cg_tid(); k < in.nnz; k += (uint64_t)cg_gdim() * COO_BS) {
+        if (!((keep[k >> 6] >> (k & 63u)) & 1ull)) continue;
+        const uint32_t r = in.rows[k], c = in.cols[k]; const float v = in.values[k];
+        spb_store(a, r, c, v); spb_store(b, r, c, v);
+    }
 }
 
 // GapsStatistics::meanChiSq per-vector partials (aux_kernels.h, mean_chisq_rows_kernel) with the data taken from the P sampler's packed

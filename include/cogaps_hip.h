@@ -137,6 +137,14 @@ int cogaps_read_matrix_file(const char *path, uint32_t *nrow, uint32_t *ncol, fl
 int cogaps_read_matrix_file_subset(const char *path, int byRows, const uint32_t *indices, uint32_t nIndices,
                                    uint32_t *nrow, uint32_t *ncol, float **data);
 void cogaps_matrix_free(float *data);
+/* the .mtx file as triplets in file order (0-based), values by the reader's text -> fp32 rule; with indices != NULL only the entries of
+ * the named rows (byRows) / columns, renumbered as cogaps_read_matrix_file_subset places them; *nrow, *ncol: of the (subset) matrix.
+ * A position may repeat: D = 0, then D[rows[k]][cols[k]] = values[k] for k = 0, 1, ... is the matrix cogaps_read_matrix_file[_subset]
+ * returns, byte for byte -- the meaning cogaps_coo_matrix gives the same arrays.  Same messages as the dense reader.  Host only: no GPU
+ * needed.  The three arrays are callee-allocated; release them with cogaps_triplets_free. */
+int cogaps_read_mtx_triplets(const char *path, int byRows, const uint32_t *indices, uint32_t nIndices,
+                             uint32_t *nrow, uint32_t *ncol, uint64_t *nnz, uint32_t **rows, uint32_t **cols, float **values);
+void cogaps_triplets_free(uint32_t *rows, uint32_t *cols, float *values);
 /* getFileInfo_cpp (src/Cogaps.cpp:229-246): dimensions and the row / column names the file carries, '\n'-joined into the
  * caller's buffers (NULL / 0 to skip; *needed = bytes of a complete copy incl. the terminator).  Host only. */
 int cogaps_file_info(const char *path, uint32_t *nrow, uint32_t *ncol, char *rowNames, size_t rowCap, size_t *rowNeeded,
@@ -208,6 +216,37 @@ typedef struct cogaps_sparse_matrix {
 cogaps_session *cogaps_session_create_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params);
 /* cogaps_run for such a matrix (host or device pointers) */
 int cogaps_run_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params, cogaps_result *out);
+
+/* A matrix as unordered triplets (COO) -- what a Matrix Market file holds, or R's dgTMatrix (@i -> rows, @j -> cols, @x -> values as
+ * fp32, @Dim -> nrow, ncol) -- as the input of the sparse model.  The triplets denote the matrix
+ *
+ *     D = zeros(nrow, ncol);  for k in 0 .. nnz-1, in that order:  D[rows[k], cols[k]] = values[k]
+ *
+ * THE ENTRY LATEST IN INPUT ORDER DECIDES A POSITION, also when its value is not > 0: the position is then absent whatever came before.
+ * (This is what the .mtx reader does with a repeated position.  It is NOT what R's Matrix package or scipy mean by repeated triplets --
+ * they sum them: a caller who wants sums canonicalises first.)  After that rule a value that is not > 0 (zero, negative, NaN) is absent,
+ * as for the compressed entry.
+ *
+ * A session created from the triplets is the session cogaps_session_create makes from D, bit for bit (flag words, prefix counts,
+ * pointers, packed values, lambda, maxGibbsMass, meanChiSq, every proposal), and holds the bytes of device memory the session created
+ * from the CSR form of D holds.  No nrow x ncol array is allocated on the host or on the device: the build (csrc/sparse_build.h) resolves
+ * repeated positions on the device by the entry index alone, so the result does not depend on how the device schedules the work; its
+ * temporaries -- the uploaded arrays, one present bit per position in one sampler's flag layout with prefix counts, one 32-bit index per
+ * present position, one bit per entry -- are released before the call returns.  The caller's arrays are not referenced afterwards.
+ * Errors (NULL / 1, cogaps_last_error): useSparseOptimization = 0; subsetData; reductionMode COGAPS_REDUCE_SEQ; a NULL array with
+ * nnz > 0; a row or column index outside the stated dimensions (checked on the device before anything is built); nnz >= 2^32 - 1.
+ * Everything else as for cogaps_sparse_matrix: transposeData, whichMatrixFixed / fixedPatterns, batches, traces, copy-outs, snapshots,
+ * PUMP.  cogaps_run_from_file takes this route for a .mtx path with useSparseOptimization = 1, the default reductionMode and no
+ * uncertainty file (a subset is taken by the reader); its results are those of the dense read of the file. */
+typedef struct cogaps_coo_matrix {
+    uint32_t nrow, ncol;          /* of the data as the caller sees it (genes x samples unless transposeData) */
+    uint64_t nnz;
+    const uint32_t *rows, *cols;  /* [nnz], 0-based, any order, repeats allowed: the latest entry of a position decides */
+    const float    *values;       /* [nnz] */
+    int32_t  onDevice;            /* 0: host pointers, 1: device pointers of params->device */
+} cogaps_coo_matrix;
+cogaps_session *cogaps_session_create_coo(const cogaps_coo_matrix *m, const cogaps_params *params);
+int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, cogaps_result *out);
 /* Bytes of device memory the session holds: the sum of its own allocations (as requested), counted as they are made and released -- not
  * hipMemGetInfo, which is device-wide.  For every session, however it was created. */
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes);
