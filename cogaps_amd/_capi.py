@@ -442,7 +442,7 @@ class Session:
         return int(v.value)
 
     def sparse_build_ms(self):
-        """HIP-event time of the ordered sums at the creation of a session from a compressed-sparse matrix (0 otherwise)"""
+        """HIP-event time of the ordered sums at the creation of a sparse-model session (0 for the dense model)"""
         v = C.c_float(0)
         self._ck(self.L.cogaps_session_sparse_build_ms(self.h, C.byref(v)))
         return float(v.value)

@@ -141,7 +141,15 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(256) chisq_seq_kernel(SamplerDev S, const float 
         return q * q; });
     if (cg_tid() == 0) out[0] = c;
 }
-// GapsStatistics::meanChiSq (GapsStatistics.cpp:63-86) in its own order: genes outer, samples inner
+// element i of the sparse model's data vector j from its packed form (sparse_build.h): the packed value where the flag bit is set, else 0
+CG_DEVICE float packed_datum(const SamplerDev &S, uint32_t j, uint32_t i)
+{
+    const size_t w = (size_t)j * S.Wn + (i >> 6);
+    const unsigned long long word = S.dflags[w], bit = 1ull << (i & 63u);
+    return (word & bit) ? S.dvals[S.dptr[j] + S.dprefix[w] + (uint32_t)cg_popc64(word & (bit - 1ull))] : 0.f;
+}
+// GapsStatistics::meanChiSq (GapsStatistics.cpp:63-86) in its own order: genes outer, samples inner.  The dense model reads D and Sraw;
+// the sparse model holds neither: d from the packed data, sd = max(0.1 d, 0.1) (the default uncertainty, the only one it knows)
 CG_KERNEL void CG_LAUNCH_BOUNDS(256) mean_chisq_seq_kernel(SamplerDev P, const float *Sraw, const float *Asum, const float *Psum, uint32_t AMpad, float n2, float *out)
 {
     CG_SHARED float lds[SEQ_CHUNK];
@@ -151,7 +159,8 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(256) mean_chisq_seq_kernel(SamplerDev P, const f
         float m = 0.f;
         for (uint32_t k = 0; k < P.K; ++k) m = m + Asum[(size_t)k * AMpad + i] * Psum[(size_t)k * P.Mpad + j];
         m = m / n2;
-        const float d = P.D[(size_t)j * P.Npad + i], sd = Sraw[(size_t)j * P.Npad + i];
+        const float d = P.sparse ? packed_datum(P, j, i) : P.D[(size_t)j * P.Npad + i];
+        const float sd = P.sparse ? gm_max(d * 0.1f, 0.1f) : Sraw[(size_t)j * P.Npad + i];
         return ((d - m) * (d - m)) / (sd * sd); });
     if (cg_tid() == 0) out[0] = c;
 }

@@ -243,7 +243,7 @@ struct GraphCache {
 // ------------------------------------------------------------------------------------------------
 struct HostSampler {
     SamplerDev d;                 // device pointers + constants (passed by value to the kernels)
-    float *Sraw = nullptr;        // un-squared uncertainty [M][Npad] (chiSq)
+    float *Sraw = nullptr;        // un-squared uncertainty [M][Npad] (chiSq); the dense model only
     uint64_t *seeds = nullptr; size_t seedCap = 0;
     uint64_t *hSeeds = nullptr; size_t hSeedCap = 0;
     float *partial = nullptr;     // [M] chi2 partials
@@ -311,7 +311,6 @@ struct cogaps_session {
     GenScalars *hGs = nullptr;    // pinned staging
     std::atomic<uint64_t> deviceBytes{0};      // device memory the session holds (rt_owner_scope; cogaps_session_device_bytes)
     float orderedSumMs = 0.f;     // ... and what the ordered sums of the packed values took at its creation (HIP events)
-    bool sparseInput = false;     // created from a compressed-sparse matrix: no dense D / S2 / Sraw exist, meanChiSq reads the packed data
     bool poisoned = false;        // a device error ended an update half way (capacity, a hand-over inside a launch that never arrived): the chain's state is not a state of the chain
 };
 
@@ -368,7 +367,8 @@ static void sampler_model(HostSampler &h, float alpha, float maxGibbsMass, float
     d.maxGibbsMass = maxGibbsMass / d.lambda;
     d.unitBytes = 4u * d.N;
 }
-// the sparse model beside its packed data (dflags, dprefix, dptr, dvals: the caller's): the HybridMatrix copies and the lookup tables
+// the sparse model beside its packed data (dflags, dprefix, dptr, dvals: sparse_build.h, whatever form the input had -- the only data a
+// sparse-model session holds: d.D, d.S2 and h.Sraw stay null): the HybridMatrix copies and the lookup tables
 static void sampler_sparse_model(HostSampler &h)
 {
     SamplerDev &d = h.d;
@@ -383,7 +383,7 @@ static void sampler_sparse_model(HostSampler &h)
     }
 }
 
-// Matrix(mat, genesInCols, subsetGenes, indices) (data_structures/Matrix.cpp:30-69) laid out as
+// The dense model's sampler: Matrix(mat, genesInCols, subsetGenes, indices) (data_structures/Matrix.cpp:30-69) laid out as
 // [vector j][element i] + the DenseNormalModel constructor (DenseNormalModel.h:66-88)
 static void build_sampler(cogaps_session *s, HostSampler &h, char name, const float *data, uint32_t nrow, uint32_t ncol, const float *unc,
                           bool genesInCols, bool subsetGenes, float alpha, float maxGibbsMass)
@@ -393,44 +393,34 @@ static void build_sampler(cogaps_session *s, HostSampler &h, char name, const fl
     const uint32_t *indices = s->subset.data(); const uint32_t nIdx = (uint32_t)s->subset.size();
     const uint32_t nG = (subsetData && subsetGenes) ? nIdx : (genesInCols ? ncol : nrow);
     const uint32_t nS = (subsetData && !subsetGenes) ? nIdx : (genesInCols ? nrow : ncol);
-    SamplerDev &d = h.d; const bool sparse = p.useSparseOptimization != 0;
+    SamplerDev &d = h.d;
     sampler_dims(s, h, name, nG, nS);
     const size_t tot = (size_t)d.M * d.Npad;
     // With the default uncertainty the evaluation kernel recomputes S*S = max(0.1 D, 0.1)^2 from the D value it loads anyway
     // (bit-identical: the same three fp32 operations as the fill below): no S2 array, one row less per proposal from HBM.
     // (COGAPS_READ_S: diagnostics, keeps the array and the loads.)
-    const bool defaultS = !sparse && unc == nullptr && !dev_env("COGAPS_READ_S");
+    const bool defaultS = unc == nullptr && !dev_env("COGAPS_READ_S");
     float *dD = dalloc<float>(tot), *dS2 = defaultS ? nullptr : dalloc<float>(tot); h.Sraw = dalloc<float>(tot);
     // The vectors are staged through the host in blocks of at most 16 M elements (pad: D = 0, S = S2 = 1) -- never three dense
     // host copies of the matrix (BASELINE configs[4]'s shard is 2.5 GB per copy).  The sums run over the vectors in order, as
     // gaps::nonZeroMean does (MatrixMath.cpp:39-55).
     const uint32_t rowsPerBlock = (uint32_t)std::max<size_t>(1, std::min<size_t>(d.M, ((size_t)1 << 24) / std::max<uint32_t>(1u, d.Npad)));
     std::vector<float> D((size_t)rowsPerBlock * d.Npad), S2(dS2 ? D.size() : 0), SR(D.size());
-    std::vector<unsigned long long> fl; std::vector<uint32_t> pre, ptr; std::vector<float> vals;
-    if (sparse) { fl.assign((size_t)d.M * d.Wn, 0ull); pre.assign((size_t)d.M * d.Wn, 0u); ptr.assign((size_t)d.M + 1, 0u); }
     float sum = 0.f; unsigned nnz = 0;
     for (uint32_t j0 = 0; j0 < nS; j0 += rowsPerBlock) {
         const uint32_t j1 = std::min(nS, j0 + rowsPerBlock);
         std::fill(D.begin(), D.end(), 0.f); std::fill(SR.begin(), SR.end(), 1.f); if (dS2) std::fill(S2.begin(), S2.end(), 1.f);
         for (uint32_t j = j0; j < j1; ++j) {
-            if (sparse) ptr[j] = (uint32_t)vals.size();
             for (uint32_t i = 0; i < nG; ++i) {
                 const uint32_t dataRow = (subsetData && (subsetGenes != genesInCols)) ? indices[genesInCols ? j : i] - 1 : (genesInCols ? j : i);
                 const uint32_t dataCol = (subsetData && (subsetGenes == genesInCols)) ? indices[genesInCols ? i : j] - 1 : (genesInCols ? i : j);
-                float v = data[(size_t)dataRow * ncol + dataCol];
-                if (sparse && !(v > 0.f)) v = 0.f;                                // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
+                const float v = data[(size_t)dataRow * ncol + dataCol];
                 const size_t o = (size_t)(j - j0) * d.Npad + i;
                 D[o] = v;
-                const float sd = (unc && !sparse) ? unc[(size_t)dataRow * ncol + dataCol] : gm_max(v * 0.1f, 0.1f);   // gaps::pmax, MatrixMath.cpp:74-84; the sparse model always assumes the default (SparseNormalModel.h:90-96)
+                const float sd = unc ? unc[(size_t)dataRow * ncol + dataCol] : gm_max(v * 0.1f, 0.1f);   // gaps::pmax, MatrixMath.cpp:74-84
                 SR[o] = sd; if (dS2) S2[o] = sd * sd;
                 sum += v; if (v > 0.f) ++nnz;                                    // gaps::nonZeroMean, MatrixMath.cpp:39-55
-                if (sparse) {      // SparseMatrix: flag words, number of packed values before each word, the values
-                    const uint32_t w = i >> 6;
-                    if ((i & 63u) == 0u) pre[(size_t)j * d.Wn + w] = (uint32_t)vals.size() - ptr[j];
-                    if (v > 0.f) { fl[(size_t)j * d.Wn + w] |= 1ull << (i & 63u); vals.push_back(v); }
-                }
             }
-            if (sparse) for (uint32_t w = (nG + 63u) >> 6; w < d.Wn; ++w) pre[(size_t)j * d.Wn + w] = (uint32_t)vals.size() - ptr[j];   // the word past the last element (Wn = N/64 + 1)
         }
         const size_t off = (size_t)j0 * d.Npad, cnt = (size_t)(j1 - j0) * d.Npad;
         rt_h2d(dD + off, D.data(), cnt * 4, s->stream); if (dS2) rt_h2d(dS2 + off, S2.data(), cnt * 4, s->stream); rt_h2d(h.Sraw + off, SR.data(), cnt * 4, s->stream);
@@ -438,17 +428,7 @@ static void build_sampler(cogaps_session *s, HostSampler &h, char name, const fl
     }
     sampler_model(h, alpha, maxGibbsMass, sum, nnz);
     d.D = dD; d.S2 = dS2; d.defaultS = defaultS ? 1u : 0u;
-    if (!sparse) d.AP = dalloc<float>(tot);
-    else {
-        // SparseMatrix (flag words + packed values per vector) and the HybridMatrix copies; D / Sraw stay for meanChiSq
-        ptr[d.M] = (uint32_t)vals.size();
-        unsigned long long *dfl = dalloc<unsigned long long>(fl.size()); uint32_t *dpre = dalloc<uint32_t>(pre.size()), *dptr = dalloc<uint32_t>(ptr.size()); float *dv = dalloc<float>(vals.size() + 1);
-        rt_h2d(dfl, fl.data(), fl.size() * 8, s->stream); rt_h2d(dpre, pre.data(), pre.size() * 4, s->stream); rt_h2d(dptr, ptr.data(), ptr.size() * 4, s->stream);
-        if (!vals.empty()) rt_h2d(dv, vals.data(), vals.size() * 4, s->stream);
-        rt_sync(s->stream);
-        d.dflags = dfl; d.dprefix = dpre; d.dptr = dptr; d.dvals = dv;
-        sampler_sparse_model(h);
-    }
+    d.AP = dalloc<float>(tot);
     sampler_domain(s, h, alpha);
 }
 
@@ -522,7 +502,6 @@ static void spb_models(cogaps_session *s, SpbSide *side, HostSampler **hs, uint3
         sampler_sparse_model(*hs[w]);
         sampler_domain(s, *hs[w], alpha[w]);
     }
-    s->sparseInput = true;
 }
 // The two samplers' dimensions and their flag / prefix / pointer arrays (the session's from here on: free_sampler releases them if anything
 // later throws).  Sampler A: vectors = genes, elements = samples; P the other way round (GapsRunner.cpp:402-406).  Genes are the data's
@@ -542,29 +521,36 @@ static void spb_sides(cogaps_session *s, uint32_t nrow, uint32_t ncol, bool majo
     }
 }
 
-// Both samplers of a session from a compressed-sparse matrix (sparse_build.h): the packed structures build_sampler makes from the dense
-// form of the same matrix, built on the device.  No nrow x ncol array exists on either side: d.D, d.S2 and h.Sraw stay null.
+// Device temporaries of a build: not the session's (allocated under a null owner scope), released when the build returns or throws
+struct SpbTemps {
+    void *p[12] = {}; int n = 0;
+    ~SpbTemps() { for (void *q : p) rt_free(q); }
+    template <class T> T *alloc(size_t count) { rt_owner_scope notTheSessions(nullptr); T *q = dalloc<T>(count); p[n++] = q; return q; }
+    // one of the caller's arrays where the kernels read it: uploaded, or used where it is
+    template <class T> const T *stage(const T *src, size_t count, bool onDevice, rt_stream_t stream)
+    {
+        if (onDevice) return src;
+        T *q = alloc<T>(count + 1);
+        if (count) rt_h2d(q, src, count * sizeof(T), stream);
+        return q;
+    }
+    uint32_t *err() { return alloc<uint32_t>(4); }      // the error word, the two ordered sums
+};
+
+// Both samplers of a sparse-model session from a compressed-sparse matrix (sparse_build.h), built on the device: the caller's matrix
+// (cogaps_session_create_sparse) or the dense input's entries > 0 (build_samplers_dense_input).  No nrow x ncol array exists on either side.
 static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
 {
     const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
-    // the caller's three arrays on the device: uploaded once (temporaries: released below, not the session's), or used where they are
     uint64_t nnz = 0;
     if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, s->stream); rt_sync(s->stream); } else nnz = m.indptr[nMajor];
     if (nnz >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
     if (nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
-    struct Temps { void *p[4] = {nullptr, nullptr, nullptr, nullptr}; ~Temps() { for (void *q : p) rt_free(q); } } tmp;
-    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz; in.indptr = m.indptr; in.indices = m.indices; in.values = m.values;
-    uint32_t *err;
-    {
-        rt_owner_scope notTheSessions(nullptr);
-        if (!m.onDevice) {
-            uint64_t *ip = dalloc<uint64_t>((size_t)nMajor + 1); tmp.p[0] = ip; uint32_t *ix = dalloc<uint32_t>(nnz + 1); tmp.p[1] = ix; float *vv = dalloc<float>(nnz + 1); tmp.p[2] = vv;
-            rt_h2d(ip, m.indptr, ((size_t)nMajor + 1) * 8, s->stream);
-            if (nnz) { rt_h2d(ix, m.indices, nnz * 4, s->stream); rt_h2d(vv, m.values, nnz * 4, s->stream); }
-            in.indptr = ip; in.indices = ix; in.values = vv;
-        }
-        err = dalloc<uint32_t>(4); tmp.p[3] = err;      // the error word, the two ordered sums
-    }
+    SpbTemps tmp;
+    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz;
+    in.indptr = tmp.stage(m.indptr, (size_t)nMajor + 1, m.onDevice != 0, s->stream);
+    in.indices = tmp.stage(m.indices, nnz, m.onDevice != 0, s->stream); in.values = tmp.stage(m.values, nnz, m.onDevice != 0, s->stream);
+    uint32_t *err = tmp.err();
     SpbSide side[2];
     HostSampler *hs[2] = {&s->A, &s->P};
     spb_sides(s, m.nrow, m.ncol, m.majorIsRow != 0, side, hs);
@@ -579,33 +565,50 @@ static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_m
     spb_models(s, side, hs, kept, (float *)(err + 1));
 }
 
+// The sparse model from a dense matrix: its entries > 0 (SparseVector.cpp:20-33: NaN, zero and negative values are absent), row by row
+// in the data's own orientation, as the CSR matrix build_samplers_sparse_input takes.  subsetData picks rows or columns here, by
+// Matrix.cpp:30-69's rule: 1-based indices in the order given, on the genes or the samples (genes are the data's rows unless
+// transposeData); output row / column i is input indices[i] - 1, so the column indices ascend whatever the order of the subset.
+static void build_samplers_dense_input(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol)
+{
+    const cogaps_params &p = s->p;
+    const bool subsetData = p.subsetData && !s->subset.empty();
+    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0), subsetCols = subsetData && !subsetRows;
+    const uint32_t *indices = s->subset.data(); const uint32_t nIdx = (uint32_t)s->subset.size();
+    cogaps_sparse_matrix m; memset(&m, 0, sizeof(m));
+    m.nrow = subsetRows ? nIdx : nrow; m.ncol = subsetCols ? nIdx : ncol; m.majorIsRow = 1;
+    std::vector<uint64_t> indptr((size_t)m.nrow + 1, 0); std::vector<uint32_t> cols; std::vector<float> vals;
+    for (uint32_t r = 0; r < m.nrow; ++r) {
+        const float *row = data + (size_t)(subsetRows ? indices[r] - 1 : r) * ncol;
+        for (uint32_t c = 0; c < m.ncol; ++c) {
+            const float v = row[subsetCols ? indices[c] - 1 : c];
+            if (v > 0.f) { cols.push_back(c); vals.push_back(v); }
+        }
+        indptr[(size_t)r + 1] = vals.size();
+    }
+    m.indptr = indptr.data(); m.indices = cols.data(); m.values = vals.data();
+    build_samplers_sparse_input(s, m);
+}
+
 // Both samplers of a session from unordered triplets (sparse_build.h, the passes of its second half): the session cogaps_session_create
 // makes from the matrix the triplets denote -- the latest entry of a position decides it.  The temporaries (the caller's arrays uploaded,
 // the present flags with their prefix counts and pointers, one winner index per present position, one keep bit per entry) are O(nnz + one
-// sampler's flag arrays); they are not the session's and are released before this returns.
+// sampler's flag arrays).
 static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix &m)
 {
     const uint64_t nnz = m.nnz;
-    struct Temps { void *p[9] = {}; ~Temps() { for (void *q : p) rt_free(q); } } tmp;
-    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz; in.rows = m.rows; in.cols = m.cols; in.values = m.values;
+    SpbTemps tmp;
+    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz;
     SpbSide side[2], pres;
     HostSampler *hs[2] = {&s->A, &s->P};
     spb_sides(s, m.nrow, m.ncol, true, side, hs);
+    in.rows = tmp.stage(m.rows, nnz, m.onDevice != 0, s->stream); in.cols = tmp.stage(m.cols, nnz, m.onDevice != 0, s->stream);
+    in.values = tmp.stage(m.values, nnz, m.onDevice != 0, s->stream);
+    uint32_t *err = tmp.err();
     pres = side[0]; pres.vals = nullptr;
-    uint32_t *err; unsigned long long *keep;
-    {
-        rt_owner_scope notTheSessions(nullptr);
-        if (!m.onDevice) {
-            uint32_t *r = dalloc<uint32_t>(nnz + 1); tmp.p[0] = r; uint32_t *c = dalloc<uint32_t>(nnz + 1); tmp.p[1] = c; float *v = dalloc<float>(nnz + 1); tmp.p[2] = v;
-            if (nnz) { rt_h2d(r, m.rows, nnz * 4, s->stream); rt_h2d(c, m.cols, nnz * 4, s->stream); rt_h2d(v, m.values, nnz * 4, s->stream); }
-            in.rows = r; in.cols = c; in.values = v;
-        }
-        err = dalloc<uint32_t>(4); tmp.p[3] = err;      // the error word, the two ordered sums
-        pres.flags = dalloc<unsigned long long>((size_t)pres.M * pres.Wn); tmp.p[4] = pres.flags;
-        pres.prefix = dalloc<uint32_t>((size_t)pres.M * pres.Wn); tmp.p[5] = pres.prefix;
-        pres.ptr = dalloc<uint32_t>((size_t)pres.M + 1); tmp.p[6] = pres.ptr;
-        keep = dalloc<unsigned long long>(nnz / 64 + 1); tmp.p[7] = keep;
-    }
+    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
+    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
+    unsigned long long *keep = tmp.alloc<unsigned long long>(nnz / 64 + 1);
     // grid-stride over the entries: enough workgroups to fill the device, never more than the entries need (at least one)
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nnz + COO_BS - 1) / COO_BS, (uint64_t)s->computeUnits * 8u));
     const uint32_t vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
@@ -616,8 +619,7 @@ static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix 
     RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, pres.ptr, pres.M);
     RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, s->stream, pres);
     uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, s->stream); rt_sync(s->stream);
-    uint32_t *winner;
-    { rt_owner_scope notTheSessions(nullptr); winner = dalloc<uint32_t>((size_t)nPresent + 1); tmp.p[8] = winner; }
+    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
     RT_LAUNCH(coo_winner_kernel, grid, COO_BS, s->stream, in, pres, winner);
     RT_LAUNCH(coo_keep_kernel, grid, COO_BS, s->stream, in, pres, (const uint32_t *)winner, side[0], side[1], keep);
     for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
@@ -1189,9 +1191,10 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
         if (sp) build_samplers_sparse_input(s, *sp);
         else if (coo) build_samplers_coo_input(s, *coo);
+        else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
         else {
-        build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
-        build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
+            build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
+            build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
         }
         s->nGenes = s->A.d.M; s->nSamples = s->P.d.M; s->K = p.nPatterns;
         if (s->A.d.N != s->P.d.M || s->P.d.N != s->A.d.M) throw std::runtime_error("internal: sampler dimensions do not mirror");
@@ -1823,7 +1826,7 @@ int cogaps_session_finish(cogaps_session *s, cogaps_result *out)
             RT_LAUNCH(mean_chisq_seq_kernel, 1, 256, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
             rt_d2h(&out->meanChiSq, s->P.partial, 4, s->stream); rt_sync(s->stream);
         } else {
-        if (s->sparseInput) LAUNCH_V(mean_chisq_rows_packed_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);      // (no dense D / Sraw: sparse_build.h)
+        if (s->P.d.sparse) LAUNCH_V(mean_chisq_rows_packed_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);      // (no dense D / Sraw: sparse_build.h)
         else LAUNCH_V(mean_chisq_rows_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
         std::vector<float> part(s->P.d.M);
         rt_d2h(part.data(), s->P.partial, (size_t)s->P.d.M * 4, s->stream); rt_sync(s->stream);

@@ -1,7 +1,7 @@
-// sparse_build.h -- the sparse model's data structures built on the device from a compressed-sparse matrix (CSR or CSC) or from unordered
-// triplets (COO: further down), and
-// meanChiSq from them: what build_sampler (cogaps_hip.cpp) builds on the host from a dense matrix, bit for bit, without an
-// nrow x ncol array anywhere.
+// sparse_build.h -- the sparse model's data structures, built on the device from a compressed-sparse matrix (CSR or CSC) or from unordered
+// triplets (COO: further down), and meanChiSq from them.  Every sparse-model session is built here, whatever its input: a dense matrix
+// is compacted to CSR on the host first (cogaps_hip.cpp, build_samplers_dense_input).  These four arrays per sampler are all the data
+// such a session holds: no genes x samples array exists on the device.
 //
 // A sampler holds its data as [vector j][element i]: dflags [M][Wn] (bit i of vector j: the entry is > 0), dprefix [M][Wn] (packed
 // values of the vector before each flag word), dptr [M + 1] (first packed value of each vector), dvals (the values > 0, vector by
@@ -10,8 +10,8 @@
 //   1. spb_validate_count_kernel: checks the input, counts the kept entries per vector into dptr, sets the flag bits (64-bit atomic OR)
 //   2. spb_scan_kernel: dptr = exclusive scan of the counts; spb_prefix_kernel: dprefix = popcount scan over each vector's flag words
 //   3. spb_scatter_kernel: every kept entry computes its own slot dptr[j] + dprefix[j][i >> 6] + popcount(flags below bit i)
-// and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order -- the sum build_sampler forms
-// over the dense elements in (j, i) order (zeros add nothing), which feeds lambda.
+// and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order -- gaps::nonZeroMean's sum over
+// the dense elements in (j, i) order (zeros add nothing), which feeds lambda.
 #pragma once
 #include "gaps_state.h"
 #include "eval_kernel.h"
@@ -89,8 +89,8 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(SPB_SCAN_BS) spb_scan_kernel(uint32_t *cnt, uint
     if (t == (uint32_t)SPB_SCAN_BS - 1u) cnt[n] = run[t];
 }
 
-// dprefix[j][w] = entries of vector j below flag word w -- all Wn words, the word past the last element (Wn = N/64 + 1) included, as
-// build_sampler fills them.  One wave per vector, 64 words per round.
+// dprefix[j][w] = entries of vector j below flag word w -- all Wn words, the word past the last element (Wn = N/64 + 1) included.
+// One wave per vector, 64 words per round.
 CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_prefix_kernel(SpbSide s)
 {
     const uint32_t lane = cg_tid() & 63u, j = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
@@ -226,8 +226,8 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_scatter_kernel(CooIn in, SpbSide a, 
 }
 
 // GapsStatistics::meanChiSq per-vector partials (aux_kernels.h, mean_chisq_rows_kernel) with the data taken from the P sampler's packed
-// form: d = the packed value where the flag bit is set, 0 elsewhere, sd = max(0.1 d, 0.1) -- the three fp32 operations that fill Sraw
-// in build_sampler.  Same lanes, chunks, slots and finish as the dense-input kernel: the partials are the same bits.
+// form: d = the packed value where the flag bit is set, 0 elsewhere, sd = max(0.1 d, 0.1) -- the default uncertainty, as the dense
+// model's build_sampler fills Sraw.  Same lanes, chunks, slots and finish as the dense model's kernel.
 template <int V>
 CG_KERNEL void CG_LAUNCH_BOUNDS(1024) mean_chisq_rows_packed_kernel(SamplerDev P, const float *Asum, const float *Psum, uint32_t AMpad, float n2, float *partial)
 {

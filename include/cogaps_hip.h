@@ -185,6 +185,11 @@ typedef struct cogaps_trace_rec {   /* one queued proposal, ProposalQueue.h:15-2
     uint32_t batch;
 } cogaps_trace_rec;
 
+/* With useSparseOptimization = 1 the session holds the sparse model's packed data only -- per sampler the flag words, prefix counts,
+ * pointers and values of the entries > 0, built on the device (csrc/sparse_build.h) -- and no nrow x ncol array, whichever of the
+ * three entries created it: this one compacts the dense matrix to CSR on the host (applying subsetData; `uncertainty` is ignored,
+ * the model knows the default only) and goes through the builder of cogaps_session_create_sparse.  A dense matrix with 2^32 - 1
+ * or more entries > 0 is refused with that builder's message. */
 cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t ncol,
                                       const cogaps_params *params, const float *uncertainty,
                                       int data_on_device);
@@ -200,7 +205,7 @@ void cogaps_session_destroy(cogaps_session *s);
  * uploaded once; with onDevice = 1 nothing is copied to the host but indptr[nMajor].  The caller's arrays are not referenced after the
  * call returns.  Stored entries that are not > 0 (zeros, negatives, NaN) are dropped, as the sparse model drops them from a dense matrix.
  * Errors (NULL / 1, cogaps_last_error): useSparseOptimization = 0; subsetData (pass the subset's rows / columns instead); reductionMode
- * COGAPS_REDUCE_SEQ (the verification mode takes dense input for now: a follow-up); indptr that does not start at 0, decreases or does
+ * COGAPS_REDUCE_SEQ (the verification mode takes dense input); indptr that does not start at 0, decreases or does
  * not end at the number of stored entries; an index >= the minor dimension; indices not strictly ascending inside a row / column
  * (duplicates included); 2^32 - 1 stored entries or more.  The input is validated on the device before anything is built from it.
  * transposeData, whichMatrixFixed / fixedPatterns and everything else in cogaps_params work as for the dense entry points; such a session
@@ -250,8 +255,8 @@ int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, coga
 /* Bytes of device memory the session holds: the sum of its own allocations (as requested), counted as they are made and released -- not
  * hipMemGetInfo, which is device-wide.  For every session, however it was created. */
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes);
-/* HIP-event time of the two ordered fp32 sums over the packed values at the creation of a session from a compressed-sparse matrix
- * (the one serial pass of that path; 0 for a session created from a dense matrix) */
+/* HIP-event time of the two ordered fp32 sums over the packed values at the creation of a sparse-model session, whatever its input
+ * (the one serial pass of the build; 0 for a session of the dense model) */
 int cogaps_session_sparse_build_ms(cogaps_session *s, float *orderedSumMs);
 /* test hook: the sparse model's data structures of sampler `which` -- flags / prefix [M][Wn], ptr [M + 1], vals [nVals] -- and the
  * constants derived from the data; NULL skips an output (sizes first, then the arrays) */

@@ -8,12 +8,16 @@ from cogaps_amd import _capi
 import pyoracle as po
 
 
-def make_pair(lib, data, **kw):
+def make_pair(lib, data, oracle_data=None, **kw):
+    """oracle_data: the matrix of the subset, taken outside the oracle -- it then gets that matrix and no subsetIndices / subsetDim"""
     S = _capi.Session(data, lib=lib, **kw)
     wA = lib.cogaps_reduction_width(S.dims("A")[1])
     wP = lib.cogaps_reduction_width(S.dims("P")[1])
     okw = dict(kw)
     okw.pop("device", None)
+    if oracle_data is not None:
+        data = oracle_data
+        okw.pop("subsetIndices", None), okw.pop("subsetDim", None)
     if okw.pop("reductionMode", "lanes") == "seq":
         # verification mode: the reference's own order (one accumulator) and the session's math mode
         math = {"portable": po.MATH_PORTABLE, "glibc-fma": po.MATH_GLIBC_FMA, "glibc-sse2": po.MATH_GLIBC_SSE2}[okw.pop("mathMode", "portable")]
@@ -51,6 +55,51 @@ def assert_state_equal(S, O, tag, chisq=True, ap=True):
         assert S.check_domain(w) == 0, "%s %s: the atomic domain's cached neighbour positions / masses or links are inconsistent" % (tag, w)
         if chisq:
             assert S.chisq(w) == O.chisq(w), "%s %s: chi2 differs" % (tag, w)
+
+
+STRUCT_FIELDS = ("flags", "prefix", "ptr", "vals")
+
+
+def structures(S):
+    """the sparse model's data of both samplers as the session holds it (cogaps_session_debug_sparse_data)"""
+    return {w: S.debug_sparse_data(w) for w in "AP"}
+
+
+def assert_structures_equal(a, b, tag=""):
+    for w in "AP":
+        for f in STRUCT_FIELDS:
+            assert a[w][f].dtype == b[w][f].dtype and a[w][f].shape == b[w][f].shape and np.array_equal(a[w][f], b[w][f]), "%s %s %s differs" % (tag, w, f)
+        for f in ("lambda", "maxGibbsMass"):      # (as bits: an empty matrix has lambda = NaN in both)
+            assert np.float32(a[w][f]).tobytes() == np.float32(b[w][f]).tobytes(), "%s %s %s differs" % (tag, w, f)
+
+
+def packed_reference(data, nPatterns, transposeData=False):
+    """What structures() must return for a sparse-model session of the dense matrix `data`, from the definition of the four arrays
+    (csrc/sparse_build.h's header) in numpy and independent of the library.  Sampler A's data vectors are the genes (elements:
+    samples), sampler P's the samples; genes are the rows of `data` unless transposeData.  Per sampler, over vectors j = 0 .. M-1 of
+    N elements, with Wn = N // 64 + 1 flag words per vector:
+      flags[j][w]  bit b set: element 64 w + b of vector j is > 0 (NaN, zero and negative entries are absent)
+      prefix[j][w] number of entries > 0 of vector j below element 64 w
+      ptr[j]       number of entries > 0 of the vectors before j; ptr[M] their total
+      vals         the entries > 0, vector by vector, ascending element index
+    lambda and maxGibbsMass are the oracle's (default alpha and maxGibbsMass)."""
+    data = np.asarray(data, dtype=np.float32)
+    genes_by_samples = data.T if transposeData else data
+    O = po.Session(data, nPatterns=nPatterns, seed=1, sparseOptimization=True, transposeData=transposeData)
+    out = {}
+    for w, mat in (("A", genes_by_samples), ("P", genes_by_samples.T)):
+        M, N = mat.shape
+        Wn = N // 64 + 1
+        kept = np.zeros((M, Wn * 64), dtype=bool)
+        kept[:, :N] = mat > 0
+        flags = np.ascontiguousarray(np.packbits(kept, axis=1, bitorder="little")).view("<u8").astype(np.uint64)
+        per_word = kept.reshape(M, Wn, 64).sum(axis=2, dtype=np.uint32)
+        prefix = (np.cumsum(per_word, axis=1, dtype=np.uint32) - per_word).astype(np.uint32)
+        ptr = np.concatenate([[0], np.cumsum(per_word.sum(axis=1, dtype=np.uint64))]).astype(np.uint32)
+        out[w] = {"flags": flags, "prefix": prefix, "ptr": ptr, "vals": np.ascontiguousarray(mat)[kept[:, :N]],
+                  "lambda": O.lam(w), "maxGibbsMass": O.max_gibbs_mass(w)}
+    O.close()
+    return out
 
 
 def run_stepwise(lib, data, n_iter, trace=True, total_iter=None, check_every=1, **kw):

@@ -1,8 +1,9 @@
 """Triplet (COO) and Matrix Market input of the sparse model (cogaps_session_create_coo, cogaps_read_mtx_triplets, the second half of
 csrc/sparse_build.h) on the test-only emulator build.  Triplets denote D = 0; D[rows[k], cols[k]] = values[k] in input order -- the
 latest entry of a position decides it -- and a session created from them is the session created from that dense D, bit for bit:
-structure by structure against the dense-input session, step by step against the oracle, and through the file route and the front
-ends."""
+structure by structure against the dense-input session and against the definition of the structures in numpy
+(parity_util.packed_reference: the dense-input session goes through the same device build as the compressed one), step by step
+against the oracle, and through the file route and the front ends."""
 import ctypes
 import os
 
@@ -12,11 +13,11 @@ import scipy.sparse as sp
 
 import parity_util as pu
 from cogaps_amd import _capi
+from parity_util import assert_structures_equal, structures
 from test_sparse_input import SHAPES
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GIST = os.path.join(GOLDEN, "GIST.mtx")
-STRUCT_FIELDS = ("flags", "prefix", "ptr", "vals")
 RESULT_FIELDS = ("Amean", "Asd", "Pmean", "Psd", "chisq", "atomsA", "atomsP")
 
 
@@ -63,25 +64,17 @@ def coo_of(data, seed, repeats=0.0):
     return _capi.CooMatrix(data.shape, r, c, v)
 
 
-def structures(S):
-    return {w: S.debug_sparse_data(w) for w in "AP"}
-
-
-def assert_structures_equal(a, b, tag=""):
-    for w in "AP":
-        for f in STRUCT_FIELDS:
-            assert a[w][f].shape == b[w][f].shape and np.array_equal(a[w][f], b[w][f]), "%s %s %s differs" % (tag, w, f)
-        for f in ("lambda", "maxGibbsMass"):      # (as bits: an empty matrix has lambda = NaN in both)
-            assert np.float32(a[w][f]).tobytes() == np.float32(b[w][f]).tobytes(), "%s %s %s differs" % (tag, w, f)
-
-
 def assert_same_session_as_dense(lib, shape, rows, cols, values, **kw):
-    """the session from the triplets against the dense-input session of the loop-built matrix; returns the latter's structures"""
+    """the session from the triplets against the dense-input session of the loop-built matrix, and both against the numpy packer's
+    structures of that matrix; returns the dense-input session's structures"""
     kw = dict(dict(lib=lib, nPatterns=2, seed=3, sparseOptimization=True), **kw)
     dense = densify(shape, rows, cols, values)
     D, S = _capi.Session(dense, **kw), _capi.Session(_capi.CooMatrix(shape, rows, cols, values), **kw)
     d = structures(D)
     assert_structures_equal(d, structures(S))
+    ref = pu.packed_reference(dense, kw["nPatterns"], transposeData=kw.get("transposeData", False))
+    assert_structures_equal(ref, d, "dense input")
+    assert_structures_equal(ref, structures(S), "triplet input")
     for w in "AP":
         assert np.float32(D.chisq(w)).tobytes() == np.float32(S.chisq(w)).tobytes()
     D.close(), S.close()
@@ -122,6 +115,9 @@ def test_structures_equal_the_dense_input_session(emul_lib, transpose):
     kw = dict(lib=lib, nPatterns=5, seed=2, sparseOptimization=True, transposeData=transpose)
     D, C = _capi.Session(data, **kw), _capi.Session(sp.csr_matrix(data), **kw)
     d = structures(D)
+    ref = pu.packed_reference(data, 5, transposeData=transpose)
+    assert_structures_equal(ref, d, "dense input")
+    assert_structures_equal(ref, structures(C), "CSR input")
     assert d["A"]["flags"].shape[1] > 1 and d["P"]["flags"].shape[1] > 1 and d["A"]["vals"].size >= 10000
     orders = []
     for seed in (1, 2):
@@ -130,9 +126,10 @@ def test_structures_equal_the_dense_input_session(emul_lib, transpose):
         assert np.array_equal(densify(data.shape, m.rows, m.cols, m.values), data)
         S = _capi.Session(m, **kw)
         assert_structures_equal(d, structures(S), "shuffle %d" % seed)
+        assert_structures_equal(ref, structures(S), "triplet input, shuffle %d" % seed)
         for w in "AP":
             assert D.chisq(w) == S.chisq(w)
-        assert S.device_bytes() == C.device_bytes() < D.device_bytes()
+        assert S.device_bytes() == C.device_bytes() == D.device_bytes()
         S.close()
     assert not np.array_equal(orders[0], orders[1])
     D.close(), C.close()

@@ -8,7 +8,8 @@ import pytest
 import scipy.sparse as sp
 
 import parity_util as pu
-from test_coo_input import RESULT_FIELDS, assert_structures_equal, coo_of, densify, run_stepwise_coo, structures
+from parity_util import assert_structures_equal, structures
+from test_coo_input import RESULT_FIELDS, coo_of, densify, run_stepwise_coo
 from test_sparse_input import SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -29,12 +30,15 @@ def test_structures_and_memory(hip_lib):
     kw = dict(lib=hip_lib, nPatterns=3, seed=1, sparseOptimization=True)
     T, S, D = _capi.Session(m, **kw), _capi.Session(data, **kw), _capi.Session(dense, **kw)
     t_bytes, s_bytes, d_bytes = T.device_bytes(), S.device_bytes(), D.device_bytes()
-    print("device bytes: dense input %d, CSR input %d, triplet input %d, six dense arrays %d" % (d_bytes, s_bytes, t_bytes, 6 * genes * samples * 4))
+    print("device bytes: dense input %d, CSR input %d, triplet input %d, one dense array %d" % (d_bytes, s_bytes, t_bytes, genes * samples * 4))
     d = structures(D)
     assert_structures_equal(d, structures(T))
+    ref = pu.packed_reference(dense, 3)
+    for name, sess in (("dense", D), ("CSR", S), ("triplet", T)):
+        assert_structures_equal(ref, structures(sess), name + " input")
     assert d["A"]["vals"].size > 10000
-    assert t_bytes == s_bytes
-    assert d_bytes - t_bytes >= 6 * genes * samples * 4 - (1 << 20) and t_bytes > 0
+    assert d_bytes == s_bytes == t_bytes and t_bytes > 0
+    assert d_bytes < genes * samples * 4
     T.close(), S.close(), D.close()
 
 
@@ -52,6 +56,9 @@ def test_contention(hip_lib):
     kw = dict(lib=hip_lib, nPatterns=3, seed=1, sparseOptimization=True)
     T, D = _capi.Session(_capi.CooMatrix((130, 70), r, c, v), **kw), _capi.Session(dense, **kw)
     assert_structures_equal(structures(D), structures(T))
+    ref = pu.packed_reference(dense, 3)
+    assert_structures_equal(ref, structures(D), "dense input")
+    assert_structures_equal(ref, structures(T), "triplet input")
     T.close(), D.close()
 
 

@@ -354,6 +354,19 @@ def test_verification_mode_full_run(emul_lib, modsim, oracle):
     assert r["totalUpdates"] == o["totalUpdates"] and r["meanChiSq"] == o["meanChiSq"] and r["averageQueueLengthP"] == o["averageQueueLengthP"]
 
 
+def test_verification_mode_sparse_full_run(emul_lib, oracle):
+    """... and with the sparse model, whose session holds the packed data only: meanChiSq in the reference's order (genes outer, samples
+    inner, one accumulator) reads the data through the flag words"""
+    from cogaps_amd import _capi
+    data = pu.synthetic_counts(150, 30, zeros=0.8, seed=21)
+    kw = dict(nPatterns=4, nIterations=40, seed=42, outputFrequency=10, sparseOptimization=True)
+    r = _capi.run(data, lib=emul_lib(256), **SEQ, **kw)
+    o = oracle.run(data, math_mode=oracle.MATH_GLIBC_FMA, **kw)
+    for f in ("atomsA", "atomsP", "chisq", "Amean", "Pmean", "Asd", "Psd"):
+        assert np.array_equal(r[f], o[f]), f
+    assert r["totalUpdates"] == o["totalUpdates"] and r["meanChiSq"] == o["meanChiSq"] and o["meanChiSq"] > 0
+
+
 def test_math_modes_on_the_host(emul_lib, oracle):
     """cogaps_debug_math (host side of the shared source): the glibc modes equal the committed libm vectors, the portable mode the
     oracle's portable functions"""

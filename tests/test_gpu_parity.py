@@ -145,6 +145,19 @@ def test_verification_mode_stepwise(hip_lib, gist):
     pu.run_stepwise(hip_lib, pu.synthetic_counts(900, 20, zeros=0.8, seed=9), 20, nPatterns=6, seed=12, total_iter=40, check_every=5, sparseOptimization=True, **SEQ)
 
 
+def test_verification_mode_sparse_full_run(hip_lib, oracle):
+    """cogaps_run in verification mode with the sparse model = the oracle's run in the same arithmetic, statistics and meanChiSq included
+    (a sparse-model session holds the packed data only: the sequential meanChiSq reads the data through the flag words)"""
+    from cogaps_amd import _capi
+    data = pu.synthetic_counts(150, 30, zeros=0.8, seed=21)
+    kw = dict(nPatterns=4, nIterations=40, seed=42, outputFrequency=10, sparseOptimization=True)
+    r = _capi.run(data, lib=hip_lib, **SEQ, **kw)
+    o = oracle.run(data, math_mode=oracle.MATH_GLIBC_FMA, **kw)
+    for f in ("atomsA", "atomsP", "chisq", "Amean", "Pmean", "Asd", "Psd"):
+        assert np.array_equal(r[f], o[f]), f
+    assert r["totalUpdates"] == o["totalUpdates"] and r["meanChiSq"] == o["meanChiSq"] and o["meanChiSq"] > 0
+
+
 @pytest.mark.parametrize("case", range(40, 56))
 def test_random_shapes_verification_mode(hip_lib, case):
     """sixteen more random shapes in the verification mode (the reference's scalar order, glibc's logf / expf) against the oracle

@@ -1,6 +1,8 @@
 """Compressed-sparse input of the sparse model (cogaps_session_create_sparse, csrc/sparse_build.h) on the test-only emulator build:
 a session created from the CSR / CSC form of a matrix is the session created from its dense form, bit for bit -- against the oracle
-(which only knows dense matrices) step by step, structure by structure against the dense-input session, and through the front ends."""
+(which only knows dense matrices) step by step, structure by structure against the dense-input session and against the definition of
+the structures in numpy (parity_util.packed_reference: the dense-input session goes through the same device build), and through the
+front ends."""
 import ctypes
 import os
 import socket
@@ -105,6 +107,9 @@ def test_structures_equal_the_dense_input_sessions(emul_lib, fmt, transpose):
         data = np.ascontiguousarray(data.T)
     kw = dict(lib=lib, nPatterns=5, seed=2, sparseOptimization=True, transposeData=transpose)
     D, S = _capi.Session(data, **kw), _capi.Session(getattr(sp, fmt + "_matrix")(data), **kw)
+    ref = pu.packed_reference(data, 5, transposeData=transpose)
+    pu.assert_structures_equal(ref, pu.structures(D), "dense input")
+    pu.assert_structures_equal(ref, pu.structures(S), fmt + " input")
     for w in "AP":
         a, b = D.debug_sparse_data(w), S.debug_sparse_data(w)
         assert a["flags"].shape[1] > 1
@@ -130,7 +135,7 @@ def test_full_run_matches_oracle(emul_lib, oracle, fmt):
         assert r["totalUpdates"] == o["totalUpdates"] and r["meanChiSq"] == o["meanChiSq"]
         if fields:
             assert r["samplingSnapshotsA"].shape[0] == 4
-    # ... and the dense-input run of the library (meanChiSq from the dense arrays there, from the packed data here)
+    # ... and the dense-input run of the library
     assert _capi.run(data, lib=lib, **kw, **extra)["meanChiSq"] == r["meanChiSq"]
 
 
@@ -177,7 +182,8 @@ def test_rejections(emul_lib):
 
 
 def test_no_dense_array_is_kept_on_the_device(emul_lib):
-    """the six dense arrays (D, S2, Sraw of both samplers) are what a dense-input sparse-model session holds beyond a sparse-input one"""
+    """a sparse-model session holds the packed data and nothing of the size of the matrix, whatever form its input had: the session
+    from the dense matrix holds what the session from its CSR form holds, less than one genes x samples array of floats"""
     lib = emul_lib(256)
     genes, samples = 3000, 2500
     rng = np.random.default_rng(3)
@@ -187,9 +193,13 @@ def test_no_dense_array_is_kept_on_the_device(emul_lib):
     S = _capi.Session(data, **kw)
     D = _capi.Session(data.toarray(), **kw)
     s_bytes, d_bytes = S.device_bytes(), D.device_bytes()
-    print("device bytes: dense input %d, sparse input %d, difference %d, six dense arrays %d" % (d_bytes, s_bytes, d_bytes - s_bytes, 6 * genes * samples * 4))
-    assert d_bytes - s_bytes >= 6 * genes * samples * 4 - (1 << 20)
+    print("device bytes: dense input %d, sparse input %d, one dense array %d" % (d_bytes, s_bytes, genes * samples * 4))
+    assert d_bytes == s_bytes
+    assert d_bytes < genes * samples * 4
     assert s_bytes > 0
+    ref = pu.packed_reference(data.toarray(), 3)
+    pu.assert_structures_equal(ref, pu.structures(D), "dense input")
+    pu.assert_structures_equal(ref, pu.structures(S), "csr input")
     for w in "AP":
         a, b = D.debug_sparse_data(w), S.debug_sparse_data(w)
         assert np.array_equal(a["vals"], b["vals"]) and np.array_equal(a["flags"], b["flags"]) and a["lambda"] == b["lambda"]

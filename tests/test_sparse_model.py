@@ -83,6 +83,20 @@ def test_sparse_transposed_subset_fixed(emul_lib):
     pu.run_stepwise(emul_lib(256), data, 20, trace=False, nPatterns=4, seed=3, total_iter=40, sparseOptimization=True, whichMatrixFixed="P", fixedPatterns=fixed)
 
 
+def test_sparse_subset_of_a_dense_matrix(emul_lib):
+    """subsetData with the sparse model through the C ABI: the subset is taken where the dense matrix is compacted, in the order the
+    indices are given (Matrix.cpp:55-62).  The oracle gets the matrix of the subset, cut out here, and no indices: genes in descending
+    order; samples in a shuffled order together with transposeData (the data is then samples x genes and the indices pick its rows)"""
+    data = pu.synthetic_counts(240, 36, zeros=0.8, seed=9)
+    kw = dict(trace=False, nPatterns=4, seed=3, total_iter=40, sparseOptimization=True)
+    idx = np.arange(5, 125, dtype=np.uint32)[::-1].copy()
+    pu.run_stepwise(emul_lib(256), data, 20, oracle_data=data[idx - 1], subsetIndices=idx, subsetDim=1, **kw)
+    transposed = np.ascontiguousarray(data.T)
+    idx = (np.random.default_rng(4).permutation(36)[:24] + 1).astype(np.uint32)
+    assert not np.array_equal(idx, np.sort(idx))
+    pu.run_stepwise(emul_lib(256), transposed, 20, oracle_data=transposed[idx - 1], subsetIndices=idx, subsetDim=2, transposeData=True, **kw)
+
+
 def test_sparse_full_run_matches_oracle(emul_lib, oracle):
     from cogaps_amd import _capi
     data = pu.synthetic_counts(150, 30, zeros=0.8, seed=21)
