@@ -1,11 +1,12 @@
 """cogaps_amd -- the CoGAPS asynchronous Gibbs sampler hot path on MI355X (HIP, gfx950).
 
 Public surface mirrors the reference's: CoGAPS(), GWCoGAPS(), scCoGAPS(), CogapsParams, CogapsResult,
-buildReport(), checkpointsEnabled(), compiledWithOpenMPSupport().  All compute goes through
+DeviceMatrix (a sparse matrix uploaded to the GPU once, the source of any number of runs and subsets), buildReport(), checkpointsEnabled(), compiledWithOpenMPSupport().  All compute goes through
 csrc/libcogaps_hip.so (include/cogaps_hip.h); importing works without a GPU, running does not."""
 from .params import CogapsParams
 from .result import CogapsResult
 from .api import CoGAPS, GWCoGAPS, scCoGAPS
+from ._capi import DeviceMatrix
 
 
 def buildReport():
@@ -22,5 +23,5 @@ def compiledWithOpenMPSupport():
     return bool(_capi.load().cogaps_compiled_with_openmp())
 
 
-__all__ = ["CoGAPS", "GWCoGAPS", "scCoGAPS", "CogapsParams", "CogapsResult", "buildReport", "checkpointsEnabled",
+__all__ = ["CoGAPS", "GWCoGAPS", "scCoGAPS", "CogapsParams", "CogapsResult", "DeviceMatrix", "buildReport", "checkpointsEnabled",
            "compiledWithOpenMPSupport"]

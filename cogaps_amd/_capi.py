@@ -94,6 +94,8 @@ EXPORTS = [
     "cogaps_run_from_file", "cogaps_read_matrix_file", "cogaps_read_matrix_file_subset", "cogaps_matrix_free", "cogaps_file_info", "cogaps_debug_math", "cogaps_current_device", "cogaps_device_memory",
     "cogaps_session_create_sparse", "cogaps_run_sparse", "cogaps_session_device_bytes", "cogaps_session_sparse_build_ms", "cogaps_session_debug_sparse_data",
     "cogaps_session_create_coo", "cogaps_run_coo", "cogaps_read_mtx_triplets", "cogaps_triplets_free",
+    "cogaps_device_matrix_create_sparse", "cogaps_device_matrix_create_coo", "cogaps_device_matrix_destroy", "cogaps_device_matrix_info",
+    "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -145,6 +147,16 @@ def bind(L):
     L.cogaps_session_create_coo.restype = vp
     L.cogaps_session_create_coo.argtypes = [C.POINTER(CogapsCooMatrixC), C.POINTER(CogapsParamsC)]
     L.cogaps_run_coo.argtypes = [C.POINTER(CogapsCooMatrixC), C.POINTER(CogapsParamsC), C.POINTER(CogapsResultC)]
+    L.cogaps_device_matrix_create_sparse.restype = vp
+    L.cogaps_device_matrix_create_sparse.argtypes = [C.POINTER(CogapsSparseMatrixC), C.c_int]
+    L.cogaps_device_matrix_create_coo.restype = vp
+    L.cogaps_device_matrix_create_coo.argtypes = [C.POINTER(CogapsCooMatrixC), C.c_int]
+    L.cogaps_device_matrix_destroy.argtypes = [vp]
+    L.cogaps_device_matrix_destroy.restype = None
+    L.cogaps_device_matrix_info.argtypes = [vp, u32p, u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.cogaps_session_create_from_device_matrix.restype = vp
+    L.cogaps_session_create_from_device_matrix.argtypes = [vp, C.POINTER(CogapsParamsC)]
+    L.cogaps_run_device_matrix.argtypes = [vp, C.POINTER(CogapsParamsC), C.POINTER(CogapsResultC)]
     L.cogaps_read_mtx_triplets.argtypes = [C.c_char_p, C.c_int, u32p, C.c_uint32, u32p, u32p, C.POINTER(C.c_uint64), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(fp)]
     L.cogaps_triplets_free.argtypes = [u32p, u32p, fp]
     L.cogaps_triplets_free.restype = None
@@ -391,11 +403,71 @@ class CooMatrix:
         return sp.csr_matrix((self.values[keep], (self.rows[keep], self.cols[keep])), shape=self.shape, dtype=np.float32)
 
 
+class DeviceMatrix:
+    """A matrix resident on one GPU (cogaps_device_matrix of include/cogaps_hip.h): uploaded, validated and -- for triplets -- resolved
+    for repeated positions once; Session / run / run_batch / CoGAPS then make any number of sparse-model sessions from it, each with its
+    own nPatterns, seed, transposeData and subsetIndices / subsetDim (the subset is taken on the device, by the dense entry's rule: the
+    1-based indices in the order given, a repeated index repeats the row / column).  `data`: a scipy.sparse matrix, a SparseMatrix, a
+    CooMatrix (host or device arrays) or the path of a .mtx file (read as triplets, never densified).  device = -1: the calling
+    thread's current one.  May be closed while sessions made from it live on."""
+
+    def __init__(self, data, device=-1, lib=None):
+        self.L = lib if lib is not None else load()
+        self.h = None
+        if isinstance(data, (str, bytes, os.PathLike)):
+            data = read_mtx_triplets(data, lib=self.L)
+        elif is_sparse(data):
+            data = SparseMatrix.from_scipy(data)
+        if not isinstance(data, (SparseMatrix, CooMatrix)):
+            raise TypeError("DeviceMatrix takes a scipy.sparse matrix, a SparseMatrix, a CooMatrix or the path of a .mtx file")
+        # what the front end's input checks (api.check_inputs) need to know of the host values; None: device arrays, never seen here
+        self.has_na = None if data.on_device else bool(np.isnan(data.values).any())
+        self.has_negative = None if data.on_device else bool((data.values < 0).any())
+        m = data.c_struct()
+        name = "cogaps_device_matrix_create_coo" if isinstance(data, CooMatrix) else "cogaps_device_matrix_create_sparse"
+        self.h = getattr(self.L, name)(C.byref(m), int(device))
+        if not self.h:
+            raise _error(self.L, name + ": ")
+        nr, nc, nnz, dev = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_int()
+        if self.L.cogaps_device_matrix_info(self.h, C.byref(nr), C.byref(nc), C.byref(nnz), None, C.byref(dev)):
+            raise _error(self.L)
+        self.shape, self.nnz, self.device = (nr.value, nc.value), int(nnz.value), dev.value
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the DeviceMatrix is closed")
+        return self.h
+
+    def device_bytes(self):
+        """bytes of device memory the handle holds (never part of a session's device_bytes())"""
+        v = C.c_uint64(0)
+        if self.L.cogaps_device_matrix_info(self._handle(), None, None, None, C.byref(v), None):
+            raise _error(self.L)
+        return int(v.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.cogaps_device_matrix_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _sparse_input(data, unc, kw):
-    """the SparseMatrix / CooMatrix to hand to the library's compressed-sparse / triplet entry, or None for the dense entry.  A
-    scipy.sparse matrix goes in compressed form when the run uses the sparse model; the dense model takes it densified (the caller
-    does: toarray())."""
-    if isinstance(data, (SparseMatrix, CooMatrix)):
+    """the SparseMatrix / CooMatrix / DeviceMatrix to hand to the library's compressed-sparse / triplet / device-matrix entry, or None
+    for the dense entry.  A scipy.sparse matrix goes in compressed form when the run uses the sparse model; the dense model takes it
+    densified (the caller does: toarray())."""
+    if isinstance(data, (SparseMatrix, CooMatrix, DeviceMatrix)):
         if unc is not None:
             raise ValueError("the sparse model takes no uncertainty matrix")
         return data
@@ -413,12 +485,19 @@ def _dense(a):
 class Session:
     """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h).  `data`: a dense matrix, a scipy.sparse matrix
     (with sparseOptimization=True it reaches the library in compressed form, cogaps_session_create_sparse; otherwise densified), a
-    SparseMatrix or a CooMatrix (cogaps_session_create_coo)."""
+    SparseMatrix, a CooMatrix (cogaps_session_create_coo) or a DeviceMatrix (cogaps_session_create_from_device_matrix)."""
 
     def __init__(self, data, unc=None, lib=None, **kw):
         self.L = lib if lib is not None else load()
         self.p = make_params(self.L, **kw)
         self.sp = _sparse_input(data, unc, kw)
+        if isinstance(self.sp, DeviceMatrix):
+            self.d = self.u = None
+            self.h = self.L.cogaps_session_create_from_device_matrix(self.sp._handle(), C.byref(self.p))
+            if not self.h:
+                raise _error(self.L, "cogaps_session_create_from_device_matrix: ")
+            self.sp = None      # the session holds nothing of the handle
+            return
         if self.sp is not None:
             self.d = self.u = None
             m = self.sp.c_struct()
@@ -700,6 +779,10 @@ def run(data, unc=None, lib=None, **kw):
     p = make_params(L, **kw)
     r = CogapsResultC()
     sp = _sparse_input(data, unc, kw)
+    if isinstance(sp, DeviceMatrix):
+        if L.cogaps_run_device_matrix(sp._handle(), C.byref(p), C.byref(r)):
+            raise _error(L, "cogaps_run_device_matrix: ")
+        return result_to_dict(L, r)
     if sp is not None:
         m = sp.c_struct()
         name = "cogaps_run_coo" if isinstance(sp, CooMatrix) else "cogaps_run_sparse"

@@ -1,7 +1,8 @@
 """CoGAPS() -- the reference's user entry point (R/CoGAPS.R:90-155) over the HIP library.
 
 Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData), a scipy.sparse matrix
-(with sparseOptimization=True it is never densified) or a path to a .mtx/.csv/.tsv file (a .mtx file with sparseOptimization=True
+(with sparseOptimization=True it is never densified), a DeviceMatrix (a matrix uploaded to the GPU once: any number of runs, subsets
+and distributed shards are then taken from it on the device; sparseOptimization=True only) or a path to a .mtx/.csv/.tsv file (a .mtx file with sparseOptimization=True
 is read as triplets by the library and never densified either).  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
 `distributed` = "genome-wide" / "single-cell" dispatches to cogaps_amd.distributed (GWCoGAPS / scCoGAPS).
 """
@@ -26,10 +27,15 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
     if params.distributed is not None and nThreads > 1:
         warnings.warn("can't run multi-threaded and distributed CoGAPS at the same time, ignoring nThreads")
     # a scipy.sparse matrix: its stored entries (the rest are zeros); triplets read from a file: their values
-    values = data.values if isinstance(data, _capi.CooMatrix) else data.data if _capi.is_sparse(data) else data
-    if np.isnan(values).any():
+    if isinstance(data, _capi.DeviceMatrix):
+        # a device-resident matrix: what its host values showed when it was built (nothing is known of arrays that were on the device already)
+        has_na, has_negative = bool(data.has_na), bool(data.has_negative)
+    else:
+        values = data.values if isinstance(data, _capi.CooMatrix) else data.data if _capi.is_sparse(data) else data
+        has_na, has_negative = np.isnan(values).any(), (values < 0).any()
+    if has_na:
         raise ValueError("NA values in data")
-    if (values < 0).any() or (uncertainty is not None and (uncertainty < 0).any()):
+    if has_negative or (uncertainty is not None and (uncertainty < 0).any()):
         raise ValueError("negative values in data and/or uncertainty matrix")
     if data.shape[0] <= params.nPatterns or data.shape[1] <= params.nPatterns:
         raise ValueError("nPatterns must be less than dimensions of data")
@@ -67,7 +73,11 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
                 data = read_matrix(path)
     elif path is not None:
         data = read_matrix(path)
-    if isinstance(data, _capi.CooMatrix):
+    if isinstance(data, _capi.DeviceMatrix):
+        # uploaded and validated once by the caller; every run from it is a sparse-model session (the subset, if any, is taken on the device)
+        if not params.sparseOptimization:
+            raise ValueError("a DeviceMatrix needs sparseOptimization=True: the dense model takes a dense matrix")
+    elif isinstance(data, _capi.CooMatrix):
         pass
     elif _capi.is_sparse(data):
         # a scipy.sparse matrix reaches the sparse model in compressed form (never densified: cogaps_session_create_sparse); the dense

@@ -628,6 +628,122 @@ static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix 
     spb_models(s, side, hs, kept, (float *)(err + 1));
 }
 
+// A matrix resident on one device (cogaps_device_matrix): device copies of the caller's arrays, validated -- and, for triplets, resolved
+// for repeated positions into one keep bit per entry -- once, at its creation.  Immutable from then on: any number of sessions, on any
+// host threads, are built from it (build_samplers_device_matrix) and copy nothing of it but what their packed structures hold.
+struct cogaps_device_matrix {
+    int device = 0; uint32_t nrow = 0, ncol = 0; uint64_t nnz = 0; unsigned computeUnits = 0;
+    bool coo = false, majorIsRow = true;
+    uint64_t *indptr = nullptr; uint32_t *indices = nullptr;       // compressed: [nMajor + 1], [nnz]
+    uint32_t *rows = nullptr, *cols = nullptr;                     // triplets: [nnz]
+    unsigned long long *keep = nullptr;                            // triplets: bit k = entry k is the latest of its position and > 0
+    float *values = nullptr;
+    std::atomic<uint64_t> deviceBytes{0};
+    ~cogaps_device_matrix() { rt_free(indptr); rt_free(indices); rt_free(rows); rt_free(cols); rt_free(keep); rt_free(values); }
+};
+// one of the caller's arrays into the handle's own memory (count + 1 elements: never an empty allocation)
+template <class T> static T *dm_copy(const T *src, size_t count, bool onDevice, rt_stream_t stream)
+{
+    T *q = dalloc<T>(count + 1);
+    if (count) { if (onDevice) rt_d2d(q, src, count * sizeof(T), stream); else rt_h2d(q, src, count * sizeof(T), stream); }
+    return q;
+}
+static uint32_t entry_grid(uint64_t n, unsigned computeUnits, uint32_t bs)
+{
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + bs - 1) / bs, (uint64_t)computeUnits * 8u));
+}
+
+static void device_matrix_from_sparse(cogaps_device_matrix *dm, const cogaps_sparse_matrix &m, rt_stream_t stream)
+{
+    const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
+    uint64_t nnz = 0;
+    if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, stream); rt_sync(stream); } else nnz = m.indptr[nMajor];
+    if (nnz >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+    if (nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
+    dm->coo = false; dm->majorIsRow = m.majorIsRow != 0; dm->nnz = nnz;
+    dm->indptr = dm_copy(m.indptr, (size_t)nMajor + 1, m.onDevice != 0, stream);
+    dm->indices = dm_copy(m.indices, nnz, m.onDevice != 0, stream); dm->values = dm_copy(m.values, nnz, m.onDevice != 0, stream);
+    SpbTemps tmp; uint32_t *err = tmp.err();
+    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz; in.indptr = dm->indptr; in.indices = dm->indices; in.values = dm->values;
+    RT_LAUNCH(spb_validate_kernel, (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, in, err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
+    if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
+    if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
+    if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
+}
+
+// build_samplers_coo_input's passes 1 to 4 in the coordinates of the whole matrix, keeping the keep bits only: the present flags (laid out
+// [nrow][ncol / 64 + 1]) with their prefix counts and pointers and the winner indices are temporaries of this call
+static void device_matrix_from_coo(cogaps_device_matrix *dm, const cogaps_coo_matrix &m, rt_stream_t stream)
+{
+    const uint64_t nnz = m.nnz;
+    dm->coo = true; dm->majorIsRow = true; dm->nnz = nnz;
+    dm->rows = dm_copy(m.rows, nnz, m.onDevice != 0, stream); dm->cols = dm_copy(m.cols, nnz, m.onDevice != 0, stream);
+    dm->values = dm_copy(m.values, nnz, m.onDevice != 0, stream);
+    dm->keep = dalloc<unsigned long long>(nnz / 64 + 1);
+    SpbTemps tmp; uint32_t *err = tmp.err();
+    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz; in.rows = dm->rows; in.cols = dm->cols; in.values = dm->values;
+    SpbSide pres; pres.M = m.nrow; pres.Wn = m.ncol / 64u + 1u; pres.swap = 0u; pres.vals = nullptr;
+    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
+    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
+    const uint32_t grid = entry_grid(nnz, dm->computeUnits, COO_BS), vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
+    RT_LAUNCH(coo_present_kernel, grid, COO_BS, stream, in, pres, err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
+    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
+    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
+    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, pres.ptr, pres.M);
+    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
+    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, stream); rt_sync(stream);
+    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
+    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, stream, in, pres, winner);
+    RT_LAUNCH(coo_keep_bits_kernel, grid, COO_BS, stream, in, pres, (const uint32_t *)winner, dm->keep);
+    rt_sync(stream);
+}
+
+// Both samplers of a session from a device-resident matrix, with or without subsetData (sparse_build.h, the map and the mapped passes):
+// the session build_samplers_dense_input makes from the dense form of the handle's matrix.  One read of the handle's entries per mapped
+// pass; the session's allocations are those of any sparse-model session, the temporaries (the subset's indices, counts, cursors, list)
+// O(dim + n).  Nothing is uploaded but the subset's indices.
+static void build_samplers_device_matrix(cogaps_session *s, const cogaps_device_matrix &dm)
+{
+    const cogaps_params &p = s->p;
+    const bool subsetData = p.subsetData && !s->subset.empty();
+    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0);
+    const uint32_t nIdx = (uint32_t)s->subset.size();
+    const uint32_t nrow = subsetData && subsetRows ? nIdx : dm.nrow, ncol = subsetData && !subsetRows ? nIdx : dm.ncol;
+    SpbTemps tmp;
+    SpbSide side[2];
+    HostSampler *hs[2] = {&s->A, &s->P};
+    spb_sides(s, nrow, ncol, dm.majorIsRow, side, hs);
+    SpbMap mp; mp.start = mp.list = nullptr; mp.onMajor = subsetRows == dm.majorIsRow ? 1u : 0u;
+    if (subsetData) {
+        const uint32_t dim = subsetRows ? dm.nrow : dm.ncol;
+        const uint32_t *indices = tmp.stage(s->subset.data(), nIdx, false, s->stream);
+        uint32_t *start = tmp.alloc<uint32_t>((size_t)dim + 1), *cursor = tmp.alloc<uint32_t>(dim), *list = tmp.alloc<uint32_t>(nIdx);
+        const uint32_t mapGrid = entry_grid(nIdx, s->computeUnits, SPB_MAP_BS);
+        RT_LAUNCH(spb_map_count_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, start);
+        RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, start, dim);
+        RT_LAUNCH(spb_map_fill_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, (const uint32_t *)start, cursor, list);
+        mp.start = start; mp.list = list;
+    }
+    SpbIn in; CooIn cin;
+    const uint32_t nMajor = dm.majorIsRow ? dm.nrow : dm.ncol;
+    in.nMajor = nMajor; in.nMinor = dm.majorIsRow ? dm.ncol : dm.nrow; in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
+    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
+    const uint32_t sliceGrid = (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, s->computeUnits, COO_BS);
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, s->stream, cin, (const unsigned long long *)dm.keep, mp, side[0], side[1]);
+    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
+    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    // an entry has as many images as its index repeats in the subset: the total in 64 bits before the 32-bit scan
+    std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, s->stream); rt_sync(s->stream);
+    uint64_t total = 0; for (uint32_t c : counts) total += c;
+    if (total >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, s->stream, cin, (const unsigned long long *)dm.keep, mp, side[0], side[1]);
+    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
+    spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
+}
+
 static void read_gs(cogaps_session *s, HostSampler &h)
 {
     rt_d2h(s->hGs, h.d.gs, sizeof(GenScalars), s->stream);
@@ -1118,10 +1234,10 @@ int cogaps_compiled_with_openmp(void) { return 0; }
 
 } // extern "C"
 
-// cogaps_session_create (sp == coo == nullptr: the dense matrix `data`), cogaps_session_create_sparse (sp: the compressed one) and
-// cogaps_session_create_coo (coo: unordered triplets)
+// cogaps_session_create (sp == coo == dm == nullptr: the dense matrix `data`), cogaps_session_create_sparse (sp: the compressed one),
+// cogaps_session_create_coo (coo: unordered triplets) and cogaps_session_create_from_device_matrix (dm: a device-resident matrix)
 static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, int data_on_device,
-                                      const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo = nullptr)
+                                      const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo = nullptr, const cogaps_device_matrix *dm = nullptr)
 {
     cogaps_session *s = nullptr;
     try {
@@ -1140,6 +1256,10 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
             if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a triplet matrix"); return nullptr; }
             if (coo->nnz >= 0xFFFFFFFFull) { fail("triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)"); return nullptr; }
             if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) { fail("null argument: rows / cols / values"); return nullptr; }
+        } else if (dm) {
+            nrow = dm->nrow; ncol = dm->ncol;
+            if (!p.useSparseOptimization) { fail("a device-resident matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
+            if (p.device != dm->device) { fail("params->device must be -1 or the device the matrix resides on (" + std::to_string(dm->device) + ")"); return nullptr; }
         } else if (!data) { fail("null argument: data"); return nullptr; }
         // The reference's distributed caller forces asynchronousUpdates = FALSE on its workers (R/DistributedCogaps.R:28-29) -- there to keep
         // BiocParallel workers single-threaded, not for the sampler's sake.  Documented deviation: a
@@ -1191,6 +1311,7 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
         if (sp) build_samplers_sparse_input(s, *sp);
         else if (coo) build_samplers_coo_input(s, *coo);
+        else if (dm) build_samplers_device_matrix(s, *dm);
         else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
         else {
             build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
@@ -1270,6 +1391,71 @@ cogaps_session *cogaps_session_create_coo(const cogaps_coo_matrix *m, const coga
 {
     if (!m) { fail("null argument"); return nullptr; }
     return session_create(nullptr, 0, 0, params, nullptr, 0, nullptr, m);
+}
+
+static cogaps_device_matrix *device_matrix_create(const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo, int device)
+{
+    cogaps_device_matrix *dm = nullptr;
+    rt_stream_t stream; bool haveStream = false;
+    try {
+        if (sp) {
+            if (!sp->indptr) { fail("null argument: indptr"); return nullptr; }
+        } else {
+            if (coo->nnz >= 0xFFFFFFFFull) { fail("triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)"); return nullptr; }
+            if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) { fail("null argument: rows / cols / values"); return nullptr; }
+        }
+        if ((sp ? sp->nrow : coo->nrow) == 0 || (sp ? sp->ncol : coo->ncol) == 0) { fail("empty problem"); return nullptr; }
+        rt_set_device(device);
+        dm = new cogaps_device_matrix();
+        dm->device = rt_get_device(); dm->computeUnits = rt_compute_units();
+        dm->nrow = sp ? sp->nrow : coo->nrow; dm->ncol = sp ? sp->ncol : coo->ncol;
+        stream = rt_stream_create(); haveStream = true;
+        {
+            rt_alloc_scope allocOn(stream); rt_owner_scope owner(&dm->deviceBytes);
+            if (sp) device_matrix_from_sparse(dm, *sp, stream); else device_matrix_from_coo(dm, *coo, stream);
+            rt_sync(stream);
+        }
+        rt_stream_destroy(stream);
+        return dm;
+    } catch (const std::exception &e) {
+        fail_exc(e);
+        if (haveStream) rt_stream_destroy(stream);
+        delete dm;
+        return nullptr;
+    }
+}
+cogaps_device_matrix *cogaps_device_matrix_create_sparse(const cogaps_sparse_matrix *m, int device)
+{
+    if (!m) { fail("null argument"); return nullptr; }
+    return device_matrix_create(m, nullptr, device);
+}
+cogaps_device_matrix *cogaps_device_matrix_create_coo(const cogaps_coo_matrix *m, int device)
+{
+    if (!m) { fail("null argument"); return nullptr; }
+    return device_matrix_create(nullptr, m, device);
+}
+void cogaps_device_matrix_destroy(cogaps_device_matrix *m)
+{
+    if (!m) return;
+    try { rt_set_device(m->device); } catch (const std::exception &) { }
+    delete m;
+}
+int cogaps_device_matrix_info(const cogaps_device_matrix *m, uint32_t *nrow, uint32_t *ncol, uint64_t *storedEntries, uint64_t *deviceBytes, int *device)
+{
+    if (!m) return fail("null argument");
+    if (nrow) *nrow = m->nrow;
+    if (ncol) *ncol = m->ncol;
+    if (storedEntries) *storedEntries = m->nnz;
+    if (deviceBytes) *deviceBytes = m->deviceBytes.load();
+    if (device) *device = m->device;
+    return 0;
+}
+cogaps_session *cogaps_session_create_from_device_matrix(const cogaps_device_matrix *m, const cogaps_params *params)
+{
+    if (!m || !params) { fail("null argument"); return nullptr; }
+    cogaps_params p = *params;
+    if (p.device == -1) p.device = m->device;
+    return session_create(nullptr, 0, 0, &p, nullptr, 0, nullptr, nullptr, m);
 }
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes)
 {
@@ -2057,6 +2243,18 @@ int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, coga
 {
     if (!out) return fail("null argument");
     cogaps_session *s = cogaps_session_create_coo(m, params);
+    if (!s) return 1;
+    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_finish(s, out);
+    cogaps_session_destroy(s);
+    return rc;
+}
+
+int cogaps_run_device_matrix(const cogaps_device_matrix *m, const cogaps_params *params, cogaps_result *out)
+{
+    if (!out) return fail("null argument");
+    cogaps_session *s = cogaps_session_create_from_device_matrix(m, params);
     if (!s) return 1;
     int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
     if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);

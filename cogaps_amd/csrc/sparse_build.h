@@ -11,7 +11,8 @@
 //   2. spb_scan_kernel: dptr = exclusive scan of the counts; spb_prefix_kernel: dprefix = popcount scan over each vector's flag words
 //   3. spb_scatter_kernel: every kept entry computes its own slot dptr[j] + dprefix[j][i >> 6] + popcount(flags below bit i)
 // and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order -- gaps::nonZeroMean's sum over
-// the dense elements in (j, i) order (zeros add nothing), which feeds lambda.
+// the dense elements in (j, i) order (zeros add nothing), which feeds lambda.  A device-resident matrix (cogaps_device_matrix: further down)
+// goes through passes of the same shape that place every entry through a map of the subset axis.
 #pragma once
 #include "gaps_state.h"
 #include "eval_kernel.h"
@@ -222,6 +223,112 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_scatter_kernel(CooIn in, SpbSide a, 
         if (!((keep[k >> 6] >> (k & 63u)) & 1ull)) continue;
         const uint32_t r = in.rows[k], c = in.cols[k]; const float v = in.values[k];
         spb_store(a, r, c, v); spb_store(b, r, c, v);
+    }
+}
+
+// ---- a device-resident matrix (cogaps_device_matrix) and a subset of its rows or columns ----
+// The handle keeps the caller's arrays as they came: validated once at its creation (spb_validate_kernel: the checks of
+// spb_validate_count_kernel and nothing else; triplets: the present / winner passes above, then coo_keep_bits_kernel).  A session made
+// from it visits every stored entry of the handle once (triplets: every kept entry) and places it through a MAP of the subset axis:
+// subsetData names n 1-based indices of that axis (dimension dim), output row / column i is input indices[i] - 1 (Matrix.cpp:30-69: in
+// the order given, an index may repeat), so input index c has the IMAGES { i : indices[i] - 1 == c } -- none when c is not in the subset.
+//   1. spb_map_count_kernel: cnt[c] = number of images of c (32-bit atomic add); spb_scan_kernel: start = exclusive scan, start[dim] = n
+//   2. spb_map_fill_kernel: list[start[c] + q] = i, q from a per-index cursor (32-bit atomic add)
+//   3. spb_mapped_kernel<false> / coo_mapped_kernel<false>: every entry ORs its bit into both samplers' flag words once per image
+//   4. spb_count_kernel (popcount: an entry may have several images), spb_scan_kernel, spb_prefix_kernel per sampler
+//   5. spb_mapped_kernel<true> / coo_mapped_kernel<true>: every entry stores its value at spb_slot of each image
+// The order of a list (which image of c got which q) depends on how the device schedules pass 2.  No bit of the session depends on it:
+// the passes that read a list treat it as a SET -- pass 3 ORs one bit per image (commutative, idempotent), pass 5 stores the same value
+// at the slot of each image, and the images of distinct stored positions are distinct positions of the subset, so no slot has two
+// writers.  Without a subset the map is the identity (SpbMap::start == nullptr): the entry is its own only image.  The temporaries are
+// the indices, cnt / start [dim + 1], the cursors [dim] and the list [n]: O(dim + n); the other axis is not mapped at all.
+struct SpbMap {
+    const uint32_t *start, *list;      // images of index c of the subset axis: list[start[c] .. start[c + 1]); start == nullptr: the identity
+    uint32_t onMajor;                  // the subset axis is the entries' major axis (their minor axis otherwise)
+};
+#define SPB_MAP_BS 256
+
+// cnt[indices[i] - 1] += 1 (the host has checked 1 <= indices[i] <= dim)
+CG_KERNEL void CG_LAUNCH_BOUNDS(SPB_MAP_BS) spb_map_count_kernel(const uint32_t *indices, uint32_t n, uint32_t *cnt)
+{
+    for (uint32_t i = cg_bid() * (uint32_t)SPB_MAP_BS + cg_tid(); i < n; i += cg_gdim() * (uint32_t)SPB_MAP_BS) cg_atomic_add_u32(cnt + (indices[i] - 1u), 1u);
+}
+// list[start[c] + (the next free place of c)] = i: each output position once, inside its input index's run of the list
+CG_KERNEL void CG_LAUNCH_BOUNDS(SPB_MAP_BS) spb_map_fill_kernel(const uint32_t *indices, uint32_t n, const uint32_t *start, uint32_t *cursor, uint32_t *list)
+{
+    for (uint32_t i = cg_bid() * (uint32_t)SPB_MAP_BS + cg_tid(); i < n; i += cg_gdim() * (uint32_t)SPB_MAP_BS) {
+        const uint32_t c = indices[i] - 1u;
+        list[start[c] + cg_atomic_add_u32(cursor + c, 1u)] = i;
+    }
+}
+
+// One stored entry > 0 at (major, minor) of the handle's matrix, once per image under the map: its flag bit in both samplers (STORE =
+// false) or its value at its slot in both (STORE = true).  Shared by the compressed and the triplet form.
+template <bool STORE>
+CG_DEVICE void spb_mapped_entry(const SpbMap &mp, const SpbSide &a, const SpbSide &b, uint32_t major, uint32_t minor, float v)
+{
+    const bool mapped = mp.start != nullptr;
+    const uint32_t c = mp.onMajor ? major : minor;
+    const uint32_t lo = mapped ? mp.start[c] : 0u, hi = mapped ? mp.start[c + 1u] : 1u;
+    for (uint32_t q = lo; q < hi; ++q) {
+        const uint32_t img = mapped ? mp.list[q] : c;
+        const uint32_t mj = mp.onMajor ? img : major, mn = mp.onMajor ? minor : img;
+        if (STORE) { spb_store(a, mj, mn, v); spb_store(b, mj, mn, v); }
+        else {
+            uint32_t vec, el;
+            spb_place(a, mj, mn, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
+            spb_place(b, mj, mn, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
+        }
+    }
+}
+
+// The checks of spb_validate_count_kernel on their own (a handle's creation builds nothing): one wave per major slice.  Nothing is read
+// outside [0, nnz) whatever the input holds, nothing written but *err.
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_validate_kernel(SpbIn in, uint32_t *err)
+{
+    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    uint64_t lo, hi; spb_slice(in, m, lo, hi);
+    if (m == 0u && m < in.nMajor && lo != 0ull) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); }
+    if (lo > hi || hi > in.nnz) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); hi = lo = 0; }
+    for (uint64_t k = lo + lane; k < hi; k += 64u) {
+        const uint32_t idx = in.indices[k];
+        if (idx >= in.nMinor) { cg_atomic_max_u32(err, SPB_ERR_RANGE); continue; }
+        if (k > lo && in.indices[k - 1] >= idx) cg_atomic_max_u32(err, SPB_ERR_ORDER);
+    }
+}
+// A validated compressed matrix through the map: one wave per major slice.  A slice whose major index has no image is left unread.
+template <bool STORE>
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_mapped_kernel(SpbIn in, SpbMap mp, SpbSide a, SpbSide b)
+{
+    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
+    uint64_t lo, hi; spb_slice(in, m, lo, hi);
+    if (m < in.nMajor && mp.start != nullptr && mp.onMajor && mp.start[m] == mp.start[m + 1u]) return;
+    for (uint64_t k = lo + lane; k < hi; k += 64u) {
+        const float v = in.values[k];
+        if (!(v > 0.f)) continue;                                             // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
+        spb_mapped_entry<STORE>(mp, a, b, m, in.indices[k], v);
+    }
+}
+
+// coo_keep_kernel's keep bits on their own (a handle's creation sets no sampler's flags): entry k is kept when it is the latest of its
+// position and its value is > 0.  A wave takes 64 consecutive entries from a multiple of 64 on, so a keep word has one writer.
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_keep_bits_kernel(CooIn in, SpbSide t, const uint32_t *winner, unsigned long long *keep)
+{
+    const uint32_t lane = cg_tid() & 63u;
+    for (uint64_t base = (uint64_t)cg_bid() * COO_BS + (cg_tid() - lane); base < in.nnz; base += (uint64_t)cg_gdim() * COO_BS) {
+        const uint64_t k = base + lane;
+        const bool kept = k < in.nnz && in.values[k] > 0.f && winner[spb_slot(t, in.rows[k], in.cols[k])] == (uint32_t)k;
+        const unsigned long long mask = cg_ballot(kept);
+        if (lane == 0u) keep[base >> 6] = mask;
+    }
+}
+// The kept triplets through the map (rows are the major axis): grid-stride over the entries
+template <bool STORE>
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_mapped_kernel(CooIn in, const unsigned long long *keep, SpbMap mp, SpbSide a, SpbSide b)
+{
+    for (uint64_t k = (uint64_t)cg_bid() * COO_BS + cg_tid(); k < in.nnz; k += (uint64_t)cg_gdim() * COO_BS) {
+        if (!((keep[k >> 6] >> (k & 63u)) & 1ull)) continue;
+        spb_mapped_entry<STORE>(mp, a, b, in.rows[k], in.cols[k], in.values[k]);
     }
 }
 

@@ -363,17 +363,22 @@ class _Source:
         the indices first: the sets are sorted to match;
       * a callable loader(i, indices) -> matrix or (matrix, uncertainty): shard i's own contiguous sub-matrix for the 1-based
         `indices` (rows of the data when the partitioned dimension is the rows, else columns), with `shape` = dimensions of the whole.
-    No rank ever materialises the whole matrix unless the caller hands it over as an array."""
+      * a DeviceMatrix (the caller's choice: the WHOLE matrix is resident on this rank's GPU): every shard's session is created from it
+        with subsetIndices = sets[i] and the subset is taken on the device (cogaps_session_create_from_device_matrix), in the order given
+        like the array's; nothing is cut or uploaded per shard.
+    No rank ever materialises the whole matrix unless the caller hands it over as an array or a DeviceMatrix."""
 
     def __init__(self, data, uncertainty, shape, subset_rows, sparse_model=False):
         self.data, self.unc, self.subset_rows = data, uncertainty, subset_rows
-        self.kind = "path" if isinstance(data, (str, bytes)) else ("loader" if callable(data) else "array")
+        self.kind = "device" if isinstance(data, _capi.DeviceMatrix) else "path" if isinstance(data, (str, bytes)) else ("loader" if callable(data) else "array")
         self.sparse = self.kind == "array" and _capi.is_sparse(data)
         self.sparse_model = bool(sparse_model)
         if self.sparse:
             self.data = data.tocsr() if subset_rows else data.tocsc()      # the form whose major slices the shards are
-        if self.kind == "array":
+        if self.kind in ("array", "device"):
             self.shape = tuple(data.shape)
+            if self.kind == "device" and (uncertainty is not None or not sparse_model):
+                raise ValueError("a DeviceMatrix takes no uncertainty matrix and needs sparseOptimization=True")
         elif self.kind == "path":
             nr, nc, self.row_names, self.col_names = _capi.file_info(data)
             self.shape = (nr, nc)
@@ -394,6 +399,8 @@ class _Source:
         return int(np.diff(self.data.indptr)[np.asarray(idx1, dtype=np.int64) - 1].sum())
 
     def shard(self, i, idx1):
+        if self.kind == "device":
+            return self.data, None      # the shard's session takes its rows / columns from the handle itself (subsetIndices)
         if self.sparse:
             idx = np.asarray(idx1, dtype=np.int64) - 1
             m = self.data[idx, :] if self.subset_rows else self.data[:, idx]
@@ -438,6 +445,8 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         # The HIP current device belongs to the calling host thread; the shards in flight run on pool threads that start on
         # device 0.  Resolve the ordinal once, here, and hand it to every shard explicitly.
         device = _current_device(run_fn)
+    if src.kind == "device" and run_fn is _capi.run and data.device != device:
+        raise ValueError("the DeviceMatrix resides on device %d, the run uses device %d" % (data.device, device))
     if comm_device is None:
         comm_device = "cpu"
         if dist is not None and dist.get_backend() == "nccl":
@@ -456,6 +465,10 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         return g_, s_, bool(params.sparseOptimization), src.has_unc()
     if src.sparse and src.sparse_model:
         shape_of.nnz = lambda i: src.shard_nnz(sets[i])
+    elif src.kind == "device":
+        shape_of.nnz = lambda i: data.nnz * len(sets[i]) // total      # (the handle's stored entries, spread evenly over the partitioned axis)
+    # a DeviceMatrix hands every worker the whole matrix and its subsetIndices, as the reference does (R/DistributedCogaps.R:12-35)
+    subset_kw = (lambda i: dict(subsetIndices=sets[i], subsetDim=1 if genome_wide else 2)) if src.kind == "device" else (lambda i: {})
 
     def make_spec(n_patterns, fixed=None, which="N"):          # callInternalCoGAPS, DistributedCogaps.R:12-35
         def spec(i):
@@ -463,7 +476,7 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
             # shard's turn comes: the library then holds and uploads one shard, never the whole matrix
             d, u = src.shard(i, sets[i])
             return d, u, dict(nPatterns=n_patterns, runningDistributed=True, workerID=i + 1, messages=messages, whichMatrixFixed=which,
-                              fixedPatterns=fixed, **common)
+                              fixedPatterns=fixed, **subset_kw(i), **common)
         spec.device = device
         return spec
 

@@ -252,6 +252,42 @@ typedef struct cogaps_coo_matrix {
 } cogaps_coo_matrix;
 cogaps_session *cogaps_session_create_coo(const cogaps_coo_matrix *m, const cogaps_params *params);
 int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, cogaps_result *out);
+/* A matrix resident on one GPU: uploaded, validated and -- for triplets -- resolved for repeated positions ONCE, then the source of any
+ * number of sparse-model sessions (a K sweep, replicate seeds, both passes of every shard of a distributed run), each with its own
+ * nPatterns, seed, fixed matrix, transposeData and subsetData.  `device` = -1: the calling thread's current device.
+ *
+ * The handle holds device copies of the input arrays (with onDevice = 1: a device-to-device copy) -- for triplets also one keep bit per
+ * entry (the latest entry > 0 of its position) -- and nothing else; the caller's arrays are not referenced after the call, which
+ * synchronises before it returns.  The handle never changes afterwards: sessions may be created from it by several host threads at once.
+ * A session copies nothing from it but what its own packed structures hold, so the handle may be destroyed while sessions made from it
+ * live on.  Its bytes are reported by cogaps_device_matrix_info and never appear in a session's cogaps_session_device_bytes.
+ * Errors of the creating calls (NULL, cogaps_last_error) are those of cogaps_session_create_sparse / _coo for the same arrays, with the
+ * same texts, checked on the device over the whole input before anything is kept: indptr that does not start at 0, decreases or does not
+ * end at the number of stored entries; an index >= the minor dimension; indices not strictly ascending; a triplet index outside the
+ * dimensions; 2^32 - 1 entries or more; NULL arrays.
+ *
+ * cogaps_session_create_from_device_matrix: THE SESSION IS, BIT FOR BIT, THE SESSION cogaps_session_create MAKES FROM THE DENSE FORM OF
+ * THE HANDLE'S MATRIX WITH THE SAME cogaps_params (flag words, prefix counts, pointers, packed values, lambda, maxGibbsMass, meanChiSq,
+ * every proposal, cogaps_session_device_bytes) -- without subsetData therefore also the session cogaps_session_create_sparse / _coo makes.
+ * Everything in cogaps_params is honoured, unlike those two entries including
+ *   - subsetData / subsetGenes (with transposeData) by the dense entry's rule (Matrix.cpp:30-69): the 1-based dataIndicesSubset name rows
+ *     or columns of the genes / samples axis IN THE ORDER GIVEN; output row / column i is input dataIndicesSubset[i] - 1; AN INDEX MAY
+ *     REPEAT, and the row / column then appears that often.  The subset is taken on the device (csrc/sparse_build.h, the map): the build
+ *     reads the whole handle once, O(stored entries), uploads nothing but the indices, and allocates nothing of the size of the whole
+ *     matrix -- its temporaries are O(dimension of the subset axis + nSubset);
+ *   - reductionMode COGAPS_REDUCE_SEQ with any mathMode (the verification mode).
+ * Errors (NULL, cogaps_last_error): useSparseOptimization = 0 (the dense model takes a dense matrix); params->device other than -1 or the
+ * handle's device; an index of dataIndicesSubset outside 1 .. dimension or an empty subset (the dense entry's messages); a subset whose
+ * repeated indices bring it to 2^32 - 1 kept entries or more. */
+typedef struct cogaps_device_matrix cogaps_device_matrix;
+cogaps_device_matrix *cogaps_device_matrix_create_sparse(const cogaps_sparse_matrix *m, int device);   /* CSR / CSC, host or device pointers */
+cogaps_device_matrix *cogaps_device_matrix_create_coo(const cogaps_coo_matrix *m, int device);         /* triplets, the latest entry decides */
+void cogaps_device_matrix_destroy(cogaps_device_matrix *m);
+/* dimensions, stored entries (triplets: all of them, overwritten ones included), bytes of device memory held, device; any pointer may be NULL */
+int  cogaps_device_matrix_info(const cogaps_device_matrix *m, uint32_t *nrow, uint32_t *ncol, uint64_t *storedEntries,
+                               uint64_t *deviceBytes, int *device);
+cogaps_session *cogaps_session_create_from_device_matrix(const cogaps_device_matrix *m, const cogaps_params *params);
+int cogaps_run_device_matrix(const cogaps_device_matrix *m, const cogaps_params *params, cogaps_result *out);
 /* Bytes of device memory the session holds: the sum of its own allocations (as requested), counted as they are made and released -- not
  * hipMemGetInfo, which is device-wide.  For every session, however it was created. */
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes);
