@@ -61,7 +61,8 @@ typedef struct cogaps_params {
     int32_t subsetGenes;         /* subsetDim == 1 (rows of A) else samples */
     const uint32_t *dataIndicesSubset; /* 1-based indices, as R passes them (Matrix.cpp:55-62) */
     uint32_t nSubset;
-    int32_t useSparseOptimization; /* SparseNormalModel (default uncertainty only) instead of DenseNormalModel */
+    int32_t useSparseOptimization; /* SparseNormalModel (default uncertainty only) instead of DenseNormalModel.  The sparse model takes at
+                                      most 512 patterns: a larger nPatterns is refused at session creation, whatever the input form */
     int32_t takePumpSamples;       /* GapsStatistics::updatePump per sampling iteration (GapsRunner.cpp:310-313) */
     int32_t asynchronousUpdates;   /* must be 1: this library IS the asynchronous sampler.  One exception: 0 is accepted, and ignored, when
                                       runningDistributed is set -- R's distributed caller forces FALSE on its workers (R/DistributedCogaps.R:28-29) */
