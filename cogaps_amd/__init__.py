@@ -1,12 +1,13 @@
 """cogaps_amd -- the CoGAPS asynchronous Gibbs sampler hot path on MI355X (HIP, gfx950).
 
 Public surface mirrors the reference's: CoGAPS(), GWCoGAPS(), scCoGAPS(), CogapsParams, CogapsResult,
-DeviceMatrix (a sparse matrix uploaded to the GPU once, the source of any number of runs and subsets), buildReport(), checkpointsEnabled(), compiledWithOpenMPSupport().  All compute goes through
+DeviceMatrix (a sparse matrix uploaded to the GPU once, the source of any number of runs and subsets), DeviceDense (a dense matrix that
+already resides on the GPU, by address; a torch tensor on the GPU is taken as one by every entry point), buildReport(), checkpointsEnabled(), compiledWithOpenMPSupport().  All compute goes through
 csrc/libcogaps_hip.so (include/cogaps_hip.h); importing works without a GPU, running does not."""
 from .params import CogapsParams
 from .result import CogapsResult
 from .api import CoGAPS, GWCoGAPS, scCoGAPS
-from ._capi import DeviceMatrix
+from ._capi import DeviceMatrix, DeviceDense
 
 
 def buildReport():
@@ -23,5 +24,5 @@ def compiledWithOpenMPSupport():
     return bool(_capi.load().cogaps_compiled_with_openmp())
 
 
-__all__ = ["CoGAPS", "GWCoGAPS", "scCoGAPS", "CogapsParams", "CogapsResult", "DeviceMatrix", "buildReport", "checkpointsEnabled",
+__all__ = ["CoGAPS", "GWCoGAPS", "scCoGAPS", "CogapsParams", "CogapsResult", "DeviceMatrix", "DeviceDense", "buildReport", "checkpointsEnabled",
            "compiledWithOpenMPSupport"]

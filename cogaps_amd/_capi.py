@@ -96,6 +96,7 @@ EXPORTS = [
     "cogaps_session_create_coo", "cogaps_run_coo", "cogaps_read_mtx_triplets", "cogaps_triplets_free",
     "cogaps_device_matrix_create_sparse", "cogaps_device_matrix_create_coo", "cogaps_device_matrix_destroy", "cogaps_device_matrix_info",
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
+    "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -133,6 +134,9 @@ def bind(L):
     L.cogaps_default_params.argtypes = [C.POINTER(CogapsParamsC)]
     L.cogaps_default_params.restype = None
     L.cogaps_run.argtypes = [fp, C.c_uint32, C.c_uint32, C.POINTER(CogapsParamsC), fp, C.POINTER(CogapsResultC)]
+    if hasattr(L, "cogaps_run_device"):      # (an A/B build of an older source tree lacks the two: tools/measure_dense_device_session_create.py)
+        L.cogaps_run_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(CogapsParamsC), vp, C.POINTER(CogapsResultC)]
+        L.cogaps_session_debug_dense_data.argtypes = [vp, C.c_char, vp, vp, vp, fp, fp, fp, C.POINTER(C.c_int)]
     L.cogaps_result_free.argtypes = [C.POINTER(CogapsResultC)]
     L.cogaps_result_free.restype = None
     L.cogaps_last_error.restype = C.c_char_p
@@ -463,6 +467,58 @@ class DeviceMatrix:
             pass
 
 
+class DeviceDense:
+    """A dense matrix resident on one GPU as cogaps_session_create takes it with data_on_device = 1 (include/cogaps_hip.h): `data_addr`
+    -- and `unc_addr`, unless None -- are the addresses of row-major fp32 arrays of `shape` in the memory of the run's device (e.g.
+    torch's data_ptr()), in the manner of SparseMatrix(..., on_device=True).  Session / run / run_batch build from them on the device,
+    for both models; nothing of the matrix goes through the host.  The arrays must be complete before the call and stay alive until it
+    returns (`keep`: objects that own them, held as long as this object lives).  A torch tensor given to Session / run / run_batch /
+    CoGAPS becomes one of these by itself (device_input)."""
+
+    def __init__(self, shape, data_addr, unc_addr=None, keep=None):
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.data_addr, self.unc_addr, self.keep = int(data_addr), (None if unc_addr is None else int(unc_addr)), keep
+
+
+def is_tensor(x):
+    """whether x is a torch tensor, without importing torch: by the module of its type (a process that holds a tensor has torch loaded)"""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def on_gpu(x):
+    return is_tensor(x) and x.is_cuda
+
+
+def device_input(data, unc, kw):
+    """Torch tensors among (data, unc) resolved: -> (data, unc, kw) for the dense entry.  A CPU tensor is its numpy view.  A GPU tensor
+    becomes a DeviceDense of contiguous fp32 copies made on its device (none where it is contiguous fp32 already); the uncertainty
+    follows the data to the device, or to the host.  kw's device = -1 resolves to the tensor's device, any other device is a
+    ValueError; the tensor's current stream is synchronised, so that the library -- which reads on a stream of its own -- finds the
+    arrays complete."""
+    if isinstance(data, DeviceDense) and unc is not None:
+        raise ValueError("a DeviceDense carries its uncertainty itself (unc_addr)")
+    if not (is_tensor(data) or is_tensor(unc)):
+        return data, unc, kw
+    if not on_gpu(data):
+        cpu = lambda t: t.detach().cpu().numpy() if is_tensor(t) else t
+        return cpu(data), cpu(unc), kw
+    import torch      # (loaded already: the caller holds a tensor.  load() imports it first in any case: one HIP runtime per process)
+    dev = data.device.index if data.device.index is not None else torch.cuda.current_device()
+    want = int(kw.get("device", -1))
+    if want not in (-1, dev):
+        raise ValueError("the data tensor resides on device %d, the run was given device=%d" % (dev, want))
+    if data.dim() != 2:
+        raise ValueError("data must be a 2-D tensor")
+    d = data.detach().to(dtype=torch.float32).contiguous()
+    u = None
+    if unc is not None:
+        u = (unc.detach() if is_tensor(unc) else torch.from_numpy(np.ascontiguousarray(unc))).to(device=data.device, dtype=torch.float32).contiguous()
+        if tuple(u.shape) != tuple(d.shape):
+            raise ValueError("the uncertainty matrix must have the shape of the data")
+    torch.cuda.current_stream(data.device).synchronize()
+    return DeviceDense(d.shape, d.data_ptr(), None if u is None else u.data_ptr(), keep=(d, u)), None, dict(kw, device=dev)
+
+
 def _sparse_input(data, unc, kw):
     """the SparseMatrix / CooMatrix / DeviceMatrix to hand to the library's compressed-sparse / triplet / device-matrix entry, or None
     for the dense entry.  A scipy.sparse matrix goes in compressed form when the run uses the sparse model; the dense model takes it
@@ -483,13 +539,22 @@ def _dense(a):
 
 
 class Session:
-    """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h).  `data`: a dense matrix, a scipy.sparse matrix
+    """One sampler run, one step at a time (cogaps_session_* of include/cogaps_hip.h).  `data`: a dense matrix (a numpy array, a torch
+    tensor -- on the GPU it is consumed there -- or a DeviceDense of raw device addresses, with `unc` alike), a scipy.sparse matrix
     (with sparseOptimization=True it reaches the library in compressed form, cogaps_session_create_sparse; otherwise densified), a
     SparseMatrix, a CooMatrix (cogaps_session_create_coo) or a DeviceMatrix (cogaps_session_create_from_device_matrix)."""
 
     def __init__(self, data, unc=None, lib=None, **kw):
         self.L = lib if lib is not None else load()
+        data, unc, kw = device_input(data, unc, kw)
         self.p = make_params(self.L, **kw)
+        if isinstance(data, DeviceDense):
+            # device pointers: built on the device (csrc/dense_build.h); the call synchronises, the arrays are not referenced afterwards
+            self.sp = self.d = self.u = None
+            self.h = self.L.cogaps_session_create(data.data_addr, data.shape[0], data.shape[1], C.byref(self.p), data.unc_addr, 1)
+            if not self.h:
+                raise _error(self.L, "cogaps_session_create: ")
+            return
         self.sp = _sparse_input(data, unc, kw)
         if isinstance(self.sp, DeviceMatrix):
             self.d = self.u = None
@@ -525,6 +590,17 @@ class Session:
         v = C.c_float(0)
         self._ck(self.L.cogaps_session_sparse_build_ms(self.h, C.byref(v)))
         return float(v.value)
+
+    def debug_dense_data(self, which):
+        """the dense model's data of sampler `which` as the device holds it: D, Sraw, S2 [M][Npad] with their pads (S2: None when the
+        session keeps none), lambda, maxGibbsMass, sparsity"""
+        m, n, _ = self.dims(which)
+        shape = (m, (n + 3) & ~3)
+        D, SR, S2 = (np.full(shape, np.nan, dtype=np.float32) for _ in range(3))
+        lam, mg, spa, has = C.c_float(), C.c_float(), C.c_float(), C.c_int()
+        self._ck(self.L.cogaps_session_debug_dense_data(self.h, which.encode(), D.ctypes.data, SR.ctypes.data, S2.ctypes.data,
+                                                        C.byref(lam), C.byref(mg), C.byref(spa), C.byref(has)))
+        return {"D": D, "Sraw": SR, "S2": S2 if has.value else None, "lambda": lam.value, "maxGibbsMass": mg.value, "sparsity": spa.value}
 
     def debug_sparse_data(self, which):
         """the sparse model's data structures of sampler `which`: flags / prefix [M][Wn], ptr [M + 1], vals, lambda, maxGibbsMass"""
@@ -776,8 +852,13 @@ def run_from_file(path, unc_path=None, lib=None, **kw):
 def run(data, unc=None, lib=None, **kw):
     """cogaps_run: one full equilibration + sampling run."""
     L = lib if lib is not None else load()
+    data, unc, kw = device_input(data, unc, kw)
     p = make_params(L, **kw)
     r = CogapsResultC()
+    if isinstance(data, DeviceDense):
+        if L.cogaps_run_device(data.data_addr, data.shape[0], data.shape[1], C.byref(p), data.unc_addr, C.byref(r)):
+            raise _error(L, "cogaps_run_device: ")
+        return result_to_dict(L, r)
     sp = _sparse_input(data, unc, kw)
     if isinstance(sp, DeviceMatrix):
         if L.cogaps_run_device_matrix(sp._handle(), C.byref(p), C.byref(r)):

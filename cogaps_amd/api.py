@@ -1,6 +1,7 @@
 """CoGAPS() -- the reference's user entry point (R/CoGAPS.R:90-155) over the HIP library.
 
-Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData), a scipy.sparse matrix
+Same arguments and defaults; `data` is a 2-D array (genes x samples unless transposeData; a numpy array or a torch tensor -- a tensor
+on the GPU is checked and consumed there, with its uncertainty, and never copied to the host; results stay numpy), a scipy.sparse matrix
 (with sparseOptimization=True it is never densified), a DeviceMatrix (a matrix uploaded to the GPU once: any number of runs, subsets
 and distributed shards are then taken from it on the device; sparseOptimization=True only) or a path to a .mtx/.csv/.tsv file (a .mtx file with sparseOptimization=True
 is read as triplets by the library and never densified either).  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
@@ -32,14 +33,16 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
         has_na, has_negative = bool(data.has_na), bool(data.has_negative)
     else:
         values = data.values if isinstance(data, _capi.CooMatrix) else data.data if _capi.is_sparse(data) else data
-        has_na, has_negative = np.isnan(values).any(), (values < 0).any()
+        # (a tensor on the GPU: torch evaluates the same tests there, one flag each comes to the host)
+        has_na = bool(values.isnan().any()) if _capi.is_tensor(values) else np.isnan(values).any()
+        has_negative = bool((values < 0).any())
     if has_na:
         raise ValueError("NA values in data")
-    if has_negative or (uncertainty is not None and (uncertainty < 0).any()):
+    if has_negative or (uncertainty is not None and bool((uncertainty < 0).any())):
         raise ValueError("negative values in data and/or uncertainty matrix")
     if data.shape[0] <= params.nPatterns or data.shape[1] <= params.nPatterns:
         raise ValueError("nPatterns must be less than dimensions of data")
-    if uncertainty is not None and (uncertainty < 1e-5).any():
+    if uncertainty is not None and bool((uncertainty < 1e-5).any()):
         warnings.warn("small values in uncertainty matrix detected")
 
 
@@ -73,7 +76,25 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
                 data = read_matrix(path)
     elif path is not None:
         data = read_matrix(path)
-    if isinstance(data, _capi.DeviceMatrix):
+    if isinstance(uncertainty, str):
+        uncertainty = read_matrix(uncertainty)
+    unc = uncertainty
+    if _capi.is_tensor(data) or _capi.is_tensor(unc):
+        # a CPU tensor is its numpy view; a GPU tensor stays where it is, as contiguous fp32 (converted on its device), and so does its
+        # uncertainty: the checks below run there, the library builds its session from the two arrays on the device
+        if _capi.on_gpu(data):
+            import torch
+            if device not in (-1, None) and device != data.device.index:
+                raise ValueError("the data tensor resides on device %d, the run was given device=%d" % (data.device.index, device))
+            device = data.device.index
+            data = data.detach().to(dtype=torch.float32).contiguous()
+            if unc is not None:
+                unc = (unc.detach() if _capi.is_tensor(unc) else torch.from_numpy(np.ascontiguousarray(unc))).to(device=data.device, dtype=torch.float32).contiguous()
+        else:
+            data, unc, _ = _capi.device_input(data, unc, {})
+    if _capi.on_gpu(data):
+        pass
+    elif isinstance(data, _capi.DeviceMatrix):
         # uploaded and validated once by the caller; every run from it is a sparse-model session (the subset, if any, is taken on the device)
         if not params.sparseOptimization:
             raise ValueError("a DeviceMatrix needs sparseOptimization=True: the dense model takes a dense matrix")
@@ -85,7 +106,8 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
         data = data.astype(np.float32) if params.sparseOptimization else np.ascontiguousarray(data.toarray(), dtype=np.float32)
     else:
         data = np.ascontiguousarray(data, dtype=np.float32)
-    unc = None if uncertainty is None else np.ascontiguousarray(read_matrix(uncertainty) if isinstance(uncertainty, str) else uncertainty, dtype=np.float32)
+    if unc is not None and not _capi.on_gpu(unc):
+        unc = np.ascontiguousarray(unc, dtype=np.float32)
     check_inputs(data, unc, params, snapshotPhase, nSnapshots, checkpointInFile, nThreads)
     if not asynchronousUpdates:
         raise ValueError("asynchronousUpdates=FALSE selects the reference's sequential sampler; this library is the asynchronous one")

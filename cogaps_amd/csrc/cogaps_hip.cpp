@@ -16,6 +16,7 @@
 #include "aux_kernels.h"
 #include "sparse_kernels.h"
 #include "sparse_build.h"
+#include "dense_build.h"
 
 #include <math.h>
 #include <cmath>
@@ -744,6 +745,100 @@ static void build_samplers_device_matrix(cogaps_session *s, const cogaps_device_
     spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
 }
 
+// ---- dense input resident on the device (cogaps_session_create with data_on_device = 1; dense_build.h) ----
+// subsetData's indices in device memory (a temporary), or null without a subset
+static const uint32_t *dnb_subset(cogaps_session *s, SpbTemps &tmp)
+{
+    const bool subsetData = s->p.subsetData && !s->subset.empty();
+    return subsetData ? tmp.stage(s->subset.data(), s->subset.size(), false, s->stream) : nullptr;
+}
+static uint32_t dnb_grid(uint64_t workgroups)
+{
+    if (workgroups == 0 || workgroups > 0x7FFFFFFFull) throw std::runtime_error("the matrix has more tiles than one launch has workgroups");
+    return (uint32_t)workgroups;
+}
+
+// Both samplers of the dense model from the device-resident matrix: build_sampler's arrays and constants, bit for bit, with nothing of
+// the matrix on the host.  Per sampler one fill launch (D, Sraw, S2 if kept, the pads, the count of entries > 0), then both ordered sums
+// in one launch (its time: cogaps_session_sparse_build_ms), then the models and the atomic domains in build_sampler's order -- the
+// seeder's outputs go to A's queue, then P's.  The session owns what build_sampler's session owns; the indices, the sums and the
+// counts are temporaries.
+static void build_samplers_dense_device(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol, const float *unc)
+{
+    const cogaps_params &p = s->p;
+    const bool subsetData = p.subsetData && !s->subset.empty();
+    const uint32_t nIdx = (uint32_t)s->subset.size();
+    SpbTemps tmp;
+    const uint32_t *dIdx = dnb_subset(s, tmp);
+    uint32_t *scratch = tmp.err();      // [0], [1]: the counts of entries > 0, [2], [3]: the ordered sums (as floats)
+    const bool defaultS = unc == nullptr && !dev_env("COGAPS_READ_S");      // (build_sampler: no S2 array with the default uncertainty)
+    HostSampler *hs[2] = {&s->A, &s->P};
+    const bool genesInCols[2] = {!p.transposeData, p.transposeData != 0}, subsetGenes[2] = {!p.subsetGenes, p.subsetGenes != 0};      // GapsRunner.cpp:402-406
+    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
+    size_t tot[2];
+    for (int w = 0; w < 2; ++w) {
+        HostSampler &h = *hs[w]; SamplerDev &d = h.d;
+        const uint32_t nG = (subsetData && subsetGenes[w]) ? nIdx : (genesInCols[w] ? ncol : nrow);
+        const uint32_t nS = (subsetData && !subsetGenes[w]) ? nIdx : (genesInCols[w] ? nrow : ncol);
+        sampler_dims(s, h, w == 0 ? 'A' : 'P', nG, nS);
+        tot[w] = (size_t)d.M * d.Npad;
+        float *dD = dalloc<float>(tot[w]); d.D = dD;
+        float *dS2 = defaultS ? nullptr : dalloc<float>(tot[w]); d.S2 = dS2;
+        h.Sraw = dalloc<float>(tot[w]); d.defaultS = defaultS ? 1u : 0u;
+        // Matrix.cpp:30-69: the indices pick input rows when subsetGenes != genesInCols, input columns otherwise
+        const uint32_t *rowMap = subsetGenes[w] != genesInCols[w] ? dIdx : nullptr, *colMap = subsetGenes[w] == genesInCols[w] ? dIdx : nullptr;
+        DnbIn in; in.data = data; in.unc = unc; in.nrow = nrow; in.ncol = ncol;
+        DnbOut o; o.D = dD; o.Sraw = h.Sraw; o.S2 = dS2; o.M = d.M; o.N = d.N; o.Npad = d.Npad;
+        if (genesInCols[w]) {      // the vectors are input rows
+            in.vecMap = rowMap; in.elMap = colMap;
+            const uint32_t chunks = (d.Npad + (uint32_t)DNB_BS - 1u) / (uint32_t)DNB_BS;
+            RT_LAUNCH(dnb_rows_kernel, dnb_grid((uint64_t)d.M * chunks), DNB_BS, s->stream, in, o, chunks, scratch + w);
+        } else {                   // the vectors are input columns
+            in.vecMap = colMap; in.elMap = rowMap;
+            const uint32_t tilesI = (d.Npad + (uint32_t)DNB_TILE - 1u) / (uint32_t)DNB_TILE, tilesJ = (d.M + (uint32_t)DNB_TILE - 1u) / (uint32_t)DNB_TILE;
+            RT_LAUNCH(dnb_cols_kernel, dnb_grid((uint64_t)tilesI * tilesJ), DNB_BS, s->stream, in, o, tilesI, scratch + w);
+        }
+    }
+    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);
+    RT_LAUNCH(dnb_ordered_sum_kernel, 2, DNB_SUM_BS, s->stream, s->A.d.D, (uint64_t)tot[0], s->P.d.D, (uint64_t)tot[1], (float *)(scratch + 2));
+    rt_event_stop(ev, s->stream);
+    uint32_t host[4]; rt_d2h(host, scratch, sizeof(host), s->stream); rt_sync(s->stream);
+    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
+    for (int w = 0; w < 2; ++w) {
+        float sum; memcpy(&sum, &host[2 + w], 4);
+        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum, host[w]);
+        hs[w]->d.AP = dalloc<float>(tot[w]);
+        sampler_domain(s, *hs[w], alpha[w]);
+    }
+}
+
+// The sparse model from the device-resident matrix: build_samplers_dense_input's CSR matrix -- the entries > 0 of the subset's rows and
+// columns, ascending column indices -- compacted on the device, then the one builder.  The CSR arrays are temporaries of this call.
+static void build_samplers_dense_device_sparse(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol)
+{
+    const cogaps_params &p = s->p;
+    const bool subsetData = p.subsetData && !s->subset.empty();
+    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0), subsetCols = subsetData && !subsetRows;
+    const uint32_t nIdx = (uint32_t)s->subset.size();
+    SpbTemps tmp;
+    const uint32_t *dIdx = dnb_subset(s, tmp);
+    cogaps_sparse_matrix m; memset(&m, 0, sizeof(m));
+    m.nrow = subsetRows ? nIdx : nrow; m.ncol = subsetCols ? nIdx : ncol; m.majorIsRow = 1; m.onDevice = 1;
+    DnbIn in; in.data = data; in.unc = nullptr; in.nrow = nrow; in.ncol = ncol; in.vecMap = subsetRows ? dIdx : nullptr; in.elMap = subsetCols ? dIdx : nullptr;
+    uint32_t *ptr = tmp.alloc<uint32_t>((size_t)m.nrow + 1);
+    const uint32_t rowGrid = (m.nrow + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
+    RT_LAUNCH(dnb_csr_count_kernel, rowGrid, 64 * SPB_WAVES, s->stream, in, m.nrow, m.ncol, ptr);
+    // the total in 64 bits before the 32-bit scan
+    std::vector<uint32_t> counts(m.nrow); rt_d2h(counts.data(), ptr, (size_t)m.nrow * 4, s->stream); rt_sync(s->stream);
+    uint64_t total = 0; for (uint32_t c : counts) total += c;
+    if (total >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, ptr, m.nrow);
+    uint64_t *indptr = tmp.alloc<uint64_t>((size_t)m.nrow + 1); uint32_t *indices = tmp.alloc<uint32_t>((size_t)total + 1); float *values = tmp.alloc<float>((size_t)total + 1);
+    RT_LAUNCH(dnb_csr_fill_kernel, rowGrid, 64 * SPB_WAVES, s->stream, in, m.nrow, m.ncol, (const uint32_t *)ptr, indptr, indices, values);
+    m.indptr = indptr; m.indices = indices; m.values = values;
+    build_samplers_sparse_input(s, m);
+}
+
 static void read_gs(cogaps_session *s, HostSampler &h)
 {
     rt_d2h(s->hGs, h.d.gs, sizeof(GenScalars), s->stream);
@@ -1290,12 +1385,6 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         if (p.subsetData && p.dataIndicesSubset) s->subset.assign(p.dataIndicesSubset, p.dataIndicesSubset + p.nSubset);
         s->stream = rt_stream_create();
         rt_alloc_scope allocOn(s->stream); rt_owner_scope owner(&s->deviceBytes);
-        std::vector<float> hostData, hostUnc;
-        if (data_on_device) {          // device-resident input: stage through the host once, outside any timed region
-            hostData.resize((size_t)nrow * ncol); rt_d2h(hostData.data(), data, hostData.size() * 4, s->stream);
-            if (unc) { hostUnc.resize((size_t)nrow * ncol); rt_d2h(hostUnc.data(), unc, hostUnc.size() * 4, s->stream); }
-            rt_sync(s->stream); data = hostData.data(); if (unc) unc = hostUnc.data();
-        }
         s->hGs = (GenScalars *)rt_malloc_host(sizeof(GenScalars));
         // GapsRandomState(seed): seeder + lookup tables (Cogaps.cpp:158, Random.cpp:264-267)
         s->seeder.init(p.seed);
@@ -1312,7 +1401,9 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         if (sp) build_samplers_sparse_input(s, *sp);
         else if (coo) build_samplers_coo_input(s, *coo);
         else if (dm) build_samplers_device_matrix(s, *dm);
-        else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
+        else if (data_on_device) {      // device-resident dense input (and uncertainty): built where it lies (dense_build.h)
+            if (p.useSparseOptimization) build_samplers_dense_device_sparse(s, data, nrow, ncol); else build_samplers_dense_device(s, data, nrow, ncol, unc);
+        } else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
         else {
             build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
             build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
@@ -2205,6 +2296,36 @@ int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_par
     if (!rc) rc = cogaps_session_finish(s, out);
     cogaps_session_destroy(s);
     return rc;
+}
+
+int cogaps_run_device(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)
+{
+    if (!out) return fail("null argument");
+    cogaps_session *s = cogaps_session_create(data, nrow, ncol, params, unc, 1);
+    if (!s) return 1;
+    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
+    if (!rc) rc = cogaps_session_finish(s, out);
+    cogaps_session_destroy(s);
+    return rc;
+}
+
+int cogaps_session_debug_dense_data(cogaps_session *s, char which, float *D, float *Sraw, float *S2, float *lambda, float *maxGibbsMass, float *sparsity, int *hasS2)
+{
+    if (!s) return fail("null argument");
+    SESSION_TRY
+    const HostSampler &h = pick(s, which); const SamplerDev &d = h.d;
+    if (d.sparse) return fail("the session does not run the dense model");
+    const size_t bytes = (size_t)d.M * d.Npad * 4;
+    if (lambda) *lambda = d.lambda;
+    if (maxGibbsMass) *maxGibbsMass = d.maxGibbsMass;
+    if (sparsity) *sparsity = h.dataSparsity;
+    if (hasS2) *hasS2 = d.S2 != nullptr;
+    if (D) rt_d2h(D, d.D, bytes, s->stream);
+    if (Sraw) rt_d2h(Sraw, h.Sraw, bytes, s->stream);
+    if (S2 && d.S2) rt_d2h(S2, d.S2, bytes, s->stream);
+    rt_sync(s->stream);
+    SESSION_END
 }
 
 int cogaps_session_debug_sparse_data(cogaps_session *s, char which, uint32_t *Wn, uint32_t *nVals, float *lambda, float *maxGibbsMass,

@@ -1,6 +1,6 @@
 // sparse_build.h -- the sparse model's data structures, built on the device from a compressed-sparse matrix (CSR or CSC) or from unordered
 // triplets (COO: further down), and meanChiSq from them.  Every sparse-model session is built here, whatever its input: a dense matrix
-// is compacted to CSR on the host first (cogaps_hip.cpp, build_samplers_dense_input).  These four arrays per sampler are all the data
+// is compacted to CSR first -- on the host (cogaps_hip.cpp, build_samplers_dense_input), or on the device when it resides there (dense_build.h).  These four arrays per sampler are all the data
 // such a session holds: no genes x samples array exists on the device.
 //
 // A sampler holds its data as [vector j][element i]: dflags [M][Wn] (bit i of vector j: the entry is > 0), dprefix [M][Wn] (packed

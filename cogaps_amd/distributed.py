@@ -363,6 +363,9 @@ class _Source:
         the indices first: the sets are sorted to match;
       * a callable loader(i, indices) -> matrix or (matrix, uncertainty): shard i's own contiguous sub-matrix for the 1-based
         `indices` (rows of the data when the partitioned dimension is the rows, else columns), with `shape` = dimensions of the whole.
+      * a torch tensor on this rank's GPU (the whole dense matrix is resident there, with its uncertainty if any): every shard's session
+        is created from the one array with subsetIndices = sets[i], the rows / columns gathered on the device (csrc/dense_build.h), in
+        the order given like the array's, for either model; nothing is cut on the host.
       * a DeviceMatrix (the caller's choice: the WHOLE matrix is resident on this rank's GPU): every shard's session is created from it
         with subsetIndices = sets[i] and the subset is taken on the device (cogaps_session_create_from_device_matrix), in the order given
         like the array's; nothing is cut or uploaded per shard.
@@ -370,14 +373,15 @@ class _Source:
 
     def __init__(self, data, uncertainty, shape, subset_rows, sparse_model=False):
         self.data, self.unc, self.subset_rows = data, uncertainty, subset_rows
-        self.kind = "device" if isinstance(data, _capi.DeviceMatrix) else "path" if isinstance(data, (str, bytes)) else ("loader" if callable(data) else "array")
+        self.tensor = _capi.on_gpu(data)
+        self.kind = "device" if isinstance(data, _capi.DeviceMatrix) or self.tensor else "path" if isinstance(data, (str, bytes)) else ("loader" if callable(data) else "array")
         self.sparse = self.kind == "array" and _capi.is_sparse(data)
         self.sparse_model = bool(sparse_model)
         if self.sparse:
             self.data = data.tocsr() if subset_rows else data.tocsc()      # the form whose major slices the shards are
         if self.kind in ("array", "device"):
             self.shape = tuple(data.shape)
-            if self.kind == "device" and (uncertainty is not None or not sparse_model):
+            if self.kind == "device" and not self.tensor and (uncertainty is not None or not sparse_model):
                 raise ValueError("a DeviceMatrix takes no uncertainty matrix and needs sparseOptimization=True")
         elif self.kind == "path":
             nr, nc, self.row_names, self.col_names = _capi.file_info(data)
@@ -400,7 +404,7 @@ class _Source:
 
     def shard(self, i, idx1):
         if self.kind == "device":
-            return self.data, None      # the shard's session takes its rows / columns from the handle itself (subsetIndices)
+            return self.data, self.unc      # the shard's session takes its rows / columns from the resident matrix itself (subsetIndices)
         if self.sparse:
             idx = np.asarray(idx1, dtype=np.int64) - 1
             m = self.data[idx, :] if self.subset_rows else self.data[:, idx]
@@ -441,12 +445,14 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist else (1, 0)
     if world > len(sets):                                      # every rank sees this before the first collective: none is left waiting
         raise ValueError("more ranks (%d) than subsets (%d)" % (world, len(sets)))
+    if src.tensor and (device is None or device < 0):
+        device = data.device.index
     if device is None or device < 0:
         # The HIP current device belongs to the calling host thread; the shards in flight run on pool threads that start on
         # device 0.  Resolve the ordinal once, here, and hand it to every shard explicitly.
         device = _current_device(run_fn)
-    if src.kind == "device" and run_fn is _capi.run and data.device != device:
-        raise ValueError("the DeviceMatrix resides on device %d, the run uses device %d" % (data.device, device))
+    if src.kind == "device" and run_fn is _capi.run and (data.device.index if src.tensor else data.device) != device:
+        raise ValueError("the %s resides on device %d, the run uses device %d" % (("data tensor", data.device.index, device) if src.tensor else ("DeviceMatrix", data.device, device)))
     if comm_device is None:
         comm_device = "cpu"
         if dist is not None and dist.get_backend() == "nccl":
@@ -465,7 +471,7 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         return g_, s_, bool(params.sparseOptimization), src.has_unc()
     if src.sparse and src.sparse_model:
         shape_of.nnz = lambda i: src.shard_nnz(sets[i])
-    elif src.kind == "device":
+    elif src.kind == "device" and not src.tensor:
         shape_of.nnz = lambda i: data.nnz * len(sets[i]) // total      # (the handle's stored entries, spread evenly over the partitioned axis)
     # a DeviceMatrix hands every worker the whole matrix and its subsetIndices, as the reference does (R/DistributedCogaps.R:12-35)
     subset_kw = (lambda i: dict(subsetIndices=sets[i], subsetDim=1 if genome_wide else 2)) if src.kind == "device" else (lambda i: {})

@@ -125,6 +125,11 @@ void cogaps_default_params(cogaps_params *p);
  * transposeData), uncertainty the same shape or NULL.  Host pointers. */
 int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params,
                const float *uncertainty, cogaps_result *out);
+/* cogaps_run for DEVICE pointers: `data` -- and `uncertainty`, unless NULL -- are row-major [nrow][ncol] fp32 arrays in the memory of
+ * params->device (-1: the calling thread's current device).  cogaps_session_create with data_on_device = 1 + phases + finish: see there
+ * for the contract.  Every field of the result is what cogaps_run gives for host copies of the same arrays. */
+int cogaps_run_device(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params,
+                      const float *uncertainty, cogaps_result *out);
 /* gaps::run for a matrix file (src/GapsRunner.h:24-29; Rcpp cogaps_from_file_cpp, src/Cogaps.cpp:217-227): .mtx, .csv, .tsv
  * or .gct, read as the reference's parsers read them (src/file_parser/, incl. the text -> fp32 rule of
  * MatrixElement.cpp:10-47); uncertaintyPath NULL or "" for the default uncertainty. */
@@ -190,7 +195,19 @@ typedef struct cogaps_trace_rec {   /* one queued proposal, ProposalQueue.h:15-2
  * pointers and values of the entries > 0, built on the device (csrc/sparse_build.h) -- and no nrow x ncol array, whichever of the
  * three entries created it: this one compacts the dense matrix to CSR on the host (applying subsetData; `uncertainty` is ignored,
  * the model knows the default only) and goes through the builder of cogaps_session_create_sparse.  A dense matrix with 2^32 - 1
- * or more entries > 0 is refused with that builder's message. */
+ * or more entries > 0 is refused with that builder's message.
+ *
+ * data_on_device = 1: `data` AND `uncertainty` (unless NULL) are device pointers of params->device, row-major [nrow][ncol] fp32, and
+ * are consumed where they lie (csrc/dense_build.h): nothing of size nrow x ncol is allocated on the host or copied to it.  The dense
+ * model's D, Sraw and S2 of both samplers are written by one kernel pass per sampler (a copy or gather for the sampler whose vectors
+ * are input rows, a transpose through LDS tiles for the other; subsetData's indices gather on either axis), lambda's sum by an ordered
+ * one-accumulator pass on the device; the sparse model's CSR matrix is compacted on the device (count, scan, fill) and handed to the
+ * builder of cogaps_session_create_sparse.  THE SESSION IS, BIT FOR BIT, THE SESSION THE SAME CALL MAKES WITH data_on_device = 0 FROM
+ * HOST COPIES OF THE ARRAYS: data arrays with their pads, lambda, maxGibbsMass, dataSparsity, the seeder's state, every proposal, and
+ * cogaps_session_device_bytes (the build's temporaries -- the subset's indices, for the sparse model the CSR arrays -- are released
+ * before the call returns and never counted).  Completion contract: the caller's arrays must be complete before the call (work queued
+ * on the caller's own streams is not waited for); the library reads them on its own stream, synchronises that stream before it
+ * returns, and does not reference them afterwards.  Errors and their texts are those of the host-pointer call. */
 cogaps_session *cogaps_session_create(const float *data, uint32_t nrow, uint32_t ncol,
                                       const cogaps_params *params, const float *uncertainty,
                                       int data_on_device);
@@ -293,12 +310,19 @@ int cogaps_run_device_matrix(const cogaps_device_matrix *m, const cogaps_params 
  * hipMemGetInfo, which is device-wide.  For every session, however it was created. */
 int cogaps_session_device_bytes(cogaps_session *s, uint64_t *bytes);
 /* HIP-event time of the two ordered fp32 sums over the packed values at the creation of a sparse-model session, whatever its input
- * (the one serial pass of the build; 0 for a session of the dense model) */
+ * (the one serial pass of the build), or of the two ordered sums over D of a dense-model session built from device pointers; 0 for a
+ * dense-model session built from host pointers (its sums run on the host) */
 int cogaps_session_sparse_build_ms(cogaps_session *s, float *orderedSumMs);
 /* test hook: the sparse model's data structures of sampler `which` -- flags / prefix [M][Wn], ptr [M + 1], vals [nVals] -- and the
  * constants derived from the data; NULL skips an output (sizes first, then the arrays) */
 int cogaps_session_debug_sparse_data(cogaps_session *s, char which, uint32_t *Wn, uint32_t *nVals, float *lambda, float *maxGibbsMass,
                                      uint64_t *flags, uint32_t *prefix, uint32_t *ptr, float *vals);
+/* test hook, the dense model's counterpart: the raw [M][Npad] arrays of sampler `which` as the device holds them, pads included -- D,
+ * Sraw (the un-squared uncertainty) and S2 -- and the constants derived from the data (lambda, maxGibbsMass, DenseNormalModel's
+ * dataSparsity).  NULL skips an output.  *hasS2 = 0 and S2 left untouched when the session keeps no S2 array (the default uncertainty:
+ * the evaluation recomputes it from D); M, N from cogaps_session_dims, Npad = (N + 3) & ~3. */
+int cogaps_session_debug_dense_data(cogaps_session *s, char which, float *D, float *Sraw, float *S2, float *lambda, float *maxGibbsMass,
+                                    float *sparsity, int *hasS2);
 /* annealing temperature of both samplers (runOnePhase sets min(1, 2*iter/nIter) while equilibrating) */
 int cogaps_session_set_annealing(cogaps_session *s, float temp);
 /* nA, nP ~ Poisson(max(nAtoms,10)) from the runner's generator (GapsRunner.cpp:294-295) */
