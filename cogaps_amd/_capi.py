@@ -97,6 +97,7 @@ EXPORTS = [
     "cogaps_device_matrix_create_sparse", "cogaps_device_matrix_create_coo", "cogaps_device_matrix_destroy", "cogaps_device_matrix_info",
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
+    "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -210,6 +211,11 @@ def bind(L):
     L.cogaps_current_device.argtypes = [C.POINTER(C.c_int)]
     L.cogaps_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.cogaps_session_debug_check_domain.argtypes = [vp, C.c_char, u32p]
+    L.cogaps_session_position.argtypes = [vp, C.POINTER(C.c_int), u32p]
+    L.cogaps_session_save_state.argtypes = [vp, C.c_char_p]
+    L.cogaps_session_load_state.argtypes = [vp, C.c_char_p]
+    L.cogaps_session_run_to_end.argtypes = [vp, C.c_char_p, C.c_uint32, C.POINTER(CogapsResultC)]
+    L.cogaps_session_debug_data_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -260,7 +266,7 @@ def make_params(L, nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, n
                 fixedPatterns=None, sparseOptimization=False, asynchronousUpdates=True,
                 messages=False, workerID=1, device=-1, takePumpSamples=False,
                 checkpointInterval=0, nSnapshots=0, snapshotPhase="sampling", snapshotFrequency=None,
-                pumpThreshold="unique", reductionMode="lanes", mathMode="portable", runningDistributed=False):
+                pumpThreshold="unique", reductionMode="lanes", mathMode="portable", runningDistributed=False, interrupt=None):
     p = CogapsParamsC()
     L.cogaps_default_params(C.byref(p))
     p.nPatterns, p.nIterations, p.seed = int(nPatterns), int(nIterations), int(seed)
@@ -283,6 +289,11 @@ def make_params(L, nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, n
     p.reductionMode = _REDUCE[reductionMode] if isinstance(reductionMode, str) else int(reductionMode)
     p.mathMode = _MATH[mathMode] if isinstance(mathMode, str) else int(mathMode)
     keep = []
+    if interrupt is not None:
+        # cogaps_params.interrupt: a callable without arguments, polled at the head of every iteration; a true value ends the run
+        fn = INTERRUPT_FN(lambda _arg: int(bool(interrupt())))
+        keep.append(fn)
+        p.interrupt = fn
     if subsetIndices is not None and subsetDim > 0:
         idx = np.ascontiguousarray(subsetIndices, dtype=np.uint32)
         keep.append(idx)
@@ -781,6 +792,34 @@ class Session:
         self._ck(self.L.cogaps_session_finish(self.h, C.byref(r)))
         return result_to_dict(self.L, r)
 
+    def position(self):
+        """(phase, next iteration of that phase) as run_iterations / Batch.run_iterations left it; phase 3: both phases complete"""
+        ph, it = C.c_int(), C.c_uint32()
+        self._ck(self.L.cogaps_session_position(self.h, C.byref(ph), C.byref(it)))
+        return ph.value, it.value
+
+    def save_state(self, path):
+        """the chain's state into the library's state file (include/cogaps_hip.h): between two iterations; written beside `path`, then renamed"""
+        self._ck(self.L.cogaps_session_save_state(self.h, os.fsencode(path)))
+
+    def load_state(self, path):
+        """continue the chain a state file holds: this session must be made from the same data and parameters (any input form); a
+        refused file leaves it untouched"""
+        self._ck(self.L.cogaps_session_load_state(self.h, os.fsencode(path)))
+
+    def run_to_end(self, state_file=None, interval=0):
+        """what remains of the two phases from position(), then finish(); with a state file: saved every `interval` iterations (0: not on
+        the way), when the run is complete, and before an interrupt ends the call"""
+        r = CogapsResultC()
+        self._ck(self.L.cogaps_session_run_to_end(self.h, None if state_file is None else os.fsencode(state_file), int(interval), C.byref(r)))
+        return result_to_dict(self.L, r)
+
+    def data_digest(self):
+        """test hook: the 64-bit digest of the session's data as the state file's fingerprint holds it"""
+        v = C.c_uint64(0)
+        self._ck(self.L.cogaps_session_debug_data_digest(self.h, C.byref(v)))
+        return int(v.value)
+
 
 def read_matrix_file(path, lib=None, rows=None, cols=None):
     """The library's own reader (csrc/file_reader.h): the file as a dense fp32 matrix.  Host only.  rows / cols (one of them): 1-based
@@ -849,9 +888,23 @@ def run_from_file(path, unc_path=None, lib=None, **kw):
     return result_to_dict(L, res)
 
 
-def run(data, unc=None, lib=None, **kw):
-    """cogaps_run: one full equilibration + sampling run."""
+def run(data, unc=None, lib=None, stateFile=None, stateInterval=0, resume=False, **kw):
+    """cogaps_run: one full equilibration + sampling run.  With stateFile the run goes through a Session of whatever input form was
+    given and cogaps_session_run_to_end: the state is saved every stateInterval iterations (0: not on the way), at the end, and when an
+    interrupt ends the run; resume=True continues from the file if it exists (a job that restarts itself) and starts from the
+    beginning if it does not."""
     L = lib if lib is not None else load()
+    if stateFile is None:
+        if resume or stateInterval:
+            raise ValueError("resume / stateInterval need a stateFile")
+    else:
+        s = Session(data, unc=unc, lib=L, **kw)
+        try:
+            if resume and os.path.exists(stateFile):
+                s.load_state(stateFile)
+            return s.run_to_end(stateFile, stateInterval)
+        finally:
+            s.close()
     data, unc, kw = device_input(data, unc, kw)
     p = make_params(L, **kw)
     r = CogapsResultC()

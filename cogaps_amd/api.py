@@ -6,6 +6,10 @@ on the GPU is checked and consumed there, with its uncertainty, and never copied
 and distributed shards are then taken from it on the device; sparseOptimization=True only) or a path to a .mtx/.csv/.tsv file (a .mtx file with sparseOptimization=True
 is read as triplets by the library and never densified either).  The standard run dispatches to cogaps_run (the C-ABI replacement of gaps::run);
 `distributed` = "genome-wide" / "single-cell" dispatches to cogaps_amd.distributed (GWCoGAPS / scCoGAPS).
+
+stateFile / stateInterval / resume (a standard run only): the library's own state file (include/cogaps_hip.h, cogaps_session_run_to_end) --
+the run saves its chain every stateInterval iterations, at its end and when it is interrupted, and resume=True continues the chain the file
+holds, bit for bit (from the beginning if there is no file).  Not the reference's checkpoints: checkpointInFile stays refused.
 """
 import warnings
 
@@ -48,7 +52,8 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
 
 def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputFrequency=1000, uncertainty=None,
            checkpointOutFile="gaps_checkpoint.out", checkpointInterval=0, checkpointInFile=None, transposeData=False,
-           BPPARAM=None, workerID=1, asynchronousUpdates=True, nSnapshots=0, snapshotPhase="sampling", device=-1, **extra):
+           BPPARAM=None, workerID=1, asynchronousUpdates=True, nSnapshots=0, snapshotPhase="sampling", device=-1,
+           stateFile=None, stateInterval=0, resume=False, **extra):
     if params is None:
         params = CogapsParams(**({} if nPatterns is None else {"nPatterns": nPatterns}))
     else:
@@ -111,7 +116,11 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
     check_inputs(data, unc, params, snapshotPhase, nSnapshots, checkpointInFile, nThreads)
     if not asynchronousUpdates:
         raise ValueError("asynchronousUpdates=FALSE selects the reference's sequential sampler; this library is the asynchronous one")
+    if stateFile is None and (resume or stateInterval):
+        raise ValueError("resume / stateInterval need a stateFile")
     if params.distributed is not None:
+        if stateFile is not None:
+            raise ValueError("the distributed drivers do not take a state file yet (stateFile / stateInterval / resume serve a standard run)")
         from .distributed import distributedCogaps
         if isinstance(data, _capi.CooMatrix):
             data = data.tocsr()                                  # the shard code cuts a scipy.sparse matrix (repeats resolved on the host: the last entry decides)
@@ -134,7 +143,8 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
                         whichMatrixFixed=params.whichMatrixFixed, **subset_kw,
                         fixedPatterns=params.fixedPatterns, sparseOptimization=params.sparseOptimization, messages=messages,
                         workerID=workerID, device=device, takePumpSamples=params.takePumpSamples,
-                        nSnapshots=nSnapshots, snapshotPhase=snapshotPhase)
+                        nSnapshots=nSnapshots, snapshotPhase=snapshotPhase,
+                        **({} if stateFile is None else dict(stateFile=stateFile, stateInterval=stateInterval, resume=resume)))
     return CogapsResult(raw, params=params, geneNames=params.geneNames, sampleNames=params.sampleNames)
 
 

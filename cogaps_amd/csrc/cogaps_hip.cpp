@@ -17,6 +17,8 @@
 #include "sparse_kernels.h"
 #include "sparse_build.h"
 #include "dense_build.h"
+#include "state_digest.h"
+#include "state_file.h"
 
 #include <math.h>
 #include <cmath>
@@ -313,6 +315,12 @@ struct cogaps_session {
     std::atomic<uint64_t> deviceBytes{0};      // device memory the session holds (rt_owner_scope; cogaps_session_device_bytes)
     float orderedSumMs = 0.f;     // ... and what the ordered sums of the packed values took at its creation (HIP events)
     bool poisoned = false;        // a device error ended an update half way (capacity, a hand-over inside a launch that never arrived): the chain's state is not a state of the chain
+    // where the run stands (cogaps_session_position): the phase and its next iteration, advanced by cogaps_session_run_iterations and
+    // cogaps_batch_run_iterations; phase 3 = both phases complete
+    int posPhase = 1; uint32_t posNext = 0;
+    // state-file fingerprint (the state-file section below): a hash of fixedPatterns, taken at creation (the caller's array is not kept), and
+    // the data digest, computed on the device at the first save or load
+    uint64_t fixedHash = 0, dataDigest = 0; bool digestValid = false;
 };
 
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
@@ -1420,6 +1428,7 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         if (p.whichMatrixFixed != 'N') {
             HostSampler &f = (p.whichMatrixFixed == 'A') ? s->A : s->P;
             if (!p.fixedPatterns || p.fixedRows != f.d.M) throw std::runtime_error("fixedPatterns must have one row per row of the fixed matrix");
+            s->fixedHash = cgstate::hash_bytes(p.fixedPatterns, (size_t)f.d.M * f.d.K * sizeof(float));
             std::vector<float> m((size_t)f.d.K * f.d.Mpad, 0.f);
             for (uint32_t r = 0; r < f.d.M; ++r) for (uint32_t k = 0; k < f.d.K; ++k) m[(size_t)k * f.d.Mpad + r] = p.fixedPatterns[(size_t)r * f.d.K + k];
             if (f.d.sparse) {
@@ -1698,6 +1707,12 @@ static int iteration_tail(cogaps_session *s, int phase, uint32_t it)
     return 0;
 }
 
+// the session's position behind iteration `done` - 1 of `phase`: the last iteration of a phase hands over to the next phase
+static void set_position(cogaps_session *s, int phase, uint32_t done)
+{
+    if (done == s->p.nIterations) { s->posPhase = phase + 1; s->posNext = 0; } else { s->posPhase = phase; s->posNext = done; }
+}
+
 // runOnePhase (GapsRunner.cpp:272-327) for iterations [firstIter, firstIter+n)
 int cogaps_session_run_iterations(cogaps_session *s, int phase, uint32_t firstIter, uint32_t n, uint64_t *updates)
 {
@@ -1710,6 +1725,7 @@ int cogaps_session_run_iterations(cogaps_session *s, int phase, uint32_t firstIt
         if (cogaps_session_iterate(s, nA, nP, phase == 2)) return 1;
         if (updates) *updates += (uint64_t)nA + nP;
         if (iteration_tail(s, phase, it)) return 1;
+        set_position(s, phase, it + 1u);
     }
     rt_sync(s->stream);
     s->samplerSeconds += now_s() - t0;
@@ -1960,6 +1976,7 @@ int cogaps_batch_run_iterations(cogaps_batch *b, int phase, uint32_t firstIter, 
                 if (updates) updates[c] += (uint64_t)nA[c] + nP[c];
                 if (iteration_tail(b->ss[c], phase, it)) return 1;
             }
+            for (cogaps_session *s : b->ss) set_position(s, phase, it + 1u);
         }
         rt_sync(b->stream);
         const double dt = now_s() - t0;
@@ -2285,6 +2302,290 @@ int cogaps_session_chained(cogaps_session *s, char which, int *chained)
     if (!chained) return fail("null argument");
     *chained = pick(s, which).chain ? 1 : 0;
     SESSION_END
+}
+
+// ================================================================================================================================
+// The library's own STATE FILE: what changes while a chain runs, saved between two iterations and loaded into a session created the
+// ordinary way from the same data and parameters -- the resumed chain is the uninterrupted chain, bit for bit.  (Not the reference's
+// Archive checkpoints: cogaps_checkpoints_enabled stays 0.)  Container: state_file.h.  Sections:
+//   fingerprint  what a file and a session must agree on, as 64-bit words in the order of FP_NAMES
+//   meta         StateMeta: position, host generators, counters, times, the lengths of the variable sections
+//   per session  the seeder's look-ahead, the four statistics accumulators, the PUMP matrix, snapshots, the three histories
+//   per sampler that runs (a fixed matrix's sampler keeps what creation gave it): GenScalars, the factor matrix, colPos, the atomic
+//                domain -- atom records up to the handle high-water mark, the index vector up to the atom count, the free-handle stack up
+//                to its depth, bin heads, occupancy bitmaps --, for the sparse model the row copy, its flags and the lookup tables
+//   A*P          the dense model's cache of ONE sampler: P's, or A's when P is fixed; without a fixed matrix A's is its transpose (do_sync)
+// Not in the file, because the next batch cannot see them: the conflict stamps and queued-move destinations (valid for their own batch
+// epoch only; a load clears them), the queue, the erase cache (empty between updates), hand-over granules; and nothing of the data, the
+// lookup tables or a capacity.  Launch form -- chained or not, graphs, generator window, a batch -- is the loading session's own.
+// ================================================================================================================================
+static const char *const FP_NAMES[] = {
+    "model (useSparseOptimization)", "nGenes", "nSamples", "nPatterns", "seed", "nIterations", "alphaA", "alphaP", "maxGibbsMassA", "maxGibbsMassP",
+    "outputFrequency", "snapshotFrequency", "snapshotPhase", "takePumpSamples", "pumpThreshold", "whichMatrixFixed", "fixedPatterns",
+    "reductionMode", "mathMode", "lambda of A (data)", "lambda of P (data)", "maxGibbsMass / lambda of A (data)", "maxGibbsMass / lambda of P (data)",
+    "dataSparsity of A (data)", "dataSparsity of P (data)", "number of packed values (data)", "data digest (the data differ)" };
+static const int FP_N = (int)(sizeof(FP_NAMES) / sizeof(FP_NAMES[0]));
+struct StateMeta {
+    uint32_t phase, nextIter;
+    uint64_t seeder0, seeder1, runnerRng, totalUpdates;
+    double samplerSeconds, elapsedSeconds;
+    uint32_t statUpdates, pumpUpdates, nSnap[2], nHistory, genScalarsBytes;
+    uint64_t nSeedFifo;
+    struct { uint32_t present, nAtoms; float avgQueue, anneal; } samp[2];
+};
+enum { SEC_FINGERPRINT = 1, SEC_META, SEC_SEEDFIFO, SEC_ASUM, SEC_ASQ, SEC_PSUM, SEC_PSQ, SEC_PUMP, SEC_SNAP_A_EQ, SEC_SNAP_P_EQ, SEC_SNAP_A_SA, SEC_SNAP_P_SA,
+       SEC_CHISQ_HIST, SEC_ATOM_HIST_A, SEC_ATOM_HIST_P,
+       SEC_SAMPLER = 0x100,      // + 0x100 * (0: A, 1: P) + one of:
+       SS_GS = 0, SS_MAT, SS_COLPOS, SS_ATOMS, SS_VEC, SS_FREE, SS_BINHEAD, SS_BITS0, SS_BITS1, SS_BITS2, SS_AP, SS_ROWS, SS_MFLAGS, SS_Z1, SS_Z2 };
+static const size_t STATE_STAGING_BYTES = (size_t)4 << 20;      // device arrays pass through one pinned buffer of this size
+
+static float f_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+// the data digest (state_digest.h), computed once per session, at its first save or load; its scratch word is not the session's
+static uint64_t data_digest(cogaps_session *s)
+{
+    if (s->digestValid) return s->dataDigest;
+    const SamplerDev &d = s->A.d;
+    rt_owner_scope notTheSessions(nullptr);
+    unsigned long long *out = dalloc<unsigned long long>(1);
+    try {
+        uint32_t nVals = 0;
+        if (d.sparse) { rt_d2h(&nVals, d.dptr + d.M, 4, s->stream); rt_sync(s->stream); }
+        const unsigned long long rows = d.sparse ? 1ull : d.M, nFlags = d.sparse ? (unsigned long long)d.M * d.Wn : 0ull;
+        const uint32_t N = d.sparse ? nVals : d.N, stride = d.sparse ? nVals : d.Npad;
+        const unsigned long long items = std::max<unsigned long long>(rows * N, nFlags);
+        const uint32_t grid = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>((items + 4u * DIGEST_BS - 1u) / (4u * DIGEST_BS), 2048u));
+        RT_LAUNCH(state_digest_kernel, grid, DIGEST_BS, s->stream, (const uint32_t *)(d.sparse ? (const void *)d.dvals : (const void *)d.D), rows, N, stride,
+                  (const unsigned long long *)d.dflags, nFlags, out);
+        unsigned long long v = 0; rt_d2h(&v, out, 8, s->stream); rt_sync(s->stream);
+        s->dataDigest = v; s->digestValid = true;
+    } catch (...) { rt_free(out); throw; }
+    rt_free(out);
+    return s->dataDigest;
+}
+static void state_fingerprint(cogaps_session *s, uint64_t *fp)
+{
+    const cogaps_params &p = s->p;
+    uint32_t nVals = 0;
+    if (p.useSparseOptimization) { rt_d2h(&nVals, s->A.d.dptr + s->A.d.M, 4, s->stream); rt_sync(s->stream); }
+    const uint64_t v[] = {
+        (uint64_t)(p.useSparseOptimization != 0), s->nGenes, s->nSamples, s->K, p.seed, p.nIterations, gm_f2u(p.alphaA), gm_f2u(p.alphaP), gm_f2u(p.maxGibbsMassA), gm_f2u(p.maxGibbsMassP),
+        p.outputFrequency, p.snapshotFrequency, (uint64_t)(uint32_t)p.snapshotPhase, (uint64_t)(p.takePumpSamples != 0), (uint64_t)(uint32_t)p.pumpThreshold, (uint64_t)(unsigned char)p.whichMatrixFixed, s->fixedHash,
+        (uint64_t)(uint32_t)p.reductionMode, (uint64_t)(uint32_t)p.mathMode, gm_f2u(s->A.d.lambda), gm_f2u(s->P.d.lambda), gm_f2u(s->A.d.maxGibbsMass), gm_f2u(s->P.d.maxGibbsMass),
+        p.useSparseOptimization ? 0u : gm_f2u(s->A.dataSparsity), p.useSparseOptimization ? 0u : gm_f2u(s->P.dataSparsity), nVals, data_digest(s) };
+    static_assert(sizeof(v) / sizeof(v[0]) == (size_t)FP_N, "one value per name");
+    memcpy(fp, v, sizeof(v));
+}
+// how a differing fingerprint word reads in a message
+static std::string fp_text(int i, uint64_t v)
+{
+    if ((i >= 6 && i <= 9) || (i >= 19 && i <= 24)) { char b[64]; snprintf(b, sizeof(b), "%.9g", (double)f_of((uint32_t)v)); return b; }
+    if (i == 15) return std::string(1, (char)v);
+    if (i == 16 || i == 26) { char b[32]; snprintf(b, sizeof(b), "%016llx", (unsigned long long)v); return b; }
+    return std::to_string(v);
+}
+// host arrays of a state: a save points at the session's own, a load at temporaries of the lengths the file's meta section states
+struct StateHostArrays { uint64_t *fifo; float *snapA[2], *snapP[2], *chisq; uint32_t *histA, *histP; };
+// Every section of the session's state with its size, in file order: the one list a save writes and a load expects.  gs: the samplers'
+// scalars (a save's: just read back; a load's: the file's), which size the atomic domain's sections.
+static std::vector<cgstate::Section> state_sections(cogaps_session *s, uint64_t *fp, StateMeta *meta, GenScalars *gs, const StateHostArrays &ha)
+{
+    std::vector<cgstate::Section> v;
+    auto host = [&](uint32_t id, void *p, uint64_t bytes) { static char none; v.push_back({id, bytes ? p : (void *)&none, nullptr, bytes}); };
+    auto dev = [&](uint32_t id, void *p, uint64_t bytes) { v.push_back({id, nullptr, p, bytes}); };
+    const uint64_t K = s->K, na = (uint64_t)s->nGenes * K, np_ = (uint64_t)s->nSamples * K;
+    host(SEC_FINGERPRINT, fp, (uint64_t)FP_N * 8); host(SEC_META, meta, sizeof(StateMeta));
+    host(SEC_SEEDFIFO, ha.fifo, meta->nSeedFifo * 8);
+    dev(SEC_ASUM, s->Asum, K * s->A.d.Mpad * 4); dev(SEC_ASQ, s->Asq, K * s->A.d.Mpad * 4);
+    dev(SEC_PSUM, s->Psum, K * s->P.d.Mpad * 4); dev(SEC_PSQ, s->Psq, K * s->P.d.Mpad * 4);
+    dev(SEC_PUMP, s->pump, na * 4);
+    host(SEC_SNAP_A_EQ, ha.snapA[0], meta->nSnap[0] * na * 4); host(SEC_SNAP_P_EQ, ha.snapP[0], meta->nSnap[0] * np_ * 4);
+    host(SEC_SNAP_A_SA, ha.snapA[1], meta->nSnap[1] * na * 4); host(SEC_SNAP_P_SA, ha.snapP[1], meta->nSnap[1] * np_ * 4);
+    host(SEC_CHISQ_HIST, ha.chisq, (uint64_t)meta->nHistory * 4); host(SEC_ATOM_HIST_A, ha.histA, (uint64_t)meta->nHistory * 4); host(SEC_ATOM_HIST_P, ha.histP, (uint64_t)meta->nHistory * 4);
+    const char fixed = s->p.whichMatrixFixed;
+    for (int w = 0; w < 2; ++w) {
+        if (!meta->samp[w].present) continue;
+        const SamplerDev &d = (w == 0 ? s->A : s->P).d; const GenScalars &g = gs[w];
+        const uint32_t base = SEC_SAMPLER + 0x100u * (uint32_t)w;
+        host(base + SS_GS, &gs[w], sizeof(GenScalars));
+        dev(base + SS_MAT, d.mat, (uint64_t)d.K * d.Mpad * 4); dev(base + SS_COLPOS, d.colPos, (uint64_t)d.K * 4);
+        dev(base + SS_ATOMS, d.atoms, (uint64_t)g.handleHi * sizeof(AtomRec)); dev(base + SS_VEC, d.vec, (uint64_t)g.nAtoms * 4); dev(base + SS_FREE, d.freeHandles, (uint64_t)g.freeCount * 4);
+        dev(base + SS_BINHEAD, d.binHead, (uint64_t)d.M * d.K * 4);
+        dev(base + SS_BITS0, d.bits0, (uint64_t)d.nWords0 * 8); dev(base + SS_BITS1, d.bits1, (uint64_t)d.nWords1 * 8); dev(base + SS_BITS2, d.bits2, (uint64_t)d.nWords2 * 8);
+        if (d.sparse) {
+            dev(base + SS_ROWS, d.rows, (uint64_t)d.M * d.Kpad * 4); dev(base + SS_MFLAGS, d.mflags, (uint64_t)d.K * d.Mw * 8);
+            dev(base + SS_Z1, d.Z1, (uint64_t)d.K * 4); dev(base + SS_Z2, d.Z2, (uint64_t)d.K * d.K * 4);
+        } else if (w == (fixed == 'P' ? 0 : 1)) dev(base + SS_AP, d.AP, (uint64_t)d.M * d.Npad * 4);
+    }
+    return v;
+}
+// pinned staging buffer of a save or load (not the session's: released before the call returns)
+struct StateStaging { void *p; StateStaging() : p(rt_malloc_host(STATE_STAGING_BYTES)) {} ~StateStaging() { rt_free_host(p); } };
+
+static int state_refusal(cogaps_session *s, const char *path, const char *what)
+{
+    if (!s || !path) return fail("null argument");
+    if (s->poisoned) return fail(std::string("this session was ended by a device error; its state cannot be ") + what);
+    return 0;
+}
+
+int cogaps_session_position(cogaps_session *s, int *phase, uint32_t *nextIter)
+{
+    if (!s) return fail("null argument");
+    if (phase) *phase = s->posPhase;
+    if (nextIter) *nextIter = s->posNext;
+    return 0;
+}
+
+int cogaps_session_debug_data_digest(cogaps_session *s, uint64_t *digest)
+{
+    if (!s || !digest) return fail("null argument");
+    SESSION_TRY
+    s->digestValid = false;      // (the hook computes it anew every time)
+    *digest = data_digest(s);
+    SESSION_END
+}
+
+int cogaps_session_save_state(cogaps_session *s, const char *path)
+{
+    if (state_refusal(s, path, "saved")) return 1;
+    SESSION_TRY
+    rt_sync(s->stream);
+    const char fixed = s->p.whichMatrixFixed;
+    StateMeta meta; memset(&meta, 0, sizeof(meta));
+    GenScalars gs[2]; memset(gs, 0, sizeof(gs));
+    HostSampler *hs[2] = {&s->A, &s->P};
+    for (int w = 0; w < 2; ++w) {
+        if (fixed == "AP"[w]) continue;
+        read_gs(s, *hs[w]); gs[w] = *s->hGs;
+        if (gs[w].error) return fail("this session's device state carries an error code; its state cannot be saved");
+        meta.samp[w].present = 1; meta.samp[w].nAtoms = hs[w]->nAtoms; meta.samp[w].avgQueue = hs[w]->avgQueue; meta.samp[w].anneal = hs[w]->anneal;
+    }
+    meta.phase = (uint32_t)s->posPhase; meta.nextIter = s->posNext;
+    meta.seeder0 = s->seeder.s0; meta.seeder1 = s->seeder.s1; meta.runnerRng = s->runnerRng; meta.totalUpdates = s->totalUpdates;
+    meta.samplerSeconds = s->samplerSeconds; meta.elapsedSeconds = now_s() - s->startTime;
+    meta.statUpdates = s->statUpdates; meta.pumpUpdates = s->pumpUpdates; meta.nSnap[0] = s->nSnap[0]; meta.nSnap[1] = s->nSnap[1];
+    meta.nHistory = (uint32_t)s->chisqHist.size(); meta.genScalarsBytes = (uint32_t)sizeof(GenScalars);
+    meta.nSeedFifo = s->seedFifo.size() - s->seedHead;
+    uint64_t fp[FP_N]; state_fingerprint(s, fp);
+    StateHostArrays ha = {s->seedFifo.data() + s->seedHead, {s->snapA[0].data(), s->snapA[1].data()}, {s->snapP[0].data(), s->snapP[1].data()},
+                          s->chisqHist.data(), s->atomHistA.data(), s->atomHistP.data()};
+    const std::vector<cgstate::Section> secs = state_sections(s, fp, &meta, gs, ha);
+    StateStaging staging;
+    cgstate::Writer out(path);
+    out.write(secs, staging.p, STATE_STAGING_BYTES, [&](const cgstate::Section &sec, uint64_t off, size_t n, void *buf) {
+        rt_d2h(buf, (const char *)sec.dev + off, n, s->stream); rt_sync(s->stream); });
+    SESSION_END
+}
+
+int cogaps_session_load_state(cogaps_session *s, const char *path)
+{
+    if (state_refusal(s, path, "replaced")) return 1;
+    if (!s->ownsStream) return fail("this session belongs to a batch: load the state first, then create the batch");
+    SESSION_TRY
+    rt_sync(s->stream);
+    // ---- everything is validated before anything of the session is overwritten ----
+    StateStaging staging;
+    cgstate::Reader in(path, staging.p, STATE_STAGING_BYTES);
+    const std::string name = std::string("state file: ") + path;
+    uint64_t fpFile[FP_N], fpMine[FP_N];
+    const cgstate::TableEntry *e = in.find(SEC_FINGERPRINT);
+    if (!e || e->bytes != sizeof(fpFile)) return fail(name + " is corrupt: it has no fingerprint section of this version's size");
+    in.read(*e, 0, fpFile, sizeof(fpFile));
+    state_fingerprint(s, fpMine);
+    for (int i = 0; i < FP_N; ++i)
+        if (fpFile[i] != fpMine[i]) return fail(name + " does not belong to this session: " + FP_NAMES[i] + " differs (file " + fp_text(i, fpFile[i]) + ", session " + fp_text(i, fpMine[i]) + ")");
+    StateMeta meta;
+    e = in.find(SEC_META);
+    if (!e || e->bytes != sizeof(meta)) return fail(name + " is corrupt: it has no meta section of this version's size");
+    in.read(*e, 0, &meta, sizeof(meta));
+    const char fixed = s->p.whichMatrixFixed;
+    HostSampler *hs[2] = {&s->A, &s->P};
+    GenScalars gs[2]; memset(gs, 0, sizeof(gs));
+    const uint64_t na = (uint64_t)s->nGenes * s->K;
+    bool sane = meta.phase >= 1 && meta.phase <= 3 && meta.genScalarsBytes == sizeof(GenScalars) && meta.nSeedFifo < ((uint64_t)1 << 32)
+                && (na == 0 || (meta.nSnap[0] < ((uint64_t)1 << 40) / na && meta.nSnap[1] < ((uint64_t)1 << 40) / na));
+    for (int w = 0; w < 2 && sane; ++w) {
+        if (meta.samp[w].present != (fixed == "AP"[w] ? 0u : 1u)) { sane = false; break; }
+        if (!meta.samp[w].present) continue;
+        e = in.find(SEC_SAMPLER + 0x100u * (uint32_t)w + SS_GS);
+        if (!e || e->bytes != sizeof(GenScalars)) { sane = false; break; }
+        in.read(*e, 0, &gs[w], sizeof(GenScalars));
+        const GenScalars &g = gs[w];
+        sane = g.error == 0 && g.handleHi < 0x7FFFFFF0u && g.nAtoms <= g.handleHi && g.freeCount <= g.handleHi && g.eraseCount == 0;
+    }
+    if (!sane) return fail(name + " is corrupt: its counters contradict each other or this session");
+    std::vector<uint64_t> fifo(meta.nSeedFifo); std::vector<float> snapA[2], snapP[2], chisq(meta.nHistory); std::vector<uint32_t> histA(meta.nHistory), histP(meta.nHistory);
+    for (int w = 0; w < 2; ++w) { snapA[w].resize((size_t)meta.nSnap[w] * na); snapP[w].resize((size_t)meta.nSnap[w] * s->nSamples * s->K); }
+    StateHostArrays ha = {fifo.data(), {snapA[0].data(), snapA[1].data()}, {snapP[0].data(), snapP[1].data()}, chisq.data(), histA.data(), histP.data()};
+    std::vector<cgstate::Section> secs = state_sections(s, fpFile, &meta, gs, ha);
+    if (secs.size() != in.tab.size()) return fail(name + " holds " + std::to_string(in.tab.size()) + " sections where this session's state has " + std::to_string(secs.size()));
+    for (const cgstate::Section &sec : secs) {
+        e = in.find(sec.id);
+        if (!e || e->bytes != sec.bytes) return fail(name + ": section " + std::to_string(sec.id) + (e ? " has " + std::to_string(e->bytes) + " bytes" : std::string(" is missing")) + " where this session's state has " + std::to_string(sec.bytes) + " bytes");
+    }
+    // capacities are not state: room for the file's atoms first (the session's own atoms move with the arrays)
+    for (int w = 0; w < 2; ++w) if (meta.samp[w].present) grow_atoms(s, *hs[w], gs[w].handleHi);
+    secs = state_sections(s, fpFile, &meta, gs, ha);      // (the same sizes; the arrays may have moved)
+    // ---- from here on the session is overwritten; a failure leaves a state that is no state of any chain ----
+    try {
+        for (const cgstate::Section &sec : secs) {
+            e = in.find(sec.id);
+            if (sec.id == SEC_FINGERPRINT || sec.id == SEC_META || (sec.id >= SEC_SAMPLER && ((sec.id & 0xFFu) == SS_GS))) continue;      // read above
+            if (sec.host) { if (sec.bytes) in.read(*e, 0, sec.host, (size_t)sec.bytes); continue; }
+            for (uint64_t off = 0; off < sec.bytes; ) {
+                const size_t n = (size_t)std::min<uint64_t>(STATE_STAGING_BYTES, sec.bytes - off);
+                in.read(*e, off, staging.p, n);
+                rt_h2d((char *)sec.dev + off, staging.p, n, s->stream); rt_sync(s->stream);      // (the buffer is reused by the next piece)
+                off += n;
+            }
+        }
+        for (int w = 0; w < 2; ++w) {
+            if (!meta.samp[w].present) continue;
+            HostSampler &h = *hs[w]; SamplerDev &d = h.d;
+            gs[w].traceOn = gs[w].traceCount = gs[w].traceCap = gs[w].traceBatchCount = 0;
+            *s->hGs = gs[w];
+            rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream); rt_sync(s->stream);
+            // what a batch of this session left for its own epoch only: cleared, as a fresh session has it
+            rt_memset(d.rowStamp, 0, (size_t)d.M * 8, s->stream); rt_memset(d.atomStamp, 0, (size_t)d.atomCap * 8, s->stream);
+            rt_memset(d.gapStamp, 0, ((size_t)d.atomCap + 1) * 8, s->stream); rt_memset(d.inlineStamp, 0, (size_t)d.atomCap * 8, s->stream);
+            rt_memset(d.atomDest, 0, (size_t)d.atomCap * 8, s->stream);
+            rt_memset(h.chainGrans, 0, (size_t)d.queueCap * CHAIN_GRAN_STRIDE * 8, s->stream); rt_memset(d.grans, 0, (size_t)d.queueCap * 64 * 8, s->stream);
+            h.nAtoms = meta.samp[w].nAtoms; h.avgQueue = meta.samp[w].avgQueue; h.anneal = meta.samp[w].anneal;
+            h.stepsPerBatch = 0.f;      // (the chunk predictor starts over; no result depends on it)
+        }
+        if (!s->p.useSparseOptimization && fixed == 'N') do_sync(s, s->A, s->P);      // A's A*P cache: the transpose of P's
+        rt_sync(s->stream);
+    } catch (...) { s->poisoned = true; throw; }
+    s->seedFifo.swap(fifo); s->seedHead = 0;
+    s->seeder.s0 = meta.seeder0; s->seeder.s1 = meta.seeder1; s->runnerRng = meta.runnerRng; s->totalUpdates = meta.totalUpdates;
+    s->samplerSeconds = meta.samplerSeconds; s->startTime = now_s() - meta.elapsedSeconds;
+    s->statUpdates = meta.statUpdates; s->pumpUpdates = meta.pumpUpdates;
+    for (int w = 0; w < 2; ++w) { s->nSnap[w] = meta.nSnap[w]; s->snapA[w].swap(snapA[w]); s->snapP[w].swap(snapP[w]); }
+    s->chisqHist.swap(chisq); s->atomHistA.swap(histA); s->atomHistP.swap(histP);
+    s->posPhase = (int)meta.phase; s->posNext = meta.nextIter;
+    SESSION_END
+}
+
+int cogaps_session_run_to_end(cogaps_session *s, const char *statePath, uint32_t interval, cogaps_result *out)
+{
+    if (!s || !out) return fail("null argument");
+    const uint32_t nIter = s->p.nIterations;
+    uint32_t sinceSave = 0;
+    while (s->posPhase < 3) {
+        const int phase = s->posPhase; const uint32_t next = s->posNext;
+        if (next >= nIter) { set_position(s, phase, nIter); continue; }      // (nothing left of this phase)
+        uint32_t n = nIter - next;
+        if (statePath && interval) n = std::min(n, interval - sinceSave);
+        if (cogaps_session_run_iterations(s, phase, next, n, nullptr)) {
+            // the interrupt hook is polled at the head of an iteration, before anything of it is drawn: the state is that of the position
+            if (statePath && g_last_error == "interrupted" && cogaps_session_save_state(s, statePath)) return fail("interrupted, and the state could not be saved: " + g_last_error);
+            return 1;
+        }
+        sinceSave += n;
+        if (statePath && interval && sinceSave >= interval) { if (cogaps_session_save_state(s, statePath)) return 1; sinceSave = 0; }
+    }
+    if (statePath && cogaps_session_save_state(s, statePath)) return 1;      // the complete run: position 3
+    return cogaps_session_finish(s, out);
 }
 
 int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)

@@ -349,6 +349,46 @@ int cogaps_session_get_atoms(cogaps_session *s, char which, uint64_t *pos, float
 int cogaps_session_dims(cogaps_session *s, char which, uint32_t *M, uint32_t *N, uint32_t *K);
 int cogaps_session_avg_queue(cogaps_session *s, char which, float *avg);
 int cogaps_session_finish(cogaps_session *s, cogaps_result *out);
+/* ------------------------------------------------------------------------------------------------
+ * State file: stop a run and go on later -- in another process, another GPU allocation -- with THE SAME CHAIN, BIT FOR BIT.  This is the
+ * library's own file, not the reference's Archive checkpoint: cogaps_checkpoints_enabled() stays 0 and checkpointInFile stays refused.
+ *
+ * Position: the session records where it stands -- phase 1 (equilibration) or 2 (sampling) and the next iteration of that phase; phase 3:
+ * both phases complete.  cogaps_session_run_iterations and cogaps_batch_run_iterations advance it; a caller that steps with
+ * cogaps_session_iterate / _update keeps its own book, and the position stays where the last run_iterations left it.
+ *
+ * save_state writes what changes while a chain runs -- per sampler the factor matrix (the sparse model's row copy, flags and lookup
+ * tables), the atomic domain and the generator's scalars, ONE sampler's A*P cache (the other's is its transpose); per session the host
+ * generators with the seeder's look-ahead, statistics accumulators, PUMP, snapshots, histories, counters, times, the position -- and
+ * nothing of the data, the lookup tables or a capacity: a sparse-model file holds no array of size genes x samples, a dense-model file
+ * one.  It is taken BETWEEN TWO ITERATIONS (after run_iterations / iterate; between two cogaps_batch_run_iterations calls for a batch
+ * member), where the queue and the erase cache are empty and the two A*P caches agree.  The file is little-endian: magic, format
+ * version, section table, payload, a 64-bit checksum; it is written to path + ".tmp", flushed and renamed, so a save that fails leaves
+ * the previous file intact.  Device arrays pass through one 4 MiB pinned buffer.
+ *
+ * load_state: create a session the ordinary way -- any creation entry, the caller's data and parameters -- then load.  The file is
+ * validated completely before anything is overwritten: magic, version, length, checksum, the fingerprint, every section's size.  The
+ * fingerprint names what file and session must share: model, nGenes, nSamples, nPatterns, seed, nIterations, alphaA/P, maxGibbsMassA/P,
+ * outputFrequency, snapshotFrequency / snapshotPhase, takePumpSamples, pumpThreshold, whichMatrixFixed and a hash of fixedPatterns,
+ * reductionMode / mathMode, the data-derived lambda, maxGibbsMass, dataSparsity / number of packed values, and a 64-bit digest of the
+ * data computed on the device (csrc/state_digest.h) at the session's first save or load.  A refused load names the first differing item
+ * and leaves the session untouched.  The loading session's capacity (grown if the file's atoms need it), launch form (chained or two
+ * launches, graphs, generator window) and later membership of a batch are its own: none is state.  A session that already belongs to a
+ * batch refuses to load (load first, then create the batch); a session ended by a device error refuses both calls.  Both synchronise the
+ * session's stream (a batch member's is the batch's).  After a load, samplerSeconds continues from the saved value and
+ * totalRunningTime is the saved elapsed time plus the time since the load; every other result field is the uninterrupted run's.
+ *
+ * run_to_end: everything that remains of the two phases from the session's position, then cogaps_session_finish.  With statePath != NULL
+ * the state is saved after every `interval` iterations (0: not on the way), once more when both phases are complete (position 3), and
+ * -- the interrupt hook is polled at the head of an iteration, before anything of it is drawn -- before the call fails with
+ * "interrupted": a later load continues at exactly that iteration.
+ * ---------------------------------------------------------------------------------------------- */
+int cogaps_session_position(cogaps_session *s, int *phase, uint32_t *nextIter);
+int cogaps_session_save_state(cogaps_session *s, const char *path);
+int cogaps_session_load_state(cogaps_session *s, const char *path);
+int cogaps_session_run_to_end(cogaps_session *s, const char *statePath, uint32_t interval, cogaps_result *out);
+/* test hook: the fingerprint's data digest, computed anew by every call (the same for every input form of a matrix) */
+int cogaps_session_debug_data_digest(cogaps_session *s, uint64_t *digest);
 /* counters for the roofline report: algorithmic bytes moved by the evaluation kernel so far, number
  * of evaluation launches, batches generated, and the accumulated HIP-event time of each kernel */
 typedef struct cogaps_perf {
