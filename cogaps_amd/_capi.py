@@ -30,7 +30,7 @@ class CogapsParamsC(C.Structure):
         ("fixedRows", C.c_uint32), ("workerID", C.c_uint32), ("runningDistributed", C.c_int32),
         ("device", C.c_int32), ("interrupt", INTERRUPT_FN), ("interruptArg", C.c_void_p),
         ("snapshotPhase", C.c_int32), ("pumpThreshold", C.c_int32), ("fixedCols", C.c_int32),
-        ("reductionMode", C.c_int32), ("mathMode", C.c_int32),
+        ("reductionMode", C.c_int32), ("mathMode", C.c_int32), ("sampler", C.c_int32),
     ]
 
 
@@ -106,6 +106,8 @@ MATH_PORTABLE, MATH_GLIBC_FMA, MATH_GLIBC_SSE2 = 0, 1, 2     # cogaps_params.mat
 _REDUCE = {"lanes": REDUCE_LANES, "seq": REDUCE_SEQ}
 _MATH = {"portable": MATH_PORTABLE, "glibc-fma": MATH_GLIBC_FMA, "glibc-sse2": MATH_GLIBC_SSE2}
 _PUMP = {"unique": 0, "cut": 1}
+SAMPLER_ASYNC, SAMPLER_SEQUENTIAL = 0, 1                     # cogaps_params.sampler
+_SAMPLER = {"async": SAMPLER_ASYNC, "sequential": SAMPLER_SEQUENTIAL}
 
 ERR_GENERIC, ERR_OUT_OF_DEVICE_MEMORY, ERR_OUT_OF_HOST_MEMORY = 1, 2, 3      # cogaps_last_error_code()
 
@@ -266,7 +268,8 @@ def make_params(L, nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, n
                 fixedPatterns=None, sparseOptimization=False, asynchronousUpdates=True,
                 messages=False, workerID=1, device=-1, takePumpSamples=False,
                 checkpointInterval=0, nSnapshots=0, snapshotPhase="sampling", snapshotFrequency=None,
-                pumpThreshold="unique", reductionMode="lanes", mathMode="portable", runningDistributed=False, interrupt=None):
+                pumpThreshold="unique", reductionMode="lanes", mathMode="portable", runningDistributed=False, interrupt=None,
+                sampler="async"):
     p = CogapsParamsC()
     L.cogaps_default_params(C.byref(p))
     p.nPatterns, p.nIterations, p.seed = int(nPatterns), int(nIterations), int(seed)
@@ -288,6 +291,9 @@ def make_params(L, nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, n
     p.pumpThreshold = _PUMP[pumpThreshold] if isinstance(pumpThreshold, str) else int(pumpThreshold)
     p.reductionMode = _REDUCE[reductionMode] if isinstance(reductionMode, str) else int(reductionMode)
     p.mathMode = _MATH[mathMode] if isinstance(mathMode, str) else int(mathMode)
+    if isinstance(sampler, str) and sampler not in _SAMPLER:
+        raise ValueError('sampler must be "async" or "sequential", not %r' % (sampler,))
+    p.sampler = _SAMPLER[sampler] if isinstance(sampler, str) else int(sampler)      # (an integer reaches the library as it is: it refuses what it does not know)
     keep = []
     if interrupt is not None:
         # cogaps_params.interrupt: a callable without arguments, polled at the head of every iteration; a true value ends the run

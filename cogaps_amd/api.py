@@ -53,7 +53,7 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
 def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputFrequency=1000, uncertainty=None,
            checkpointOutFile="gaps_checkpoint.out", checkpointInterval=0, checkpointInFile=None, transposeData=False,
            BPPARAM=None, workerID=1, asynchronousUpdates=True, nSnapshots=0, snapshotPhase="sampling", device=-1,
-           stateFile=None, stateInterval=0, resume=False, **extra):
+           stateFile=None, stateInterval=0, resume=False, sampler=None, **extra):
     if params is None:
         params = CogapsParams(**({} if nPatterns is None else {"nPatterns": nPatterns}))
     else:
@@ -62,6 +62,8 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
             params.setParam("nPatterns", nPatterns)
     for k, v in extra.items():                                   # parseExtraParams: named CogapsParams slots in ...
         params.setParam(k, v)
+    if sampler is not None:                                      # "async" | "sequential" (CogapsParams.sampler; include/cogaps_hip.h)
+        params.setParam("sampler", sampler)
     params.validate()
     path = data if isinstance(data, str) else None
     subset = params.subsetIndices is not None and params.subsetDim > 0     # a distributed worker's call: the run takes these rows / columns only
@@ -115,7 +117,7 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
         unc = np.ascontiguousarray(unc, dtype=np.float32)
     check_inputs(data, unc, params, snapshotPhase, nSnapshots, checkpointInFile, nThreads)
     if not asynchronousUpdates:
-        raise ValueError("asynchronousUpdates=FALSE selects the reference's sequential sampler; this library is the asynchronous one")
+        raise ValueError("asynchronousUpdates=FALSE is not taken here: the reference's sequential sampler is selected with sampler=\"sequential\"")
     if stateFile is None and (resume or stateInterval):
         raise ValueError("resume / stateInterval need a stateFile")
     if params.distributed is not None:
@@ -143,7 +145,7 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
                         whichMatrixFixed=params.whichMatrixFixed, **subset_kw,
                         fixedPatterns=params.fixedPatterns, sparseOptimization=params.sparseOptimization, messages=messages,
                         workerID=workerID, device=device, takePumpSamples=params.takePumpSamples,
-                        nSnapshots=nSnapshots, snapshotPhase=snapshotPhase,
+                        nSnapshots=nSnapshots, snapshotPhase=snapshotPhase, sampler=params.sampler,
                         **({} if stateFile is None else dict(stateFile=stateFile, stateInterval=stateInterval, resume=resume)))
     return CogapsResult(raw, params=params, geneNames=params.geneNames, sampleNames=params.sampleNames)
 

@@ -13,6 +13,7 @@
 #include "file_reader.h"
 #include "eval_kernel.h"
 #include "chain_kernel.h"
+#include "seq_kernel.h"
 #include "aux_kernels.h"
 #include "sparse_kernels.h"
 #include "sparse_build.h"
@@ -1182,10 +1183,15 @@ static uint32_t chunk_size(uint32_t C, const GenScalars *g, const uint32_t *nSte
 // evaluate) pairs are enqueued in chunks and the generator's progress word is read back per chunk;
 // pairs enqueued past the end are no-ops (the generator flushes the last erase cache and reports
 // qlen = 0).
+static int run_update_seq(cogaps_session *s, HostSampler &h, uint32_t nSteps);
 static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, uint32_t traceCap)
 {
     SamplerDev &d = h.d;
     if (s->poisoned) return fail("this session was ended by a device error in an earlier update; its chain cannot be continued");
+    if (s->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) {
+        if (traceCap) return fail("proposal traces belong to the asynchronous sampler's queue: a sequential session has none");
+        return run_update_seq(s, h, nSteps);
+    }
     UpdateInFlight inFlight(s->p.device);
     read_gs(s, h);
     if (h.traceCap < traceCap) {
@@ -1236,6 +1242,51 @@ static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, uint32
     }
     end_update(h, *s->hGs, nSteps);
     retune_window(s, h, h.stepsPerBatch);
+    return 0;
+}
+
+// ---- the sequential sampler (seq_kernel.h): SingleThreadedGibbsSampler::update ------------------------------------------------------
+// Arms sampler h for update(n): room for the atoms n births can add, progress and temperature in its scalars `g` (as read back; the
+// caller uploads them).  No seeder output is taken: the sampler's one generator lives in g.qrng since the session's creation.
+static void begin_update_seq(cogaps_session *s, HostSampler &h, GenScalars &g, uint32_t n)
+{
+    rt_owner_scope owner(&s->deviceBytes);
+    grow_atoms(s, h, g.nAtoms + n + 1024u);
+    g.annealTemp = h.anneal;
+    g.nSteps = n; g.nDone = 0; g.nBatches = 0; g.updateFlushed = n == 0 ? 1u : 0u; g.qlen = 0;
+    g.traceOn = 0; g.traceCount = 0; g.traceBatchCount = 0;
+    h.updLaunches = 0;
+}
+static uint32_t seq_launches(uint32_t nSteps) { return (nSteps + (uint32_t)SEQ_STEPS_PER_LAUNCH - 1u) / (uint32_t)SEQ_STEPS_PER_LAUNCH; }
+// workgroup size of a sampler's sequential launch: the reduction's width up to 1024 threads; the verification mode's term scratch holds 256
+static uint32_t seq_block(const SamplerDev &d) { return std::min<uint32_t>(d.redW, d.seq ? (uint32_t)EVAL_SEQ_BS : 1024u); }
+// One workgroup runs the whole update, SEQ_STEPS_PER_LAUNCH steps per launch; the number of launches is known beforehand, so they are
+// enqueued at once and the scalars are read back once.
+static int run_update_seq(cogaps_session *s, HostSampler &h, uint32_t nSteps)
+{
+    SamplerDev &d = h.d;
+    read_gs(s, h);
+    begin_update_seq(s, h, *s->hGs, nSteps);
+    rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream);
+    rt_sync(s->stream);
+    if (nSteps == 0) return 0;
+    sync_record(s, h);
+    h.chain = false;
+    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
+    const uint32_t bs = seq_block(d);
+    for (uint32_t k = seq_launches(nSteps); k; --k) {
+        const int slot = timing_slot(s, h, EV_EVAL, 0);
+        if (d.seq) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, seq_update_kernel<true>, 1, bs, rec);
+        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, seq_update_kernel<false>, 1, bs, rec);
+        h.evalLaunches++; h.updLaunches++;
+    }
+    read_gs(s, h);
+    timing_resolve(s, ~0ull);
+    if (s->hGs->error || !s->hGs->updateFlushed) {
+        s->poisoned = true;
+        return fail(std::string("device error code ") + std::to_string(s->hGs->error) + " in sampler " + h.name + " (sequential sampler)");
+    }
+    h.nAtoms = s->hGs->nAtoms;      // (avgQueue stays 0: SingleThreadedGibbsSampler::getAverageQueueLength)
     return 0;
 }
 
@@ -1320,6 +1371,7 @@ void cogaps_default_params(cogaps_params *p)
     p->nPatterns = 3; p->nIterations = 1000; p->maxThreads = 1; p->outputFrequency = 500;   // GapsParameters.h:79-111
     p->alphaA = 0.01f; p->alphaP = 0.01f; p->maxGibbsMassA = 100.f; p->maxGibbsMassP = 100.f;
     p->printMessages = 0; p->asynchronousUpdates = 1; p->whichMatrixFixed = 'N'; p->workerID = 1; p->device = -1;
+    p->sampler = COGAPS_SAMPLER_ASYNC;
 }
 const char *cogaps_last_error(void) { return g_last_error.c_str(); }
 int cogaps_last_error_code(void) { return g_last_code; }
@@ -1369,6 +1421,9 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // distributed worker call (runningDistributed, i.e. subsetDim > 0 in cogaps_cpp, Cogaps.cpp:82) runs the asynchronous sampler anyway,
         // so that GWCoGAPS / scCoGAPS through the real R package reach this library.  Everywhere else FALSE is refused.
         if (!p.asynchronousUpdates && !p.runningDistributed) { fail("asynchronousUpdates=FALSE (SingleThreadedGibbsSampler) is not part of this library"); return nullptr; }
+        // The sequential sampler (seq_kernel.h) is chosen by `sampler` alone: asynchronousUpdates keeps the meaning above.
+        if (p.sampler != COGAPS_SAMPLER_ASYNC && p.sampler != COGAPS_SAMPLER_SEQUENTIAL) { fail("sampler must be COGAPS_SAMPLER_ASYNC or COGAPS_SAMPLER_SEQUENTIAL"); return nullptr; }
+        if (p.sampler == COGAPS_SAMPLER_SEQUENTIAL && p.useSparseOptimization) { fail("sampler = COGAPS_SAMPLER_SEQUENTIAL supports the dense model only: the SparseNormalModel evaluation of the sequential kernel is missing (useSparseOptimization must be 0)"); return nullptr; }
         if (p.nPatterns == 0 || nrow == 0 || ncol == 0) { fail("empty problem"); return nullptr; }
         if (p.whichMatrixFixed != 'N' && p.whichMatrixFixed != 'A' && p.whichMatrixFixed != 'P') { fail("whichMatrixFixed must be 'N', 'A' or 'P'"); return nullptr; }
         if (p.reductionMode != COGAPS_REDUCE_LANES && p.reductionMode != COGAPS_REDUCE_SEQ) { fail("reductionMode must be COGAPS_REDUCE_LANES or COGAPS_REDUCE_SEQ"); return nullptr; }
@@ -1821,9 +1876,11 @@ static void multi_launch_pair(cogaps_batch *b, int w, const MultiGeom &g, int sl
 }
 
 // AsynchronousGibbsSampler::update of sampler `w` (0 = A, 1 = P) of every chain, nSteps[c] proposals each
+static int run_update_multi_seq(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps);
 static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps)
 {
     const uint32_t C = (uint32_t)b->ss.size();
+    if (b->ss[0]->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) return run_update_multi_seq(b, w, nSteps);
     UpdateInFlight inFlight(b->ss[0]->p.device);      // (a one-chain session stepped beside the batch on the same GPU keeps two launches per batch meanwhile)
     rt_alloc_scope allocOn(b->stream);
     for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
@@ -1895,6 +1952,44 @@ static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> 
     return 0;
 }
 
+// The sequential sampler's update of sampler `w` of every chain: ONE launch of a workgroup per chain per SEQ_STEPS_PER_LAUNCH steps of the
+// longest update; a chain whose update is over leaves at once and nobody waits for anybody.
+static int run_update_multi_seq(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps)
+{
+    const uint32_t C = (uint32_t)b->ss.size();
+    rt_alloc_scope allocOn(b->stream);
+    for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
+    rt_sync(b->stream);
+    uint32_t longest = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+        HostSampler &h = bpick(b, c, w);
+        begin_update_seq(b->ss[c], h, b->hGs[c], nSteps[c]);
+        rt_h2d(h.d.gs, &b->hGs[c], sizeof(GenScalars), b->stream);
+        longest = std::max(longest, nSteps[c]);
+    }
+    bool changed = false;
+    for (uint32_t c = 0; c < C; ++c) if (memcmp(&b->host[w][c], &bpick(b, c, w).d, sizeof(SamplerDev)) != 0) { b->host[w][c] = bpick(b, c, w).d; changed = true; }
+    if (changed) rt_h2d(b->dev[w], b->host[w].data(), (size_t)C * sizeof(SamplerDev), b->stream);
+    rt_sync(b->stream);
+    if (longest == 0) return 0;
+    const SamplerDev CG_CONSTANT *arr = (const SamplerDev CG_CONSTANT *)b->dev[w];
+    const uint32_t bs = seq_block(bpick(b, 0, w).d);      // (equal reduction widths: checked at the batch's creation)
+    for (uint32_t k = seq_launches(longest); k; --k) {
+        const int slot = (b->timing && b->ev.room(1)) ? b->ev.take(EV_EVAL) : -1;
+        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slot, seq_update_kernel_multi, C, bs, arr);
+        b->launches[w]++; b->ord++;
+    }
+    for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
+    rt_sync(b->stream);
+    b->ev.drain([&](const EvSample &, float ms) { b->evalMs[w] += ms; b->evalTimed[w]++; });
+    for (uint32_t c = 0; c < C; ++c) {
+        const GenScalars &g = b->hGs[c];
+        if (g.error || !g.updateFlushed) { b->ss[c]->poisoned = true; return fail(std::string("device error code ") + std::to_string(g.error) + " in sampler " + (w ? 'P' : 'A') + " of chain " + std::to_string(c) + " (sequential sampler)"); }
+        bpick(b, c, w).nAtoms = g.nAtoms; bpick(b, c, w).chain = false;
+    }
+    return 0;
+}
+
 cogaps_batch *cogaps_batch_create(cogaps_session **sessions, uint32_t n)
 {
     cogaps_batch *b = nullptr;
@@ -1906,6 +2001,7 @@ cogaps_batch *cogaps_batch_create(cogaps_session **sessions, uint32_t n)
             if (!s) { fail("null session"); return nullptr; }
             if (!s->ownsStream) { fail("a session can be in one batch only"); return nullptr; }
             if (s->A.d.seq || s0->A.d.seq) { fail("the verification mode runs one chain at a time"); return nullptr; }
+            if (s->p.sampler != s0->p.sampler) { fail("the sessions of a batch must share the sampler: sequential and asynchronous chains cannot be mixed"); return nullptr; }
             // one launch geometry for all chains: the same model, reduction widths and slice counts (subsets of one job have them)
             if (s->p.useSparseOptimization != s0->p.useSparseOptimization || s->p.whichMatrixFixed != s0->p.whichMatrixFixed || s->p.device != s0->p.device
                 || s->A.d.redW != s0->A.d.redW || s->P.d.redW != s0->P.d.redW || ((s->A.d.Npad >> 2) + 511u) / 512u != ((s0->A.d.Npad >> 2) + 511u) / 512u
@@ -2425,6 +2521,7 @@ static int state_refusal(cogaps_session *s, const char *path, const char *what)
 {
     if (!s || !path) return fail("null argument");
     if (s->poisoned) return fail(std::string("this session was ended by a device error; its state cannot be ") + what);
+    if (s->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) return fail(std::string("a state file holds the asynchronous sampler's chain: the state of a sequential session (sampler = COGAPS_SAMPLER_SEQUENTIAL) cannot be ") + what);
     return 0;
 }
 
@@ -2569,6 +2666,7 @@ int cogaps_session_load_state(cogaps_session *s, const char *path)
 int cogaps_session_run_to_end(cogaps_session *s, const char *statePath, uint32_t interval, cogaps_result *out)
 {
     if (!s || !out) return fail("null argument");
+    if (statePath && state_refusal(s, statePath, "saved")) return 1;      // (before anything runs: a sequential session keeps no state file)
     const uint32_t nIter = s->p.nIterations;
     uint32_t sinceSave = 0;
     while (s->posPhase < 3) {

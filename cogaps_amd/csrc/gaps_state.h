@@ -97,7 +97,8 @@ struct GenScalars {
     unsigned long long prof[16];    // GEN_PROFILE builds: cycles per generator phase
 };
 
-enum GapsError { GAPS_OK = 0, GAPS_ERR_ATOM_CAP = 1, GAPS_ERR_QUEUE_CAP = 2, GAPS_ERR_ERASE_CAP = 3, GAPS_ERR_SPIN = 4 };
+enum GapsError { GAPS_OK = 0, GAPS_ERR_ATOM_CAP = 1, GAPS_ERR_QUEUE_CAP = 2, GAPS_ERR_ERASE_CAP = 3, GAPS_ERR_SPIN = 4,
+                 GAPS_ERR_DOMAIN = 5 /* sequential sampler: a drawn position lies past the last bin */ };
 
 #define GAPS_DEATH_PROB_PAD 1024u
 struct SamplerDev {

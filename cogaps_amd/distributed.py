@@ -11,8 +11,9 @@ subset per GPU.
   stitchTogether                   :226-278
 
 Differences from the reference, both documented in DESIGN.md: (1) the reference forces its sequential
-sampler inside workers (:28-29); this library is the asynchronous sampler, so each shard is an asynchronous
-chain (the per-shard oracle is the asynchronous reference run with the same dataIndicesSubset); (2) the
+sampler inside workers (:28-29); by default each shard here is an asynchronous chain (the per-shard oracle
+is the asynchronous reference run with the same dataIndicesSubset), and params.sampler = "sequential" runs
+both passes of every shard with the reference's worker sampler (csrc/seq_kernel.h; dense model); (2) the
 uniform partition uses numpy's generator, not R's sample(): results with explicitSets are comparable, the
 random partition is not.  The reference's quirk that the shared factor comes back all-zero from pass 2
 (:236-237, src/GapsRunner.cpp:301-306) is reproduced in Pmean/Amean; the consensus actually used is
@@ -463,6 +464,11 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
                   alphaP=params.alphaP, maxGibbsMassA=params.maxGibbsMassA, maxGibbsMassP=params.maxGibbsMassP,
                   transposeData=transposeData, sparseOptimization=params.sparseOptimization, device=device,
                   takePumpSamples=params.takePumpSamples, nSnapshots=nSnapshots, snapshotPhase=snapshotPhase)      # allParams reaches every worker unchanged (:12-35)
+
+    if getattr(params, "sampler", "async") != "async":
+        # both passes of every shard, the fixed-factor one included, run the chosen sampler; a rank's shards still run as batches (one
+        # launch with a workgroup per chain).  (Only passed on when chosen: another run_fn need not know the keyword.)
+        common["sampler"] = params.sampler
 
     def shape_of(i):
         """(genes, samples, sparse model, uncertainty given) of shard i, from the index sets alone"""

@@ -11,6 +11,9 @@ class CogapsParams:
         explicitSets=None, samplingAnnotation=None, samplingWeight=None, subsetIndices=None, subsetDim=0,
         geneNames=None, sampleNames=None, fixedPatterns=None, whichMatrixFixed="N", takePumpSamples=False,
         checkpointInterval=0, checkpointInFile="", checkpointOutFile="",
+        # no slot of the reference's class: which of its two samplers runs ("async": AsynchronousGibbsSampler; "sequential":
+        # SingleThreadedGibbsSampler, what the reference's distributed workers run -- dense model only)
+        sampler="async",
     )
 
     def __init__(self, **kwargs):
@@ -141,6 +144,8 @@ class CogapsParams:
                 raise ValueError("samplingWeight must be non-negative")
             if set(self.samplingWeight) != set(self.samplingAnnotation):
                 raise ValueError("names of samplingWeight must match the groups of samplingAnnotation")
+        if self.sampler not in ("async", "sequential"):
+            raise ValueError('sampler must be "async" or "sequential"')
         if self.fixedPatterns is not None and np.any(np.asarray(self.fixedPatterns) < 0):
             raise ValueError("fixedPatterns must be non-negative")
         return True

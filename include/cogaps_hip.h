@@ -90,7 +90,17 @@ typedef struct cogaps_params {
      * reference's atom histories, totalUpdates and statistics digit for digit (tests/test_gpu_parity.py). */
     int32_t reductionMode;
     int32_t mathMode;
+    /* ---- which of the reference's two samplers runs (GapsRunner.cpp:69-77) ------------------------------------------------
+     * COGAPS_SAMPLER_ASYNC (default): AsynchronousGibbsSampler.  COGAPS_SAMPLER_SEQUENTIAL: SingleThreadedGibbsSampler -- one
+     * generator per sampler, no queue; what every worker of the reference's GWCoGAPS / scCoGAPS runs (R/DistributedCogaps.R:28-29).
+     * One workgroup runs a whole update (csrc/seq_kernel.h); a cogaps_batch of sequential sessions is one launch with a workgroup
+     * per chain.  Dense model only (useSparseOptimization is refused); no state file (cogaps_session_save_state / _load_state and
+     * cogaps_session_run_to_end with a path are refused); averageQueueLengthA / P are 0; a batch cannot mix samplers.
+     * asynchronousUpdates keeps its meaning above and does NOT select this sampler.  Any other value is refused. */
+    int32_t sampler;
 } cogaps_params;
+#define COGAPS_SAMPLER_ASYNC 0
+#define COGAPS_SAMPLER_SEQUENTIAL 1
 #define COGAPS_REDUCE_LANES 0
 #define COGAPS_REDUCE_SEQ 1
 #define COGAPS_MATH_PORTABLE 0
