@@ -535,7 +535,11 @@ static void spb_sides(cogaps_session *s, uint32_t nrow, uint32_t ncol, bool majo
 struct SpbTemps {
     void *p[12] = {}; int n = 0;
     ~SpbTemps() { for (void *q : p) rt_free(q); }
-    template <class T> T *alloc(size_t count) { rt_owner_scope notTheSessions(nullptr); T *q = dalloc<T>(count); p[n++] = q; return q; }
+    template <class T> T *alloc(size_t count)
+    {
+        if (n == (int)(sizeof(p) / sizeof(p[0]))) throw std::runtime_error("internal: a build has more temporaries than SpbTemps holds");
+        rt_owner_scope notTheSessions(nullptr); T *q = dalloc<T>(count); p[n++] = q; return q;
+    }
     // one of the caller's arrays where the kernels read it: uploaded, or used where it is
     template <class T> const T *stage(const T *src, size_t count, bool onDevice, rt_stream_t stream)
     {
@@ -547,32 +551,147 @@ struct SpbTemps {
     uint32_t *err() { return alloc<uint32_t>(4); }      // the error word, the two ordered sums
 };
 
-// Both samplers of a sparse-model session from a compressed-sparse matrix (sparse_build.h), built on the device: the caller's matrix
-// (cogaps_session_create_sparse) or the dense input's entries > 0 (build_samplers_dense_input).  No nrow x ncol array exists on either side.
-static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
+// A sparse-model matrix in device memory as the one builder reads it: a plain description that owns nothing.  The arrays are a
+// caller's, staged for one session (build_samplers_sparse_input / _coo_input), or a cogaps_device_matrix's; either way they have been
+// through spb_compressed or spb_triplets -- checked, triplets resolved into keep[] -- before anything is built from them.
+struct SpbMatrix {
+    uint32_t nrow = 0, ncol = 0; uint64_t nnz = 0;
+    bool coo = false, majorIsRow = true;
+    const uint64_t *indptr = nullptr; const uint32_t *indices = nullptr;      // compressed: [nMajor + 1], [nnz]
+    const uint32_t *rows = nullptr, *cols = nullptr;                          // triplets: [nnz]
+    const unsigned long long *keep = nullptr;                                 // triplets: bit k = entry k is the latest of its position and > 0
+    const float *values = nullptr;
+    uint32_t nMajor() const { return majorIsRow ? nrow : ncol; }
+    uint32_t nMinor() const { return majorIsRow ? ncol : nrow; }
+};
+static uint32_t entry_grid(uint64_t n, unsigned computeUnits, uint32_t bs)
 {
-    const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
-    uint64_t nnz = 0;
-    if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, s->stream); rt_sync(s->stream); } else nnz = m.indptr[nMajor];
-    if (nnz >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
-    if (nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
-    SpbTemps tmp;
-    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz;
-    in.indptr = tmp.stage(m.indptr, (size_t)nMajor + 1, m.onDevice != 0, s->stream);
-    in.indices = tmp.stage(m.indices, nnz, m.onDevice != 0, s->stream); in.values = tmp.stage(m.values, nnz, m.onDevice != 0, s->stream);
-    uint32_t *err = tmp.err();
-    SpbSide side[2];
-    HostSampler *hs[2] = {&s->A, &s->P};
-    spb_sides(s, m.nrow, m.ncol, m.majorIsRow != 0, side, hs);
-    const uint32_t sliceGrid = (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
-    RT_LAUNCH(spb_validate_count_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1], err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, s->stream); rt_sync(s->stream);
+    // grid-stride over the entries: enough workgroups to fill the device, never more than the entries need (at least one)
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + bs - 1) / bs, (uint64_t)computeUnits * 8u));
+}
+static void spb_check_entries(uint64_t n)
+{
+    if (n >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+}
+// What a caller's sparse matrix is refused for before anything else is looked at (null: nothing)
+static const char *sparse_args_refusal(const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo)
+{
+    if (sp) return sp->indptr ? nullptr : "null argument: indptr";
+    if (!coo) return nullptr;
+    if (coo->nnz >= 0xFFFFFFFFull) return "triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)";
+    if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) return "null argument: rows / cols / values";
+    return nullptr;
+}
+
+// The caller's compressed matrix, checked (sparse_build.h, spb_validate_kernel), as d.  place(array, count) puts one of the caller's
+// arrays where the kernels read it and says where that is: staged for the call, or copied into a handle's own memory.
+template <class Place> static void spb_compressed(SpbMatrix &d, const cogaps_sparse_matrix &m, rt_stream_t stream, Place &&place)
+{
+    d.nrow = m.nrow; d.ncol = m.ncol; d.coo = false; d.majorIsRow = m.majorIsRow != 0;
+    const uint32_t nMajor = d.nMajor();
+    if (m.onDevice) { rt_d2h(&d.nnz, m.indptr + nMajor, 8, stream); rt_sync(stream); } else d.nnz = m.indptr[nMajor];
+    spb_check_entries(d.nnz);
+    if (d.nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
+    d.indptr = place(m.indptr, (size_t)nMajor + 1); d.indices = place(m.indices, (size_t)d.nnz); d.values = place(m.values, (size_t)d.nnz);
+    SpbTemps tmp; uint32_t *err = tmp.err();
+    SpbIn in; in.nMajor = nMajor; in.nMinor = d.nMinor(); in.nnz = d.nnz; in.indptr = d.indptr; in.indices = d.indices; in.values = d.values;
+    RT_LAUNCH(spb_validate_kernel, (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, in, err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
     if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
     if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
     if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
+}
+
+// The caller's triplets, checked and resolved (sparse_build.h, passes 1 to 4 of its second half), as d: keep -- nnz / 64 + 1 words, the
+// caller's to own -- gets one bit per entry.  The present flags with their prefix counts and pointers and the winner indices are
+// temporaries of this call: O(nnz + nrow x ncol / 64 bits).
+template <class Place> static void spb_triplets(SpbMatrix &d, const cogaps_coo_matrix &m, unsigned long long *keep, unsigned computeUnits, rt_stream_t stream, Place &&place)
+{
+    d.keep = keep;
+    d.nrow = m.nrow; d.ncol = m.ncol; d.coo = true; d.majorIsRow = true; d.nnz = m.nnz;
+    d.rows = place(m.rows, (size_t)d.nnz); d.cols = place(m.cols, (size_t)d.nnz); d.values = place(m.values, (size_t)d.nnz);
+    SpbTemps tmp; uint32_t *err = tmp.err();
+    CooIn in; in.nrow = d.nrow; in.ncol = d.ncol; in.nnz = d.nnz; in.rows = d.rows; in.cols = d.cols; in.values = d.values;
+    SpbSide pres; pres.M = d.nrow; pres.Wn = d.ncol / 64u + 1u; pres.swap = 0u; pres.vals = nullptr;
+    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
+    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
+    const uint32_t grid = entry_grid(d.nnz, computeUnits, COO_BS), vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
+    RT_LAUNCH(coo_present_kernel, grid, COO_BS, stream, in, pres, err);
+    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
+    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
+    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
+    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, pres.ptr, pres.M);
+    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
+    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, stream); rt_sync(stream);
+    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
+    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, stream, in, pres, winner);
+    RT_LAUNCH(coo_keep_bits_kernel, grid, COO_BS, stream, in, pres, (const uint32_t *)winner, keep);
+    rt_sync(stream);
+}
+
+// Both samplers of a sparse-model session from a checked matrix in device memory, with or without a subset of its rows or columns
+// (sparse_build.h, the map and the mapped passes): THE builder of the sparse model, whatever form the input had.  subset: subsetData's
+// 1-based indices, or null -- also for a caller that has applied them already.  One read of the entries per mapped pass; the session's
+// allocations are those of any sparse-model session, the temporaries (the subset's indices, counts, cursors, list) O(dim + n).  Nothing
+// is uploaded but the subset's indices.
+static void build_samplers_device_matrix(cogaps_session *s, const SpbMatrix &dm, const std::vector<uint32_t> *subset)
+{
+    const cogaps_params &p = s->p;
+    const bool subsetRows = subset && (p.subsetGenes != 0) == (p.transposeData == 0);
+    const uint32_t nIdx = subset ? (uint32_t)subset->size() : 0u;
+    const uint32_t nrow = subset && subsetRows ? nIdx : dm.nrow, ncol = subset && !subsetRows ? nIdx : dm.ncol;
+    SpbTemps tmp;
+    SpbSide side[2];
+    HostSampler *hs[2] = {&s->A, &s->P};
+    spb_sides(s, nrow, ncol, dm.majorIsRow, side, hs);
+    SpbMap mp; mp.start = mp.list = nullptr; mp.onMajor = subsetRows == dm.majorIsRow ? 1u : 0u;
+    if (subset) {
+        const uint32_t dim = subsetRows ? dm.nrow : dm.ncol;
+        const uint32_t *indices = tmp.stage(subset->data(), nIdx, false, s->stream);
+        uint32_t *start = tmp.alloc<uint32_t>((size_t)dim + 1), *cursor = tmp.alloc<uint32_t>(dim), *list = tmp.alloc<uint32_t>(nIdx);
+        const uint32_t mapGrid = entry_grid(nIdx, s->computeUnits, SPB_MAP_BS);
+        RT_LAUNCH(spb_map_count_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, start);
+        RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, start, dim);
+        RT_LAUNCH(spb_map_fill_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, (const uint32_t *)start, cursor, list);
+        mp.start = start; mp.list = list;
+    }
+    SpbIn in; CooIn cin;
+    in.nMajor = dm.nMajor(); in.nMinor = dm.nMinor(); in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
+    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
+    const uint32_t sliceGrid = (in.nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, s->computeUnits, COO_BS);
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, s->stream, cin, dm.keep, mp, side[0], side[1]);
+    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
+    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    if (subset) {
+        // an entry has as many images as its index repeats in the subset: the total in 64 bits before the 32-bit scan (without a
+        // subset it cannot exceed nnz)
+        std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, s->stream); rt_sync(s->stream);
+        uint64_t total = 0; for (uint32_t c : counts) total += c;
+        spb_check_entries(total);
+    }
     const uint32_t kept = spb_scan_and_allocate(s, side, hs);
-    RT_LAUNCH(spb_scatter_kernel, sliceGrid, 64 * SPB_WAVES, s->stream, in, side[0], side[1]);
-    spb_models(s, side, hs, kept, (float *)(err + 1));
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, s->stream, cin, dm.keep, mp, side[0], side[1]);
+    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
+    spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
+}
+
+// The one-shot entries: the caller's arrays staged for this call (SpbTemps::stage: uploaded from host pointers, read in place from
+// device pointers), checked, then the builder with no subset.  A compressed-sparse matrix is the caller's (cogaps_session_create_sparse)
+// or a dense input's entries > 0 (build_samplers_dense_input, build_samplers_dense_device_sparse); triplets (cogaps_session_create_coo)
+// make the session cogaps_session_create makes from the matrix they denote -- the latest entry of a position decides it.  No nrow x ncol
+// array exists on either side.
+static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
+{
+    SpbTemps tmp; SpbMatrix d;
+    spb_compressed(d, m, s->stream, [&](auto *src, size_t n) { return tmp.stage(src, n, m.onDevice != 0, s->stream); });
+    build_samplers_device_matrix(s, d, nullptr);
+}
+static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix &m)
+{
+    SpbTemps tmp; SpbMatrix d;
+    spb_triplets(d, m, tmp.alloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), s->computeUnits, s->stream,
+                 [&](auto *src, size_t n) { return tmp.stage(src, n, m.onDevice != 0, s->stream); });
+    build_samplers_device_matrix(s, d, nullptr);
 }
 
 // The sparse model from a dense matrix: its entries > 0 (SparseVector.cpp:20-33: NaN, zero and negative values are absent), row by row
@@ -600,56 +719,14 @@ static void build_samplers_dense_input(cogaps_session *s, const float *data, uin
     build_samplers_sparse_input(s, m);
 }
 
-// Both samplers of a session from unordered triplets (sparse_build.h, the passes of its second half): the session cogaps_session_create
-// makes from the matrix the triplets denote -- the latest entry of a position decides it.  The temporaries (the caller's arrays uploaded,
-// the present flags with their prefix counts and pointers, one winner index per present position, one keep bit per entry) are O(nnz + one
-// sampler's flag arrays).
-static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix &m)
-{
-    const uint64_t nnz = m.nnz;
-    SpbTemps tmp;
-    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz;
-    SpbSide side[2], pres;
-    HostSampler *hs[2] = {&s->A, &s->P};
-    spb_sides(s, m.nrow, m.ncol, true, side, hs);
-    in.rows = tmp.stage(m.rows, nnz, m.onDevice != 0, s->stream); in.cols = tmp.stage(m.cols, nnz, m.onDevice != 0, s->stream);
-    in.values = tmp.stage(m.values, nnz, m.onDevice != 0, s->stream);
-    uint32_t *err = tmp.err();
-    pres = side[0]; pres.vals = nullptr;
-    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
-    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
-    unsigned long long *keep = tmp.alloc<unsigned long long>(nnz / 64 + 1);
-    // grid-stride over the entries: enough workgroups to fill the device, never more than the entries need (at least one)
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nnz + COO_BS - 1) / COO_BS, (uint64_t)s->computeUnits * 8u));
-    const uint32_t vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
-    RT_LAUNCH(coo_present_kernel, grid, COO_BS, s->stream, in, pres, err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, s->stream); rt_sync(s->stream);
-    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
-    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, s->stream, pres);
-    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, pres.ptr, pres.M);
-    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, s->stream, pres);
-    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, s->stream); rt_sync(s->stream);
-    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
-    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, s->stream, in, pres, winner);
-    RT_LAUNCH(coo_keep_kernel, grid, COO_BS, s->stream, in, pres, (const uint32_t *)winner, side[0], side[1], keep);
-    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
-    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
-    RT_LAUNCH(coo_scatter_kernel, grid, COO_BS, s->stream, in, side[0], side[1], (const unsigned long long *)keep);
-    spb_models(s, side, hs, kept, (float *)(err + 1));
-}
-
-// A matrix resident on one device (cogaps_device_matrix): device copies of the caller's arrays, validated -- and, for triplets, resolved
-// for repeated positions into one keep bit per entry -- once, at its creation.  Immutable from then on: any number of sessions, on any
-// host threads, are built from it (build_samplers_device_matrix) and copy nothing of it but what their packed structures hold.
+// A matrix resident on one device: the description with device copies of the caller's arrays, which it owns -- checked and, for
+// triplets, resolved once, at its creation.  Immutable from then on: any number of sessions, on any host threads, are built from it
+// (build_samplers_device_matrix) and copy nothing of it but what their packed structures hold.
 struct cogaps_device_matrix {
-    int device = 0; uint32_t nrow = 0, ncol = 0; uint64_t nnz = 0; unsigned computeUnits = 0;
-    bool coo = false, majorIsRow = true;
-    uint64_t *indptr = nullptr; uint32_t *indices = nullptr;       // compressed: [nMajor + 1], [nnz]
-    uint32_t *rows = nullptr, *cols = nullptr;                     // triplets: [nnz]
-    unsigned long long *keep = nullptr;                            // triplets: bit k = entry k is the latest of its position and > 0
-    float *values = nullptr;
+    SpbMatrix m;
+    int device = 0; unsigned computeUnits = 0;
     std::atomic<uint64_t> deviceBytes{0};
-    ~cogaps_device_matrix() { rt_free(indptr); rt_free(indices); rt_free(rows); rt_free(cols); rt_free(keep); rt_free(values); }
+    ~cogaps_device_matrix() { rt_free((void *)m.indptr); rt_free((void *)m.indices); rt_free((void *)m.rows); rt_free((void *)m.cols); rt_free((void *)m.keep); rt_free((void *)m.values); }
 };
 // one of the caller's arrays into the handle's own memory (count + 1 elements: never an empty allocation)
 template <class T> static T *dm_copy(const T *src, size_t count, bool onDevice, rt_stream_t stream)
@@ -658,100 +735,14 @@ template <class T> static T *dm_copy(const T *src, size_t count, bool onDevice, 
     if (count) { if (onDevice) rt_d2d(q, src, count * sizeof(T), stream); else rt_h2d(q, src, count * sizeof(T), stream); }
     return q;
 }
-static uint32_t entry_grid(uint64_t n, unsigned computeUnits, uint32_t bs)
-{
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + bs - 1) / bs, (uint64_t)computeUnits * 8u));
-}
-
 static void device_matrix_from_sparse(cogaps_device_matrix *dm, const cogaps_sparse_matrix &m, rt_stream_t stream)
 {
-    const uint32_t nMajor = m.majorIsRow ? m.nrow : m.ncol, nMinor = m.majorIsRow ? m.ncol : m.nrow;
-    uint64_t nnz = 0;
-    if (m.onDevice) { rt_d2h(&nnz, m.indptr + nMajor, 8, stream); rt_sync(stream); } else nnz = m.indptr[nMajor];
-    if (nnz >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
-    if (nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
-    dm->coo = false; dm->majorIsRow = m.majorIsRow != 0; dm->nnz = nnz;
-    dm->indptr = dm_copy(m.indptr, (size_t)nMajor + 1, m.onDevice != 0, stream);
-    dm->indices = dm_copy(m.indices, nnz, m.onDevice != 0, stream); dm->values = dm_copy(m.values, nnz, m.onDevice != 0, stream);
-    SpbTemps tmp; uint32_t *err = tmp.err();
-    SpbIn in; in.nMajor = nMajor; in.nMinor = nMinor; in.nnz = nnz; in.indptr = dm->indptr; in.indices = dm->indices; in.values = dm->values;
-    RT_LAUNCH(spb_validate_kernel, (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, in, err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
-    if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
-    if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
-    if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
+    spb_compressed(dm->m, m, stream, [&](auto *src, size_t n) { return dm_copy(src, n, m.onDevice != 0, stream); });
 }
-
-// build_samplers_coo_input's passes 1 to 4 in the coordinates of the whole matrix, keeping the keep bits only: the present flags (laid out
-// [nrow][ncol / 64 + 1]) with their prefix counts and pointers and the winner indices are temporaries of this call
 static void device_matrix_from_coo(cogaps_device_matrix *dm, const cogaps_coo_matrix &m, rt_stream_t stream)
 {
-    const uint64_t nnz = m.nnz;
-    dm->coo = true; dm->majorIsRow = true; dm->nnz = nnz;
-    dm->rows = dm_copy(m.rows, nnz, m.onDevice != 0, stream); dm->cols = dm_copy(m.cols, nnz, m.onDevice != 0, stream);
-    dm->values = dm_copy(m.values, nnz, m.onDevice != 0, stream);
-    dm->keep = dalloc<unsigned long long>(nnz / 64 + 1);
-    SpbTemps tmp; uint32_t *err = tmp.err();
-    CooIn in; in.nrow = m.nrow; in.ncol = m.ncol; in.nnz = nnz; in.rows = dm->rows; in.cols = dm->cols; in.values = dm->values;
-    SpbSide pres; pres.M = m.nrow; pres.Wn = m.ncol / 64u + 1u; pres.swap = 0u; pres.vals = nullptr;
-    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
-    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
-    const uint32_t grid = entry_grid(nnz, dm->computeUnits, COO_BS), vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
-    RT_LAUNCH(coo_present_kernel, grid, COO_BS, stream, in, pres, err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
-    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
-    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
-    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, pres.ptr, pres.M);
-    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
-    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, stream); rt_sync(stream);
-    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
-    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, stream, in, pres, winner);
-    RT_LAUNCH(coo_keep_bits_kernel, grid, COO_BS, stream, in, pres, (const uint32_t *)winner, dm->keep);
-    rt_sync(stream);
-}
-
-// Both samplers of a session from a device-resident matrix, with or without subsetData (sparse_build.h, the map and the mapped passes):
-// the session build_samplers_dense_input makes from the dense form of the handle's matrix.  One read of the handle's entries per mapped
-// pass; the session's allocations are those of any sparse-model session, the temporaries (the subset's indices, counts, cursors, list)
-// O(dim + n).  Nothing is uploaded but the subset's indices.
-static void build_samplers_device_matrix(cogaps_session *s, const cogaps_device_matrix &dm)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetData = p.subsetData && !s->subset.empty();
-    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0);
-    const uint32_t nIdx = (uint32_t)s->subset.size();
-    const uint32_t nrow = subsetData && subsetRows ? nIdx : dm.nrow, ncol = subsetData && !subsetRows ? nIdx : dm.ncol;
-    SpbTemps tmp;
-    SpbSide side[2];
-    HostSampler *hs[2] = {&s->A, &s->P};
-    spb_sides(s, nrow, ncol, dm.majorIsRow, side, hs);
-    SpbMap mp; mp.start = mp.list = nullptr; mp.onMajor = subsetRows == dm.majorIsRow ? 1u : 0u;
-    if (subsetData) {
-        const uint32_t dim = subsetRows ? dm.nrow : dm.ncol;
-        const uint32_t *indices = tmp.stage(s->subset.data(), nIdx, false, s->stream);
-        uint32_t *start = tmp.alloc<uint32_t>((size_t)dim + 1), *cursor = tmp.alloc<uint32_t>(dim), *list = tmp.alloc<uint32_t>(nIdx);
-        const uint32_t mapGrid = entry_grid(nIdx, s->computeUnits, SPB_MAP_BS);
-        RT_LAUNCH(spb_map_count_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, start);
-        RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, start, dim);
-        RT_LAUNCH(spb_map_fill_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, (const uint32_t *)start, cursor, list);
-        mp.start = start; mp.list = list;
-    }
-    SpbIn in; CooIn cin;
-    const uint32_t nMajor = dm.majorIsRow ? dm.nrow : dm.ncol;
-    in.nMajor = nMajor; in.nMinor = dm.majorIsRow ? dm.ncol : dm.nrow; in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
-    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
-    const uint32_t sliceGrid = (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, s->computeUnits, COO_BS);
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, s->stream, cin, (const unsigned long long *)dm.keep, mp, side[0], side[1]);
-    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
-    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
-    // an entry has as many images as its index repeats in the subset: the total in 64 bits before the 32-bit scan
-    std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, s->stream); rt_sync(s->stream);
-    uint64_t total = 0; for (uint32_t c : counts) total += c;
-    if (total >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
-    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, s->stream, cin, (const unsigned long long *)dm.keep, mp, side[0], side[1]);
-    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
-    spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
+    spb_triplets(dm->m, m, dalloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), dm->computeUnits, stream,
+                 [&](auto *src, size_t n) { return dm_copy(src, n, m.onDevice != 0, stream); });
 }
 
 // ---- dense input resident on the device (cogaps_session_create with data_on_device = 1; dense_build.h) ----
@@ -840,7 +831,7 @@ static void build_samplers_dense_device_sparse(cogaps_session *s, const float *d
     // the total in 64 bits before the 32-bit scan
     std::vector<uint32_t> counts(m.nrow); rt_d2h(counts.data(), ptr, (size_t)m.nrow * 4, s->stream); rt_sync(s->stream);
     uint64_t total = 0; for (uint32_t c : counts) total += c;
-    if (total >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
+    spb_check_entries(total);
     RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, ptr, m.nrow);
     uint64_t *indptr = tmp.alloc<uint64_t>((size_t)m.nrow + 1); uint32_t *indices = tmp.alloc<uint32_t>((size_t)total + 1); float *values = tmp.alloc<float>((size_t)total + 1);
     RT_LAUNCH(dnb_csr_fill_kernel, rowGrid, 64 * SPB_WAVES, s->stream, in, m.nrow, m.ncol, (const uint32_t *)ptr, indptr, indices, values);
@@ -1403,19 +1394,17 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
             if (!p.useSparseOptimization) { fail("a compressed-sparse matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
             if (p.subsetData) { fail("subsetData is not supported with a compressed-sparse matrix: pass the rows / columns of the subset"); return nullptr; }
             if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a compressed-sparse matrix"); return nullptr; }
-            if (!sp->indptr) { fail("null argument: indptr"); return nullptr; }
         } else if (coo) {
             nrow = coo->nrow; ncol = coo->ncol;
             if (!p.useSparseOptimization) { fail("a triplet matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
             if (p.subsetData) { fail("subsetData is not supported with a triplet matrix: pass the entries of the subset"); return nullptr; }
             if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a triplet matrix"); return nullptr; }
-            if (coo->nnz >= 0xFFFFFFFFull) { fail("triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)"); return nullptr; }
-            if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) { fail("null argument: rows / cols / values"); return nullptr; }
         } else if (dm) {
-            nrow = dm->nrow; ncol = dm->ncol;
+            nrow = dm->m.nrow; ncol = dm->m.ncol;
             if (!p.useSparseOptimization) { fail("a device-resident matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
             if (p.device != dm->device) { fail("params->device must be -1 or the device the matrix resides on (" + std::to_string(dm->device) + ")"); return nullptr; }
         } else if (!data) { fail("null argument: data"); return nullptr; }
+        if (const char *refusal = sparse_args_refusal(sp, coo)) { fail(refusal); return nullptr; }
         // The reference's distributed caller forces asynchronousUpdates = FALSE on its workers (R/DistributedCogaps.R:28-29) -- there to keep
         // BiocParallel workers single-threaded, not for the sampler's sake.  Documented deviation: a
         // distributed worker call (runningDistributed, i.e. subsetDim > 0 in cogaps_cpp, Cogaps.cpp:82) runs the asynchronous sampler anyway,
@@ -1463,7 +1452,7 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
         if (sp) build_samplers_sparse_input(s, *sp);
         else if (coo) build_samplers_coo_input(s, *coo);
-        else if (dm) build_samplers_device_matrix(s, *dm);
+        else if (dm) build_samplers_device_matrix(s, dm->m, p.subsetData && !s->subset.empty() ? &s->subset : nullptr);
         else if (data_on_device) {      // device-resident dense input (and uncertainty): built where it lies (dense_build.h)
             if (p.useSparseOptimization) build_samplers_dense_device_sparse(s, data, nrow, ncol); else build_samplers_dense_device(s, data, nrow, ncol, unc);
         } else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
@@ -1553,17 +1542,11 @@ static cogaps_device_matrix *device_matrix_create(const cogaps_sparse_matrix *sp
     cogaps_device_matrix *dm = nullptr;
     rt_stream_t stream; bool haveStream = false;
     try {
-        if (sp) {
-            if (!sp->indptr) { fail("null argument: indptr"); return nullptr; }
-        } else {
-            if (coo->nnz >= 0xFFFFFFFFull) { fail("triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)"); return nullptr; }
-            if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) { fail("null argument: rows / cols / values"); return nullptr; }
-        }
+        if (const char *refusal = sparse_args_refusal(sp, coo)) { fail(refusal); return nullptr; }
         if ((sp ? sp->nrow : coo->nrow) == 0 || (sp ? sp->ncol : coo->ncol) == 0) { fail("empty problem"); return nullptr; }
         rt_set_device(device);
         dm = new cogaps_device_matrix();
         dm->device = rt_get_device(); dm->computeUnits = rt_compute_units();
-        dm->nrow = sp ? sp->nrow : coo->nrow; dm->ncol = sp ? sp->ncol : coo->ncol;
         stream = rt_stream_create(); haveStream = true;
         {
             rt_alloc_scope allocOn(stream); rt_owner_scope owner(&dm->deviceBytes);
@@ -1598,9 +1581,9 @@ void cogaps_device_matrix_destroy(cogaps_device_matrix *m)
 int cogaps_device_matrix_info(const cogaps_device_matrix *m, uint32_t *nrow, uint32_t *ncol, uint64_t *storedEntries, uint64_t *deviceBytes, int *device)
 {
     if (!m) return fail("null argument");
-    if (nrow) *nrow = m->nrow;
-    if (ncol) *ncol = m->ncol;
-    if (storedEntries) *storedEntries = m->nnz;
+    if (nrow) *nrow = m->m.nrow;
+    if (ncol) *ncol = m->m.ncol;
+    if (storedEntries) *storedEntries = m->m.nnz;
     if (deviceBytes) *deviceBytes = m->deviceBytes.load();
     if (device) *device = m->device;
     return 0;

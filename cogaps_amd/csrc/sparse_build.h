@@ -6,13 +6,11 @@
 // A sampler holds its data as [vector j][element i]: dflags [M][Wn] (bit i of vector j: the entry is > 0), dprefix [M][Wn] (packed
 // values of the vector before each flag word), dptr [M + 1] (first packed value of each vector), dvals (the values > 0, vector by
 // vector, ascending element index).  For one sampler the input's major axis is the vector axis, for the other the element axis
-// (SpbSide::swap); both are built by the same three passes, none of which depends on the order in which the entries arrive:
-//   1. spb_validate_count_kernel: checks the input, counts the kept entries per vector into dptr, sets the flag bits (64-bit atomic OR)
-//   2. spb_scan_kernel: dptr = exclusive scan of the counts; spb_prefix_kernel: dprefix = popcount scan over each vector's flag words
-//   3. spb_scatter_kernel: every kept entry computes its own slot dptr[j] + dprefix[j][i >> 6] + popcount(flags below bit i)
-// and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order -- gaps::nonZeroMean's sum over
-// the dense elements in (j, i) order (zeros add nothing), which feeds lambda.  A device-resident matrix (cogaps_device_matrix: further down)
-// goes through passes of the same shape that place every entry through a map of the subset axis.
+// (SpbSide::swap).  The input is validated first (spb_validate_kernel; triplets: resolved into one keep bit per entry, further down);
+// both samplers are then built by ONE route, the mapped passes at the end of this file (cogaps_hip.cpp, build_samplers_device_matrix),
+// whether the arrays are a caller's of one session or a cogaps_device_matrix's of many.  None of its passes depends on the order in
+// which the entries arrive, and spb_ordered_sum_kernel adds each sampler's packed values with one fp32 accumulator in their order --
+// gaps::nonZeroMean's sum over the dense elements in (j, i) order (zeros add nothing), which feeds lambda.
 #pragma once
 #include "gaps_state.h"
 #include "eval_kernel.h"
@@ -43,30 +41,20 @@ CG_DEVICE void spb_place(const SpbSide &s, uint32_t major, uint32_t minor, uint3
     vec = s.swap ? minor : major; el = s.swap ? major : minor;
 }
 
-// One wave per major slice: the slice's bounds, every index against nMinor and against its predecessor; the entries > 0 are counted
-// per major slice (one store per wave) and per minor index (one integer atomic each: the indices of a slice differ), and set their bit
-// in both samplers' flag words.  Nothing is read outside [0, nnz) and nothing written outside the two samplers' arrays whatever the
-// input holds; what is written for a malformed input is never used (the host reads *err first).
-CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_validate_count_kernel(SpbIn in, SpbSide a, SpbSide b, uint32_t *err)
+// The checks of a compressed matrix, one wave per major slice: the slice's bounds, every index against nMinor and against its
+// predecessor.  Nothing is read outside [0, nnz) whatever the input holds, nothing written but *err; the host reads *err before
+// anything is built from the arrays.
+CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_validate_kernel(SpbIn in, uint32_t *err)
 {
     const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
     uint64_t lo, hi; spb_slice(in, m, lo, hi);
     if (m == 0u && m < in.nMajor && lo != 0ull) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); }
     if (lo > hi || hi > in.nnz) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); hi = lo = 0; }
-    uint32_t kept = 0;
     for (uint64_t k = lo + lane; k < hi; k += 64u) {
         const uint32_t idx = in.indices[k];
         if (idx >= in.nMinor) { cg_atomic_max_u32(err, SPB_ERR_RANGE); continue; }
         if (k > lo && in.indices[k - 1] >= idx) cg_atomic_max_u32(err, SPB_ERR_ORDER);
-        if (!(in.values[k] > 0.f)) continue;                              // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
-        ++kept;
-        uint32_t vec, el;
-        spb_place(a, m, idx, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
-        spb_place(b, m, idx, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
-        cg_atomic_add_u32((a.swap ? a.ptr : b.ptr) + idx, 1u);
     }
-    kept = cg_wave_sum_u32(kept);
-    if (lane == 0u && m < in.nMajor) (a.swap ? b.ptr : a.ptr)[m] = kept;
 }
 
 // cnt[0 .. n) -> their exclusive prefix sums, cnt[n] = the total.  One workgroup of 1024 threads: a contiguous run of the array per
@@ -114,19 +102,6 @@ CG_DEVICE uint32_t spb_slot(const SpbSide &s, uint32_t major, uint32_t minor)
     return s.ptr[vec] + s.prefix[w] + (uint32_t)cg_popc64(s.flags[w] & ((1ull << (el & 63u)) - 1ull));
 }
 CG_DEVICE void spb_store(const SpbSide &s, uint32_t major, uint32_t minor, float v) { s.vals[spb_slot(s, major, minor)] = v; }
-// every kept entry to its slot in both samplers' packed values (validated input only: the slots are then distinct and below ptr[M])
-CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_scatter_kernel(SpbIn in, SpbSide a, SpbSide b)
-{
-    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
-    uint64_t lo, hi; spb_slice(in, m, lo, hi);
-    for (uint64_t k = lo + lane; k < hi; k += 64u) {
-        const float v = in.values[k];
-        if (!(v > 0.f)) continue;
-        const uint32_t idx = in.indices[k];
-        spb_store(a, m, idx, v); spb_store(b, m, idx, v);
-    }
-}
-
 // out[0], out[1] = 0 + v[0] + v[1] + ... of sampler a's and sampler b's packed values, one accumulator each (seq_sum): workgroup 0
 // and workgroup 1.  The order of the additions is the result; a tree or an atomic sum would give other bits.
 CG_KERNEL void CG_LAUNCH_BOUNDS(256) spb_ordered_sum_kernel(const float *va, const float *vb, uint32_t n, float *out)
@@ -142,13 +117,14 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(256) spb_ordered_sum_kernel(const float *va, con
 // also when its value is not > 0 (the position is then absent).  Which entry is the latest depends on k alone, never on which wave ran
 // first:
 //   1. coo_present_kernel: checks every index, sets a PRESENT bit per entry -- whatever its value -- in a temporary flag array laid out
-//      like sampler A's (64-bit atomic OR: idempotent)
+//      [nrow][ncol / 64 + 1] (64-bit atomic OR: idempotent)
 //   2. spb_count_kernel, spb_scan_kernel, spb_prefix_kernel on that array: every present position gets a slot
 //   3. coo_winner_kernel: winner[slot] = max k over the position's entries (32-bit atomic max: commutative, so the order of arrival is
 //      immaterial)
-//   4. coo_keep_kernel: entry k is KEPT when winner[slot] == k and its value is > 0; the kept entries are distinct positions.  They set
-//      both samplers' flag bits, and one bit each in keep[] (a wave's ballot: one 64-bit store per 64 entries)
-//   5. spb_count_kernel, scan, prefix per sampler, then coo_scatter_kernel: every kept entry to its slot, as in the compressed build
+//   4. coo_keep_bits_kernel: entry k is KEPT when winner[slot] == k and its value is > 0; the kept entries are distinct positions, one
+//      bit each in keep[] (a wave's ballot: one 64-bit store per 64 entries)
+// The present flags with their prefix counts and pointers and the winner indices are temporaries; the
+// rows, columns, values and keep[] then go through the mapped passes below, which read the kept entries only.
 // Hot positions (many entries of one position, or of one flag word) meet at one address in passes 1 and 3; an entry first reads the word
 // (a relaxed device-scope atomic load: served where the atomics are carried out, no cache line of this compute unit involved) and leaves
 // the atomic out when it would change nothing (both words only ever grow, so an old value costs an atomic, never the result).
@@ -171,7 +147,7 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_present_kernel(CooIn in, SpbSide t, 
     }
 }
 
-// ptr[j] = set flag bits of vector j (what the compressed build counts entry by entry: here an entry may repeat).  One wave per vector.
+// ptr[j] = set flag bits of vector j (a popcount, not a count of entries: a triplet position or an image of a subset may repeat).  One wave per vector.
 CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_count_kernel(SpbSide s)
 {
     const uint32_t lane = cg_tid() & 63u, j = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
@@ -194,42 +170,23 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_winner_kernel(CooIn in, SpbSide t, u
     }
 }
 
-// The kept entries: their bit in both samplers' flag words and in keep[k >> 6] (bit k & 63).  A wave takes 64 consecutive entries from a
-// multiple of 64 on, so a keep word has one writer.
-CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_keep_kernel(CooIn in, SpbSide t, const uint32_t *winner, SpbSide a, SpbSide b, unsigned long long *keep)
+// keep[k >> 6] bit k & 63: entry k is the latest of its position and its value is > 0 (SparseVector keeps v > 0 only,
+// SparseVector.cpp:20-33).  A wave takes 64 consecutive entries from a multiple of 64 on, so a keep word has one writer.
+CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_keep_bits_kernel(CooIn in, SpbSide t, const uint32_t *winner, unsigned long long *keep)
 {
     const uint32_t lane = cg_tid() & 63u;
     for (uint64_t base = (uint64_t)cg_bid() * COO_BS + (cg_tid() - lane); base < in.nnz; base += (uint64_t)cg_gdim() * COO_BS) {
         const uint64_t k = base + lane;
-        bool kept = false;
-        if (k < in.nnz) {
-            const uint32_t r = in.rows[k], c = in.cols[k];
-            kept = in.values[k] > 0.f && winner[spb_slot(t, r, c)] == (uint32_t)k;      // SparseVector keeps v > 0 only (SparseVector.cpp:20-33)
-            if (kept) {
-                uint32_t vec, el;
-                spb_place(a, r, c, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
-                spb_place(b, r, c, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
-            }
-        }
+        const bool kept = k < in.nnz && in.values[k] > 0.f && winner[spb_slot(t, in.rows[k], in.cols[k])] == (uint32_t)k;
         const unsigned long long mask = cg_ballot(kept);
         if (lane == 0u) keep[base >> 6] = mask;
     }
 }
 
-// every kept entry to its slot in both samplers' packed values (the kept entries are distinct positions: the slots are distinct)
-CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_scatter_kernel(CooIn in, SpbSide a, SpbSide b, const unsigned long long *keep)
-{
-    for (uint64_t k = (uint64_t)cg_bid() * COO_BS + cg_tid(); k < in.nnz; k += (uint64_t)cg_gdim() * COO_BS) {
-        if (!((keep[k >> 6] >> (k & 63u)) & 1ull)) continue;
-        const uint32_t r = in.rows[k], c = in.cols[k]; const float v = in.values[k];
-        spb_store(a, r, c, v); spb_store(b, r, c, v);
-    }
-}
-
-// ---- a device-resident matrix (cogaps_device_matrix) and a subset of its rows or columns ----
-// The handle keeps the caller's arrays as they came: validated once at its creation (spb_validate_kernel: the checks of
-// spb_validate_count_kernel and nothing else; triplets: the present / winner passes above, then coo_keep_bits_kernel).  A session made
-// from it visits every stored entry of the handle once (triplets: every kept entry) and places it through a MAP of the subset axis:
+// ---- the one route from validated arrays to both samplers, with or without a subset of the rows or columns ----
+// The arrays are a caller's (one session: staged for the call) or a cogaps_device_matrix's (kept as they came, validated -- triplets:
+// resolved -- once at its creation, any number of sessions).  A session visits every stored entry once (triplets: every kept entry)
+// and places it through a MAP of the subset axis:
 // subsetData names n 1-based indices of that axis (dimension dim), output row / column i is input indices[i] - 1 (Matrix.cpp:30-69: in
 // the order given, an index may repeat), so input index c has the IMAGES { i : indices[i] - 1 == c } -- none when c is not in the subset.
 //   1. spb_map_count_kernel: cnt[c] = number of images of c (32-bit atomic add); spb_scan_kernel: start = exclusive scan, start[dim] = n
@@ -282,20 +239,6 @@ CG_DEVICE void spb_mapped_entry(const SpbMap &mp, const SpbSide &a, const SpbSid
     }
 }
 
-// The checks of spb_validate_count_kernel on their own (a handle's creation builds nothing): one wave per major slice.  Nothing is read
-// outside [0, nnz) whatever the input holds, nothing written but *err.
-CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_validate_kernel(SpbIn in, uint32_t *err)
-{
-    const uint32_t lane = cg_tid() & 63u, m = cg_bid() * (uint32_t)SPB_WAVES + (cg_tid() >> 6);
-    uint64_t lo, hi; spb_slice(in, m, lo, hi);
-    if (m == 0u && m < in.nMajor && lo != 0ull) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); }
-    if (lo > hi || hi > in.nnz) { if (lane == 0u) cg_atomic_max_u32(err, SPB_ERR_INDPTR); hi = lo = 0; }
-    for (uint64_t k = lo + lane; k < hi; k += 64u) {
-        const uint32_t idx = in.indices[k];
-        if (idx >= in.nMinor) { cg_atomic_max_u32(err, SPB_ERR_RANGE); continue; }
-        if (k > lo && in.indices[k - 1] >= idx) cg_atomic_max_u32(err, SPB_ERR_ORDER);
-    }
-}
 // A validated compressed matrix through the map: one wave per major slice.  A slice whose major index has no image is left unread.
 template <bool STORE>
 CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_mapped_kernel(SpbIn in, SpbMap mp, SpbSide a, SpbSide b)
@@ -310,18 +253,6 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(64 * SPB_WAVES) spb_mapped_kernel(SpbIn in, SpbM
     }
 }
 
-// coo_keep_kernel's keep bits on their own (a handle's creation sets no sampler's flags): entry k is kept when it is the latest of its
-// position and its value is > 0.  A wave takes 64 consecutive entries from a multiple of 64 on, so a keep word has one writer.
-CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_keep_bits_kernel(CooIn in, SpbSide t, const uint32_t *winner, unsigned long long *keep)
-{
-    const uint32_t lane = cg_tid() & 63u;
-    for (uint64_t base = (uint64_t)cg_bid() * COO_BS + (cg_tid() - lane); base < in.nnz; base += (uint64_t)cg_gdim() * COO_BS) {
-        const uint64_t k = base + lane;
-        const bool kept = k < in.nnz && in.values[k] > 0.f && winner[spb_slot(t, in.rows[k], in.cols[k])] == (uint32_t)k;
-        const unsigned long long mask = cg_ballot(kept);
-        if (lane == 0u) keep[base >> 6] = mask;
-    }
-}
 // The kept triplets through the map (rows are the major axis): grid-stride over the entries
 template <bool STORE>
 CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_mapped_kernel(CooIn in, const unsigned long long *keep, SpbMap mp, SpbSide a, SpbSide b)
@@ -334,7 +265,7 @@ CG_KERNEL void CG_LAUNCH_BOUNDS(COO_BS) coo_mapped_kernel(CooIn in, const unsign
 
 // GapsStatistics::meanChiSq per-vector partials (aux_kernels.h, mean_chisq_rows_kernel) with the data taken from the P sampler's packed
 // form: d = the packed value where the flag bit is set, 0 elsewhere, sd = max(0.1 d, 0.1) -- the default uncertainty, as the dense
-// model's build_sampler fills Sraw.  Same lanes, chunks, slots and finish as the dense model's kernel.
+// model's dnb_sd (dense_build.h) fills Sraw.  Same lanes, chunks, slots and finish as the dense model's kernel.
 template <int V>
 CG_KERNEL void CG_LAUNCH_BOUNDS(1024) mean_chisq_rows_packed_kernel(SamplerDev P, const float *Asum, const float *Psum, uint32_t AMpad, float n2, float *partial)
 {

@@ -102,6 +102,53 @@ def packed_reference(data, nPatterns, transposeData=False):
     return out
 
 
+def seq_sum(x):
+    """one fp32 accumulator, left to right"""
+    return np.cumsum(np.ascontiguousarray(x, dtype=np.float32).ravel(), dtype=np.float32)[-1]
+
+
+def lam(total, nnz, k, alpha=0.01):
+    return np.float32(alpha) * np.sqrt(np.float32(k) / (np.float32(total) / np.float32(nnz)))
+
+
+def dense_reference(data, unc, nPatterns, transposeData=False, subsetIndices=None, subsetDim=0):
+    """What Session.debug_dense_data() must return for a dense-model session of `data` (and the uncertainty `unc`, or None: the default
+    max(0.1 v, 0.1)), in numpy and independent of the library.  Genes are the rows of `data` unless transposeData; subsetIndices are
+    1-based indices of the genes (subsetDim 1) or the samples (2), applied in the order given, repeats included (Matrix.cpp:30-69).
+    Sampler A's data vectors are the genes (elements: samples), sampler P's the samples.  Per sampler, over vectors j = 0 .. M-1 of N
+    elements in rows of Npad = N rounded up to 4:
+      D, Sraw, S2  [M][Npad]: the value, its uncertainty sd and sd * sd in fp32; the pads hold D = 0, Sraw = S2 = 1; S2 is None with
+                   the default uncertainty (the session keeps no such array)
+      lambda       alpha * sqrt(K / (sum / nnz)): sum = ONE fp32 accumulator over the elements in (j, i) order -- every value, a
+                   negative one too -- and nnz = the entries > 0 (gaps::nonZeroMean, MatrixMath.cpp:39-55)
+      maxGibbsMass 100 / lambda;  sparsity  1 - nnz / (M * N), all in fp32 (default alpha and maxGibbsMass)
+    lambda and maxGibbsMass are checked here against the oracle's, which is given the cut matrix and no subset."""
+    f32 = np.float32
+    genes = np.asarray(data, dtype=f32).T if transposeData else np.asarray(data, dtype=f32)
+    sd = None if unc is None else (np.asarray(unc, dtype=f32).T if transposeData else np.asarray(unc, dtype=f32))
+    if subsetIndices is not None and subsetDim:
+        idx = np.asarray(subsetIndices, dtype=np.int64) - 1
+        genes = genes[idx] if subsetDim == 1 else genes[:, idx]
+        if sd is not None:
+            sd = sd[idx] if subsetDim == 1 else sd[:, idx]
+    cut = (lambda x: None if x is None else np.ascontiguousarray(x.T if transposeData else x))
+    O = po.Session(cut(genes), unc=cut(sd), nPatterns=nPatterns, seed=1, transposeData=transposeData)
+    out = {}
+    for w, mat, s in (("A", genes, sd), ("P", genes.T, None if sd is None else sd.T)):
+        M, N = mat.shape
+        D, Sraw = np.zeros((M, (N + 3) & ~3), dtype=f32), np.ones((M, (N + 3) & ~3), dtype=f32)
+        D[:, :N] = mat
+        Sraw[:, :N] = np.maximum(mat * f32(0.1), f32(0.1)) if s is None else s
+        nnz = int((mat > 0).sum())
+        lm = lam(seq_sum(mat), nnz, nPatterns)
+        out[w] = {"D": D, "Sraw": Sraw, "S2": None if s is None else Sraw * Sraw, "lambda": lm, "maxGibbsMass": f32(100) / lm,
+                  "sparsity": f32(1) - f32(nnz) / f32(M * N)}
+        for f, o in (("lambda", O.lam(w)), ("maxGibbsMass", O.max_gibbs_mass(w))):
+            assert f32(out[w][f]).tobytes() == f32(o).tobytes(), "dense_reference %s %s: %r, the oracle has %r" % (w, f, out[w][f], o)
+    O.close()
+    return out
+
+
 def run_stepwise(lib, data, n_iter, trace=True, total_iter=None, check_every=1, **kw):
     total_iter = total_iter or max(n_iter, 2)
     kw.setdefault("nIterations", total_iter)

@@ -1,7 +1,9 @@
 """Dense input resident on the "device" (csrc/dense_build.h; cogaps_session_create with data_on_device = 1, cogaps_run_device) on the
 test-only emulator build, where device addresses are host addresses: a session built from _capi.DeviceDense is, byte for byte, the
 session the host-pointer entry builds from the same numpy matrix -- the dense model's D / Sraw / S2 with their pads and its constants,
-the sparse model's packed structures, the bytes the session owns, and every step of the chain after that."""
+the sparse model's packed structures, the bytes the session owns, and every step of the chain after that.  Each of the two
+dense-model sessions is also compared, as bytes, with parity_util.dense_reference: numpy's statement of what such a session holds,
+which depends on neither builder."""
 import numpy as np
 import pytest
 
@@ -46,11 +48,19 @@ def bits(x):
     return np.float32(x).tobytes()
 
 
-def assert_dense_equal(H, S, tag):
+def assert_dense_equal(H, S, tag, ref):
+    """H (host pointers) and S (DeviceDense) each against ref (pu.dense_reference of their input), then against each other"""
     for w in "AP":
         a, b = H.debug_dense_data(w), S.debug_dense_data(w)
         m, n, _ = H.dims(w)
-        assert S.dims(w) == H.dims(w) and a["D"].shape == (m, (n + 3) & ~3)
+        assert S.dims(w) == H.dims(w) and a["D"].shape == (m, (n + 3) & ~3) == ref[w]["D"].shape
+        for name, got in (("host pointers", a), ("device pointers", b)):
+            for f in ("D", "Sraw", "S2"):
+                assert (got[f] is None) == (ref[w][f] is None), "%s %s, %s: %s kept, the reference says otherwise" % (tag, w, name, f)
+                if got[f] is not None:
+                    assert got[f].tobytes() == ref[w][f].tobytes(), "%s %s, %s: %s differs from the reference" % (tag, w, name, f)
+            for f in ("lambda", "maxGibbsMass", "sparsity"):
+                assert bits(got[f]) == bits(ref[w][f]), "%s %s, %s: %s is %r, the reference has %r" % (tag, w, name, f, got[f], ref[w][f])
         for f in ("D", "Sraw", "S2"):
             assert (a[f] is None) == (b[f] is None), "%s %s: %s kept by one session only" % (tag, w, f)
             if a[f] is not None:
@@ -73,11 +83,12 @@ def subset_kw(shape, which, transpose):
 def check_structures(lib, dd, shape, transpose, which):
     d = matrix(*shape)
     u = uncertainty(d)
-    kw = dict(lib=lib, nPatterns=3, seed=4, transposeData=transpose, **subset_kw(shape, which, transpose))
+    sub = subset_kw(shape, which, transpose)
+    kw = dict(lib=lib, nPatterns=3, seed=4, transposeData=transpose, **sub)
     for unc in (None, u):
         H, S = _capi.Session(d, unc=unc, **kw), _capi.Session(dd(d, unc), **kw)
         assert (H.debug_dense_data("A")["S2"] is None) == (unc is None)
-        assert_dense_equal(H, S, "dense model, unc %s" % (unc is not None))
+        assert_dense_equal(H, S, "dense model, unc %s" % (unc is not None), pu.dense_reference(d, unc, 3, transpose, **sub))
         H.close(), S.close()
     H, S = _capi.Session(d, sparseOptimization=True, **kw), _capi.Session(dd(d), sparseOptimization=True, **kw)
     pu.assert_structures_equal(pu.structures(H), pu.structures(S), "sparse model")
@@ -94,7 +105,7 @@ def check_a_negative_value_and_a_negative_zero(lib, dd, shape):
     plain[1, 2] = 0
     kw = dict(lib=lib, nPatterns=3, seed=4)
     H, S, Z = _capi.Session(d, **kw), _capi.Session(dd(d), **kw), _capi.Session(plain, **kw)
-    assert_dense_equal(H, S, "dense model")
+    assert_dense_equal(H, S, "dense model", pu.dense_reference(d, None, 3))
     D = S.debug_dense_data("A")
     assert D["D"][1, 2] == np.float32(-2.5) and D["D"][2, 1].tobytes() == np.float32(-0.0).tobytes()
     assert bits(D["lambda"]) != bits(Z.debug_dense_data("A")["lambda"]), "the negative value is not in the sum"
@@ -106,13 +117,7 @@ def check_a_negative_value_and_a_negative_zero(lib, dd, shape):
     H.close(), S.close(), Z.close()
 
 
-def seq_sum(x):
-    """one fp32 accumulator, left to right"""
-    return np.cumsum(np.ascontiguousarray(x, dtype=np.float32).ravel(), dtype=np.float32)[-1]
-
-
-def lam(total, nnz, k, alpha=0.01):
-    return np.float32(alpha) * np.sqrt(np.float32(k) / (np.float32(total) / np.float32(nnz)))
+seq_sum, lam = pu.seq_sum, pu.lam
 
 
 def wide_range_matrix():
@@ -135,9 +140,9 @@ def check_the_order_of_the_sum(lib, dd):
     H, S = _capi.Session(d, lib=lib, nPatterns=3, seed=1), _capi.Session(dd(d), lib=lib, nPatterns=3, seed=1)
     for w in "AP":
         h, s = H.debug_dense_data(w)["lambda"], S.debug_dense_data(w)["lambda"]
-        print("lambda %s: host build %r, device build %r, numpy's ordered sum %r" % (w, h, s, float(want[w])))
+        print("lambda %s: host pointers %r, device pointers %r, numpy's ordered sum %r" % (w, h, s, float(want[w])))
         assert bits(s) == bits(h) and bits(s) == bits(want[w])
-    assert_dense_equal(H, S, "wide range")
+    assert_dense_equal(H, S, "wide range", pu.dense_reference(d, None, 3))
     H.close(), S.close()
 
 

@@ -1,5 +1,6 @@
-"""Dense input resident on the MI355X (product library): the kernels of csrc/dense_build.h against the host-pointer entry -- the checks
-of test_dense_device_input.py with real device addresses -- and torch tensors on the GPU through CoGAPS / GWCoGAPS / scCoGAPS."""
+"""Dense input resident on the MI355X (product library): the kernels of csrc/dense_build.h from device pointers and from host pointers,
+each against parity_util.dense_reference and against each other -- the checks of test_dense_device_input.py with real device addresses
+-- and torch tensors on the GPU through CoGAPS / GWCoGAPS / scCoGAPS."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Creation of a session from a DENSE matrix on one MI355X, by where the matrix lies: from host pointers, from device pointers on this
-tree (built on the device: csrc/dense_build.h), and from device pointers with the library of the parent commit (which staged the matrix
-through the host) -- at 20000 x 2000 (dense model, K = 50) and at 50000 x 12500 with 95 % zeros (BASELINE configs[4]'s shard; both
+"""Creation of a session from a DENSE matrix on one MI355X, by where the matrix lies: from host pointers and from device pointers on this
+tree (from device pointers: built on the device, csrc/dense_build.h), and the same two with the library of the parent commit -- at 20000 x 2000 (dense model, K = 50) and at 50000 x 12500 with 95 % zeros (BASELINE configs[4]'s shard; both
 models, K = 50).  Per row: wall time of three runs after a warm-up (host clock around the call, which ends in a stream synchronise),
 the HIP-event time of the ordered sums, cogaps_session_device_bytes, and the peak of device memory during the build above what was
 in use before it (cogaps_device_memory, polled from a second thread) next to it.
@@ -77,6 +76,7 @@ def main():
             row["host_pointers"] = timed_create(_capi, lib, lambda: _capi.Session(data, lib=lib, **kw), a.runs)
             row["device_pointers"] = timed_create(_capi, lib, lambda: _capi.Session(_capi.DeviceDense(data.shape, t.data_ptr()), lib=lib, device=dev.index, **kw), a.runs)
             if parent:
+                row["host_pointers_parent_commit"] = timed_create(_capi, parent, lambda: _capi.Session(data, lib=parent, **kw), a.runs)
                 row["device_pointers_parent_commit"] = timed_create(_capi, parent, lambda: _capi.Session(_capi.DeviceDense(data.shape, t.data_ptr()), lib=parent, device=dev.index, **kw), a.runs)
             assert row["device_pointers"]["session_device_bytes"] == row["host_pointers"]["session_device_bytes"]
             print(json.dumps(row), flush=True)
