@@ -98,6 +98,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -218,6 +219,9 @@ def bind(L):
     L.cogaps_session_load_state.argtypes = [vp, C.c_char_p]
     L.cogaps_session_run_to_end.argtypes = [vp, C.c_char_p, C.c_uint32, C.POINTER(CogapsResultC)]
     L.cogaps_session_debug_data_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
+    u64p, dp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    L.cogaps_gene_set_stat.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
+    L.cogaps_debug_permutation_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -945,6 +949,44 @@ def debug_math(fn, x, mathMode="portable", on_device=False, lib=None):
     if L.cogaps_debug_math({"log": 0, "exp": 1}[fn], _MATH[mathMode] if isinstance(mathMode, str) else int(mathMode), _fp(xs), _fp(ys), xs.size, int(on_device)):
         raise _error(L)
     return ys
+
+
+def gene_set_stat(z, members, sizes, numPerm, seed=0, device=-1, lib=None):
+    """cogaps_gene_set_stat: the permutation counts of the gene-set statistic.  z: the Z matrix (n x K; float64, any strides: a
+    column-major array goes in as it is), members: per set the 0-based member rows, ascending; sizes: per set the rows to draw.
+    -> (lessThanCount uint32 [nSets][K], actualMean float64 [nSets][K])"""
+    L = lib if lib is not None else load()
+    z = np.asarray(z, dtype=np.float64)
+    if z.ndim != 2:
+        raise ValueError("z must be a matrix")
+    if any(st % 8 or st < 0 for st in z.strides):
+        z = np.ascontiguousarray(z)
+    members = [np.asarray(m, dtype=np.uint32).reshape(-1) for m in members]
+    off = np.zeros(len(members) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([m.size for m in members], dtype=np.uint64)
+    mem = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), dtype=np.uint32)
+    if mem.size == 0:
+        mem = np.zeros(1, dtype=np.uint32)      # (an address to hand over; nothing of it is read)
+    sz = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    if sz.size != len(members):
+        raise ValueError("one draw size per set")
+    cnt = np.zeros((len(members), z.shape[1]), dtype=np.uint32)
+    act = np.zeros((len(members), z.shape[1]), dtype=np.float64)
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    if L.cogaps_gene_set_stat(z.ctypes.data_as(dp), z.shape[0], z.shape[1], z.strides[0] // 8, z.strides[1] // 8, len(members),
+                              off.ctypes.data_as(C.POINTER(C.c_uint64)), mem.ctypes.data_as(u32p), sz.ctypes.data_as(u32p),
+                              int(numPerm), int(seed) & 0xFFFFFFFF, int(device), cnt.ctypes.data_as(u32p), act.ctypes.data_as(dp)):
+        raise _error(L)
+    return cnt, act
+
+
+def permutation_draw(nRows, size, seed, set_index, perm, device=-1, lib=None):
+    """cogaps_debug_permutation_draw: the `size` rows of draw (seed, set_index, perm) from nRows rows, by the statistic's kernel code"""
+    L = lib if lib is not None else load()
+    out = np.zeros(max(int(size), 1), dtype=np.uint32)
+    if L.cogaps_debug_permutation_draw(int(nRows), int(size), int(seed) & 0xFFFFFFFF, int(set_index), int(perm), int(device), out.ctypes.data_as(C.POINTER(C.c_uint32))):
+        raise _error(L)
+    return out[:int(size)]
 
 
 def device_memory(device=-1, lib=None):

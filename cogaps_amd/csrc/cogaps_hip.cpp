@@ -20,6 +20,7 @@
 #include "dense_build.h"
 #include "state_digest.h"
 #include "state_file.h"
+#include "geneset_kernel.h"
 
 #include <math.h>
 #include <cmath>
@@ -1352,6 +1353,109 @@ int cogaps_device_memory(int device, uint64_t *freeBytes, uint64_t *totalBytes)
         size_t f = 0, t = 0; rt_mem_info(&f, &t);
         if (device >= 0) rt_set_device(before);
         *freeBytes = (uint64_t)f; *totalBytes = (uint64_t)t;
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result statistics: the gene-set permutation statistic (geneset_kernel.h)
+// ------------------------------------------------------------------------------------------------
+} // extern "C"
+
+// device memory of one call, released however the call ends
+struct GsScratch {
+    std::vector<void *> mem; rt_stream_t st; int before; bool moved;
+    explicit GsScratch(int device) : st(0), before(rt_get_device()), moved(device >= 0 && device != before)
+    {
+        if (moved) rt_set_device(device);
+        try { st = rt_stream_create(); } catch (...) { if (moved) rt_set_device(before); throw; }
+    }
+    template <class T> T *get(size_t n) { mem.push_back(nullptr); mem.back() = rt_malloc(n * sizeof(T)); return (T *)mem.back(); }
+    ~GsScratch()
+    {
+        for (void *p : mem) rt_free(p);
+        rt_stream_destroy(st);
+        if (moved) { try { rt_set_device(before); } catch (const std::exception &) {} }
+    }
+};
+// workgroups of a looping grid: eight of 256 threads fill a compute unit
+static uint32_t gs_grid(unsigned long long units)
+{
+    const unsigned long long room = (unsigned long long)rt_compute_units() * 8ull;
+    const unsigned long long g = units < room ? units : room;
+    return (uint32_t)(g < 1ull ? 1ull : (g > 0x7FFFFFFFull ? 0x7FFFFFFFull : g));
+}
+template <int SLOTS>
+static void gs_launch(const GsArgs &a, rt_stream_t st)
+{
+    const unsigned long long colBlocks = (a.K + 64u * SLOTS - 1u) / (64u * SLOTS), chunks = (a.numPerm + GS_PERMS - 1u) / GS_PERMS;
+    RT_LAUNCH(gs_actual_kernel<SLOTS>, gs_grid(((unsigned long long)a.nSets * colBlocks + GS_WAVES - 1ull) / GS_WAVES), GS_THREADS, st, a);
+    RT_LAUNCH(gs_count_kernel<SLOTS>, gs_grid((unsigned long long)a.nSets * chunks * colBlocks), GS_THREADS, st, a);
+}
+
+extern "C" {
+
+int cogaps_gene_set_stat(const double *z, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                         uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members, const uint32_t *drawSizes,
+                         uint32_t numPerm, uint32_t seed, int device, uint32_t *lessThanCount, double *actualMean)
+{
+    try {
+        if (!z || !memberOffsets || !drawSizes || !lessThanCount) return fail("cogaps_gene_set_stat: null argument");
+        if (nRows == 0u || nCols == 0u) return fail("cogaps_gene_set_stat: the Z matrix is empty");
+        if (nSets == 0u) return fail("cogaps_gene_set_stat: nSets must be at least 1");
+        if (numPerm == 0u) return fail("cogaps_gene_set_stat: numPerm must be at least 1");
+        for (uint32_t t = 0; t < nSets; ++t) {
+            const std::string set = "cogaps_gene_set_stat: set " + std::to_string(t);
+            if (drawSizes[t] == 0u || drawSizes[t] > nRows) return fail(set + ": a draw of " + std::to_string(drawSizes[t]) + " rows is outside 1 .. nRows = " + std::to_string(nRows));
+            if (memberOffsets[t + 1u] < memberOffsets[t]) return fail(set + ": memberOffsets decrease");
+            if (memberOffsets[t + 1u] > memberOffsets[t] && !members) return fail("cogaps_gene_set_stat: null argument");
+            for (uint64_t i = memberOffsets[t]; i < memberOffsets[t + 1u]; ++i) {
+                if (members[i] >= nRows) return fail(set + ": member " + std::to_string(members[i]) + " is not a row of Z (nRows = " + std::to_string(nRows) + ")");
+                if (i > memberOffsets[t] && members[i] <= members[i - 1u]) return fail(set + ": members are not ascending");
+            }
+        }
+        // Z repacked row-major, rows of whole 128-byte lines
+        const size_t ld = ((size_t)nCols + 15u) & ~(size_t)15u;
+        std::vector<double> zp((size_t)nRows * ld, 0.0);
+        for (uint32_t i = 0; i < nRows; ++i)
+            for (uint32_t k = 0; k < nCols; ++k) zp[(size_t)i * ld + k] = z[(size_t)i * rowStride + (size_t)k * colStride];
+        const uint64_t first = memberOffsets[0], nMem = memberOffsets[nSets] - first;
+        std::vector<unsigned long long> off(nSets + 1u);
+        for (uint32_t t = 0; t <= nSets; ++t) off[t] = memberOffsets[t] - first;
+        const size_t nOut = (size_t)nSets * nCols;
+
+        GsScratch g(device);
+        rt_alloc_scope allocOn(g.st);
+        double *dz = g.get<double>(zp.size()), *dAct = g.get<double>(nOut);
+        unsigned long long *dOff = g.get<unsigned long long>(off.size());
+        uint32_t *dMem = g.get<uint32_t>(nMem), *dSize = g.get<uint32_t>(nSets), *dCnt = g.get<uint32_t>(nOut);      // (zero-filled)
+        rt_h2d(dz, zp.data(), zp.size() * 8, g.st);
+        rt_h2d(dOff, off.data(), off.size() * 8, g.st);
+        if (nMem) rt_h2d(dMem, members + first, nMem * 4, g.st);
+        rt_h2d(dSize, drawSizes, (size_t)nSets * 4, g.st);
+        GsArgs a;
+        a.z = dz; a.ld = ld; a.nRows = nRows; a.K = nCols; a.nSets = nSets; a.numPerm = numPerm; a.seed = seed;
+        a.memberOffsets = dOff; a.members = dMem; a.drawSizes = dSize; a.actual = dAct; a.counts = dCnt;
+        if (nCols <= 64u) gs_launch<1>(a, g.st);
+        else if (nCols <= 128u) gs_launch<2>(a, g.st);
+        else gs_launch<4>(a, g.st);
+        rt_d2h(lessThanCount, dCnt, nOut * 4, g.st);
+        if (actualMean) rt_d2h(actualMean, dAct, nOut * 8, g.st);
+        rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, uint32_t set, uint32_t perm, int device, uint32_t *out)
+{
+    try {
+        if (!out) return fail("cogaps_debug_permutation_draw: null argument");
+        if (size == 0u || size > nRows) return fail("cogaps_debug_permutation_draw: a draw of " + std::to_string(size) + " rows is outside 1 .. nRows = " + std::to_string(nRows));
+        GsScratch g(device);
+        rt_alloc_scope allocOn(g.st);
+        uint32_t *d = g.get<uint32_t>(size);
+        RT_LAUNCH(gs_draw_kernel, 1, 64, g.st, nRows, size, seed, set, perm, d);
+        rt_d2h(out, d, (size_t)size * 4, g.st); rt_sync(g.st);
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

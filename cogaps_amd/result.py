@@ -1,7 +1,58 @@
 """CogapsResult -- the numeric core of the reference's S4 result (R/class-CogapsResult.R): the four
 factor matrices under their LinearEmbeddingMatrix names and the metadata list createCogapsResult fills
-(R/methods-CogapsResult.R:8-20).  Plots / gene-set statistics are out of scope."""
+(R/methods-CogapsResult.R:8-20), and of its methods calcZ and calcCoGAPSStat -- the gene-set permutation statistic, computed on the GPU
+(cogaps_gene_set_stat of include/cogaps_hip.h; DESIGN.md 4.8 has the definition, the draw and the deviations from R: the permutations
+come from the library's keyed draw, not from R's sample() stream; a set none of whose members is a row gives NaN where R gives NA; a
+set with one matching row uses that row where R fails).  calcGeneGSStat, computeGeneGSProb, patternMarkers, getPatternGeneSet and the
+plots are out of scope."""
+import warnings
+
 import numpy as np
+
+_WHICH = {"featureLoadings": ("featureLoadings", "loadingStdDev", "geneNames"), "sampleFactors": ("sampleFactors", "factorStdDev", "sampleNames")}
+
+
+def _is_index(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _resolve_sets(sets, names, n, which):
+    """-> (set names, per set the 0-based member rows ascending and unique, per set length(thisSet) as given)"""
+    if isinstance(sets, dict):
+        labels, groups = [str(k) for k in sets.keys()], list(sets.values())
+    elif isinstance(sets, (list, tuple)):
+        labels, groups = [str(i + 1) for i in range(len(sets))], list(sets)
+    else:
+        raise ValueError("sets must be a list of either measurements or samples")
+    if not groups:
+        raise ValueError("sets is empty")
+    out = []
+    for g in groups:
+        if isinstance(g, (str, bytes)) or not hasattr(g, "__iter__"):
+            raise ValueError("sets must be a list of either measurements or samples")
+        out.append([x.item() if isinstance(x, np.generic) else x for x in g])
+    flat = [x for g in out for x in g]
+    by_name = [isinstance(x, str) for x in flat]
+    if not all(by_name) and not all(_is_index(x) for x in flat):
+        raise ValueError("sets must be all index sets or all name sets")
+    if flat and all(by_name):
+        if names is None:
+            raise ValueError("sets holds names but the result carries no %s" % _WHICH[which][2])
+        lookup = {}
+        for i, nm in enumerate(names):
+            lookup.setdefault(nm, []).append(i)
+        members = [np.unique(np.array([i for x in set(g) for i in lookup.get(x, ())], dtype=np.int64)) for g in out]      # rownames %in% thisSet
+    else:
+        if any(x < 1 or x > n for x in flat):
+            raise ValueError("sets holds an index outside 1 .. %d" % n)
+        members = [np.unique(np.array(g, dtype=np.int64) - 1) for g in out]
+    sizes = [len(g) for g in out]
+    for lab, sz in zip(labels, sizes):
+        if sz == 0:
+            raise ValueError("set %s is empty" % lab)
+        if sz > n:
+            raise ValueError("set %s has %d entries, the matrix %d rows: no draw without replacement" % (lab, sz, n))
+    return labels, members, sizes
 
 
 class CogapsResult:
@@ -49,3 +100,43 @@ class CogapsResult:
 
     def getClusteredPatterns(self):
         return self.metadata["diagnostics"].get("clusteredPatterns")
+
+    def calcZ(self, whichMatrix="featureLoadings"):
+        """R/methods-CogapsResult.R:220-231: mean / standard deviation of the chosen matrix in float64; a zero deviation becomes 1e-6"""
+        if whichMatrix not in _WHICH:
+            raise ValueError("whichMatrix must be either 'featureLoadings' or 'sampleFactors'")
+        mean = np.asarray(getattr(self, _WHICH[whichMatrix][0]), dtype=np.float64)
+        sd = np.array(getattr(self, _WHICH[whichMatrix][1]), dtype=np.float64)
+        if (sd == 0).any():
+            warnings.warn("zeros detected in the standard deviation matrix")
+            sd[sd == 0] = 1e-6
+        return mean / sd
+
+    def calcCoGAPSStat(self, sets=None, whichMatrix="featureLoadings", numPerm=1000, seed=None, GStoGenes=None, lib=None):
+        """R/methods-CogapsResult.R:499-531 on the GPU: for every set the share of numPerm random row sets of its size whose mean Z
+        exceeds the set's own, per pattern.  sets: a dict name -> members, or a list of member lists (named "1", "2", ...); members are
+        row names (geneNames for featureLoadings, sampleNames for sampleFactors) or 1-based row indices, never both.  GStoGenes: the
+        reference's older name of `sets`.  seed keys the draws (default: the run's seed).  -> {"twoSidedPValue", "GSUpreg", "GSDownreg",
+        "GSActEst"}: arrays [nPatterns][nSets], and "sets": the set names in order.  A set none of whose members is a row: NaN."""
+        from . import _capi
+        if GStoGenes is not None:
+            sets = GStoGenes
+        if isinstance(numPerm, bool) or not isinstance(numPerm, (int, np.integer)) or numPerm < 1 or numPerm > 0xFFFFFFFF:
+            raise ValueError("numPerm must be a whole number of at least 1")
+        z = self.calcZ(whichMatrix)
+        labels, members, sizes = _resolve_sets(sets, getattr(self, _WHICH[whichMatrix][2]), z.shape[0], whichMatrix)
+        if seed is None:
+            seed = self.metadata.get("seed") or 0
+        count, _ = _capi.gene_set_stat(z, members, sizes, int(numPerm), seed=int(seed), lib=lib)
+        up = count.T / float(numPerm)
+        up[:, [m.size == 0 for m in members]] = np.nan
+        down = 1.0 - up
+        return {"twoSidedPValue": np.maximum(np.minimum(down, up), 1.0 / numPerm), "GSUpreg": up, "GSDownreg": down, "GSActEst": 1.0 - 2.0 * up, "sets": labels}
+
+
+def calcZ(result, whichMatrix="featureLoadings"):
+    return result.calcZ(whichMatrix)
+
+
+def calcCoGAPSStat(result, sets=None, whichMatrix="featureLoadings", numPerm=1000, **kw):
+    return result.calcCoGAPSStat(sets, whichMatrix=whichMatrix, numPerm=numPerm, **kw)

@@ -474,6 +474,29 @@ int cogaps_session_debug_check_domain(cogaps_session *s, char which, uint32_t *v
  * the current device (on_device != 0) or by the same source compiled for the host */
 int cogaps_debug_math(int fn, int mathMode, const float *x, float *y, uint32_t n, int on_device);
 
+/* ------------------------------------------------------------------------------------------------
+ * Result statistics: the gene-set permutation test of the reference's calcCoGAPSStat (R/methods-CogapsResult.R:499-531).
+ *
+ * z: the Z-score matrix (calcZ: mean / standard deviation of a factor matrix), nRows x nCols doubles in host memory, element (i, k)
+ * at z[i * rowStride + k * colStride] -- rowStride = nCols, colStride = 1 for a row-major matrix, rowStride = 1, colStride = nRows
+ * for R's column-major one.  It is uploaded (and repacked) per call.  Set t has the member rows members[memberOffsets[t] ..
+ * memberOffsets[t + 1]), 0-based and ascending, and the draw size drawSizes[t] (the reference draws length(thisSet) rows, whether or
+ * not every name matched a row).  For every set and column k:
+ *   actualMean[t][k]    = the fp64 sum of z over the members, in ascending row order, divided once by their number
+ *   lessThanCount[t][k] = the number of permutations p < numPerm with actualMean[t][k] < the mean of z over the drawSizes[t]
+ *                         distinct rows of draw (seed, t, p), summed in the order of the draw and divided once
+ * The draw is the keyed permutation DESIGN.md 4.8 writes down (not R's sample() stream); a count does not depend on the device or
+ * on how the work was divided.  A set without members has NaN means and counts of 0.  device: -1 for the calling thread's current
+ * one (it is restored before the call returns).  Refused, with a message: null arguments (actualMean may be NULL), nSets == 0,
+ * numPerm == 0, an empty matrix, a draw size of 0 or above nRows, a member that is no row or not above its predecessor,
+ * memberOffsets that decrease.
+ * ---------------------------------------------------------------------------------------------- */
+int cogaps_gene_set_stat(const double *z, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                         uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members, const uint32_t *drawSizes,
+                         uint32_t numPerm, uint32_t seed, int device, uint32_t *lessThanCount, double *actualMean);
+/* test hook: out[j], j < size: the rows of draw (seed, set, perm) from nRows rows, computed on the device by the statistic's own code */
+int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, uint32_t set, uint32_t perm, int device, uint32_t *out);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
