@@ -98,7 +98,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -222,6 +222,7 @@ def bind(L):
     u64p, dp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
     L.cogaps_gene_set_stat.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     L.cogaps_debug_permutation_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p]
+    L.cogaps_pattern_markers.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint64, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_int, C.c_int, u32p, dp, u32p, u32p]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -987,6 +988,47 @@ def permutation_draw(nRows, size, seed, set_index, perm, device=-1, lib=None):
     if L.cogaps_debug_permutation_draw(int(nRows), int(size), int(seed) & 0xFFFFFFFF, int(set_index), int(perm), int(device), out.ctypes.data_as(C.POINTER(C.c_uint32))):
         raise _error(L)
     return out[:int(size)]
+
+
+MARKERS_ALL, MARKERS_CUT = 0, 1       # COGAPS_MARKERS_*
+
+
+def pattern_markers(A, O, lp=None, threshold="all", device=-1, lib=None):
+    """cogaps_pattern_markers: ranks, scores and marker lists of the rows of A (n x K) against the pattern vectors lp (L x K; None: the
+    K unit vectors), O (m x K) being the other factor matrix.  A, O: float64, any strides (a column-major array goes in as it is).
+    -> (ranks uint32 [n][L], scores float64 [n][L], markers: a list of L uint32 arrays of 0-based rows, best rank first)"""
+    L = lib if lib is not None else load()
+    if threshold not in ("all", "cut"):
+        raise ValueError("threshold must be 'all' or 'cut'")
+    mats = []
+    for x in (A, O):
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("A and O must be matrices")
+        if any(st % 8 or st < 0 for st in x.strides):
+            x = np.ascontiguousarray(x)
+        mats.append(x)
+    A, O = mats
+    if A.shape[1] != O.shape[1]:
+        raise ValueError("A and O must have the same number of columns")
+    K = A.shape[1]
+    if lp is not None:
+        lp = [np.asarray(v, dtype=np.float64).reshape(-1) for v in lp]
+        if not lp or any(v.size != K for v in lp):
+            raise ValueError("lp length must equal the number of columns of the Amatrix")
+        lp = np.ascontiguousarray(np.stack(lp))
+    nL = K if lp is None else lp.shape[0]
+    n = A.shape[0]
+    ranks, scores = np.zeros((n, nL), dtype=np.uint32), np.zeros((n, nL), dtype=np.float64)
+    markers, count = np.zeros((nL, n), dtype=np.uint32), np.zeros(nL, dtype=np.uint32)
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    if L.cogaps_pattern_markers(A.ctypes.data_as(dp), n, K, A.strides[0] // 8, A.strides[1] // 8,
+                                O.ctypes.data_as(dp), O.shape[0], O.strides[0] // 8, O.strides[1] // 8,
+                                None if lp is None else lp.ctypes.data_as(dp), 0 if lp is None else nL,
+                                MARKERS_ALL if threshold == "all" else MARKERS_CUT, int(device),
+                                ranks.ctypes.data_as(u32p), scores.ctypes.data_as(dp), markers.ctypes.data_as(u32p), count.ctypes.data_as(u32p)):
+        raise _error(L)
+    return ranks, scores, [markers[l, :int(count[l])].copy() for l in range(nL)]
 
 
 def device_memory(device=-1, lib=None):

@@ -21,6 +21,7 @@
 #include "state_digest.h"
 #include "state_file.h"
 #include "geneset_kernel.h"
+#include "markers_kernel.h"
 
 #include <math.h>
 #include <cmath>
@@ -1456,6 +1457,118 @@ int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, 
         uint32_t *d = g.get<uint32_t>(size);
         RT_LAUNCH(gs_draw_kernel, 1, 64, g.st, nRows, size, seed, set, perm, d);
         rt_d2h(out, d, (size_t)size * 4, g.st); rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result statistics: pattern markers (markers_kernel.h)
+// ------------------------------------------------------------------------------------------------
+} // extern "C"
+
+static_assert(COGAPS_MARKERS_ALL == PM_THRESHOLD_ALL && COGAPS_MARKERS_CUT == PM_THRESHOLD_CUT, "the header's thresholds are the kernels'");
+
+// a host matrix (element (i, k) at src[i * rowStride + k * colStride]) transposed: column k is the run dst[k * ld ..]; rows are taken a
+// block at a time so that a row-major source is read from the cache, not once per column
+static void pm_transpose(std::vector<double> &dst, size_t ld, const double *src, size_t rows, uint32_t cols, size_t rowStride, size_t colStride)
+{
+    dst.assign(ld * cols, 0.0);
+    for (size_t i0 = 0; i0 < rows; i0 += 1024u) {
+        const size_t i1 = rows - i0 < 1024u ? rows : i0 + 1024u;
+        for (uint32_t k = 0; k < cols; ++k)
+            for (size_t i = i0; i < i1; ++i) dst[(size_t)k * ld + i] = src[i * rowStride + (size_t)k * colStride];
+    }
+}
+// test-only: COGAPS_TEST_MARKERS_SMALL_ROWS / COGAPS_TEST_MARKERS_TILE_ROWS move the ranking's cutoff and the radix sort's tile, so
+// that a test reaches every form, and more than one tile, at a few hundred rows
+static uint64_t pm_test_override(const char *name, uint64_t natural)
+{
+    const char *e = getenv(name);
+    return e && *e ? (uint64_t)strtoull(e, nullptr, 10) : natural;
+}
+
+extern "C" {
+
+int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size_t aRowStride, size_t aColStride,
+                           const double *o, uint64_t oRows, size_t oRowStride, size_t oColStride,
+                           const double *lp, uint32_t nLp, int threshold, int device,
+                           uint32_t *ranks, double *scores, uint32_t *markers, uint32_t *markerCount)
+{
+    try {
+        if (!a || !o) return fail("cogaps_pattern_markers: null argument");
+        if (nRows == 0u || nCols == 0u || oRows == 0u) return fail("cogaps_pattern_markers: a matrix is empty");
+        if (nRows > 0xFFFFFFFFull) return fail("cogaps_pattern_markers: " + std::to_string(nRows) + " rows are more than 32-bit ranks hold");
+        if (oRows > 0xFFFFFFFFull) return fail("cogaps_pattern_markers: " + std::to_string(oRows) + " rows of the other matrix are more than 32 bits hold");
+        if ((lp == nullptr) != (nLp == 0u)) return fail("cogaps_pattern_markers: lp and its length must be given together (NULL and 0: the unit vectors)");
+        for (size_t x = 0; lp && x < (size_t)nLp * nCols; ++x)
+            if (!(lp[x] <= 1.0)) return fail("cogaps_pattern_markers: lp should be a list of vectors with max value of 1");
+        if (threshold != COGAPS_MARKERS_ALL && threshold != COGAPS_MARKERS_CUT) return fail("cogaps_pattern_markers: unknown threshold " + std::to_string(threshold));
+        const uint32_t n = (uint32_t)nRows, m = (uint32_t)oRows, K = nCols, L = lp ? nLp : nCols;
+        const size_t ldn = ((size_t)n + 15u) & ~(size_t)15u, ldm = ((size_t)m + 15u) & ~(size_t)15u;
+        uint64_t smallRows = pm_test_override("COGAPS_TEST_MARKERS_SMALL_ROWS", PM_SMALL_ROWS);
+        if (smallRows > (uint64_t)PM_SMALL_ROWS) smallRows = PM_SMALL_ROWS;      // (what the kernel's LDS holds)
+        uint64_t tileRows = pm_test_override("COGAPS_TEST_MARKERS_TILE_ROWS", PM_TILE_ROWS);
+        tileRows = (tileRows + PM_THREADS - 1u) / PM_THREADS * PM_THREADS;
+        if (tileRows < (uint64_t)PM_THREADS) tileRows = PM_THREADS;
+        if (tileRows > (uint64_t)PM_TILE_ROWS) tileRows = PM_TILE_ROWS;
+        std::vector<double> at, ot;
+        pm_transpose(at, ldn, a, n, K, aRowStride, aColStride);
+        pm_transpose(ot, ldm, o, m, K, oRowStride, oColStride);
+        const size_t nOut = (size_t)n * L, nCol = ldn * L;
+
+        GsScratch g(device);
+        rt_alloc_scope allocOn(g.st);
+        PmArgs p;
+        memset(&p, 0, sizeof(p));
+        p.ldn = ldn; p.ldm = ldm; p.n = n; p.m = m; p.K = K; p.L = L; p.threshold = threshold;
+        p.tileRows = (uint32_t)tileRows; p.nTiles = (uint32_t)(((uint64_t)n + tileRows - 1u) / tileRows);
+        const bool small = (uint64_t)n <= smallRows;
+        double *dat = g.get<double>(at.size()), *dot = g.get<double>(ot.size());
+        p.at = dat; p.ot = dot;                                              // (everything below is zero-filled)
+        rt_h2d(dat, at.data(), at.size() * 8, g.st);
+        rt_h2d(dot, ot.data(), ot.size() * 8, g.st);
+        if (lp) { double *dlp = g.get<double>((size_t)L * K); rt_h2d(dlp, lp, (size_t)L * K * 8, g.st); p.lp = dlp; }
+        p.colMax = g.get<unsigned long long>(K);
+        p.keys[0] = g.get<unsigned long long>(nCol); p.order[0] = g.get<uint32_t>(nCol);
+        if (!small) {
+            p.keys[1] = g.get<unsigned long long>(nCol); p.order[1] = g.get<uint32_t>(nCol);
+            p.hist = g.get<uint32_t>((size_t)L * PM_THREADS * p.nTiles); p.digitBase = g.get<uint32_t>((size_t)L * PM_THREADS);
+        }
+        p.rankT = g.get<uint32_t>(nCol); p.rowMin = g.get<uint32_t>(n); p.best = g.get<uint32_t>(n);
+        p.nanRows = g.get<uint32_t>(1); p.cutPos = g.get<uint32_t>(L); p.tileCount = g.get<uint32_t>((size_t)L * p.nTiles);
+        p.markerCount = g.get<uint32_t>(L);
+        if (scores) p.scores = g.get<double>(nOut);
+        if (ranks) p.ranks = g.get<uint32_t>(nOut);
+        const std::vector<uint32_t> noCut(L, n);
+        rt_h2d(p.cutPos, noCut.data(), (size_t)L * 4, g.st);
+        if (markers) { p.markers = g.get<uint32_t>(nOut); rt_memset(p.markers, 0xFF, nOut * 4, g.st); }
+
+        const unsigned long long rowBlocks = ((unsigned long long)n + PM_THREADS - 1ull) / PM_THREADS, tiles = (unsigned long long)L * p.nTiles;
+        RT_LAUNCH(pm_colmax_kernel, gs_grid((unsigned long long)K * ((m + PM_TILE_ROWS - 1ull) / PM_TILE_ROWS)), PM_THREADS, g.st, p);
+        RT_LAUNCH(pm_normalise_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
+        RT_LAUNCH(pm_score_kernel, gs_grid(rowBlocks * ((L + PM_LBLOCK - 1u) / PM_LBLOCK)), PM_THREADS, g.st, p);
+        if (small) RT_LAUNCH(pm_rank_small_kernel, gs_grid(L), PM_THREADS, g.st, p);
+        else {
+            for (int pass = 0; pass < PM_PASSES; ++pass) {
+                p.shift = (uint32_t)pass * PM_DIGIT_BITS;
+                RT_LAUNCH(pm_hist_kernel, gs_grid(tiles), PM_THREADS, g.st, p, pass & 1);
+                RT_LAUNCH(pm_hist_scan_kernel, gs_grid(L), PM_THREADS, g.st, p);
+                RT_LAUNCH(pm_scatter_kernel, gs_grid(tiles), PM_THREADS, g.st, p, pass & 1);
+            }
+            RT_LAUNCH(pm_rank_scatter_kernel, gs_grid(rowBlocks * L), PM_THREADS, g.st, p);
+        }
+        RT_LAUNCH(pm_rowmin_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
+        if (markers || markerCount) {
+            if (threshold == COGAPS_MARKERS_CUT) RT_LAUNCH(pm_cutpos_kernel, gs_grid(rowBlocks * L), PM_THREADS, g.st, p);
+            RT_LAUNCH(pm_marker_count_kernel, gs_grid(tiles), PM_THREADS, g.st, p);
+            RT_LAUNCH(pm_marker_scan_kernel, gs_grid((L + 63u) / 64u), 64, g.st, p);
+            if (markers) RT_LAUNCH(pm_marker_write_kernel, gs_grid(tiles), PM_THREADS, g.st, p);
+        }
+        if (ranks) rt_d2h(ranks, p.ranks, nOut * 4, g.st);
+        if (scores) rt_d2h(scores, p.scores, nOut * 8, g.st);
+        if (markers) rt_d2h(markers, p.markers, nOut * 4, g.st);
+        if (markerCount) rt_d2h(markerCount, p.markerCount, (size_t)L * 4, g.st);
+        rt_sync(g.st);
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

@@ -3,8 +3,10 @@ factor matrices under their LinearEmbeddingMatrix names and the metadata list cr
 (R/methods-CogapsResult.R:8-20), and of its methods calcZ and calcCoGAPSStat -- the gene-set permutation statistic, computed on the GPU
 (cogaps_gene_set_stat of include/cogaps_hip.h; DESIGN.md 4.8 has the definition, the draw and the deviations from R: the permutations
 come from the library's keyed draw, not from R's sample() stream; a set none of whose members is a row gives NaN where R gives NA; a
-set with one matching row uses that row where R fails).  calcGeneGSStat, computeGeneGSProb, patternMarkers, getPatternGeneSet and the
-plots are out of scope."""
+set with one matching row uses that row where R fails), and patternMarkers -- every gene (or sample) ranked by its distance to each
+pattern, and the marker lists, on the GPU as well (cogaps_pattern_markers; DESIGN.md 4.9: all-zero rows rank last and mark nothing
+where R breaks on their NA, a column none of whose rows ranks better elsewhere gives every row where R fails, a wrong lp length is an
+error).  calcGeneGSStat, computeGeneGSProb, getPatternGeneSet and the plots are out of scope."""
 import warnings
 
 import numpy as np
@@ -132,6 +134,54 @@ class CogapsResult:
         up[:, [m.size == 0 for m in members]] = np.nan
         down = 1.0 - up
         return {"twoSidedPValue": np.maximum(np.minimum(down, up), 1.0 / numPerm), "GSUpreg": up, "GSDownreg": down, "GSActEst": 1.0 - 2.0 * up, "sets": labels}
+
+    def patternMarkers(self, threshold="all", lp=None, axis=1, lib=None):
+        """R/methods-CogapsResult.R:397-494 on the GPU: the rows of featureLoadings (axis=1: genes) or sampleFactors (axis=2: samples),
+        scaled by the other matrix's column maxima and normalised by their own maximum, scored by their distance to each pattern vector
+        and ranked per pattern (ties in row order).  lp: a dict name -> vector or a list of vectors of nPatterns entries, none above 1;
+        None: the unit vectors, one per pattern.  threshold "all": every row marks the pattern it ranks best in; "cut": a pattern's
+        markers are its best rows up to the first that ranks better elsewhere.  -> {"PatternMarkers": label -> list of row names (1-based
+        indices if the result carries no names), "PatternRanks": int [rows][L], "PatternScores": float64 [rows][L], "patterns": the labels}"""
+        from . import _capi
+        if axis == 1:
+            A, O, names = self.featureLoadings, self.sampleFactors, self.geneNames
+        elif axis == 2:
+            A, O, names = self.sampleFactors, self.featureLoadings, self.sampleNames
+        else:
+            raise ValueError("axis must be 1 or 2")
+        if threshold not in ("all", "cut"):
+            raise ValueError("threshold must be 'all' or 'cut'")
+        A, O = np.asarray(A, dtype=np.float64), np.asarray(O, dtype=np.float64)
+        K = A.shape[1]
+        if lp is None:
+            labels, vectors = ["Pattern_%d" % (k + 1) for k in range(K)], None
+        else:
+            if isinstance(lp, dict):
+                labels, vectors = [str(k) for k in lp.keys()], list(lp.values())
+            elif isinstance(lp, (list, tuple)):
+                labels, vectors = [str(i + 1) for i in range(len(lp))], list(lp)
+            else:
+                raise ValueError("lp must be a list of vectors")
+            if not vectors:
+                raise ValueError("lp is empty")
+            try:
+                vectors = [np.asarray(v, dtype=np.float64).reshape(-1) for v in vectors]
+            except (TypeError, ValueError):
+                raise ValueError("lp must be a list of vectors")
+            if any(v.size != K for v in vectors):
+                raise ValueError("lp length must equal the number of columns of the Amatrix")
+            if any(not (v <= 1).all() for v in vectors):
+                raise ValueError("lp should be a list of vectors with max value of 1")
+        ranks, scores, rows = _capi.pattern_markers(A, O, lp=vectors, threshold=threshold, lib=lib)
+        if names is not None:
+            lists = [[names[i] for i in r] for r in rows]
+        else:
+            lists = [[int(i) + 1 for i in r] for r in rows]
+        return {"PatternMarkers": dict(zip(labels, lists)), "PatternRanks": ranks.astype(np.int64), "PatternScores": scores, "patterns": labels}
+
+
+def patternMarkers(result, threshold="all", lp=None, axis=1, **kw):
+    return result.patternMarkers(threshold=threshold, lp=lp, axis=axis, **kw)
 
 
 def calcZ(result, whichMatrix="featureLoadings"):

@@ -497,6 +497,35 @@ int cogaps_gene_set_stat(const double *z, uint32_t nRows, uint32_t nCols, size_t
 /* test hook: out[j], j < size: the rows of draw (seed, set, perm) from nRows rows, computed on the device by the statistic's own code */
 int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, uint32_t set, uint32_t perm, int device, uint32_t *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Result statistics: the pattern markers of the reference's patternMarkers (R/methods-CogapsResult.R:397-494).
+ *
+ * a: the matrix whose rows are ranked (featureLoadings for the reference's axis = 1, sampleFactors for axis = 2), nRows x nCols doubles
+ * in host memory, element (i, k) at a[i * aRowStride + k * aColStride]; o: the other factor matrix, oRows x nCols, addressed the same
+ * way through its own strides (rowStride = nCols, colStride = 1 for a row-major matrix; rowStride = 1, colStride = rows for R's
+ * column-major one).  Both are uploaded per call.  lp: nLp pattern vectors of nCols entries each, row-major; NULL with nLp = 0 stands
+ * for the nCols unit vectors.  With L = nLp, or nCols for the unit vectors:
+ *   X[i][k]     = a[i][k] * max_j o[j][k], divided by the largest such product of row i
+ *   score[i][l] = sqrt(sum over k, ascending, of (X[i][k] - lp[l][k])^2)            (fp64, no contraction)
+ *   rank[i][l]  = 1 + the rows with a smaller score in column l + the rows before i with the same score; NaN scores (a row whose
+ *                 largest product is 0) are above every number and equal to each other
+ *   COGAPS_MARKERS_ALL: the markers of l are the rows whose smallest rank over the columns is first reached in column l, NaN rows
+ *                 left out, by ascending rank in l
+ *   COGAPS_MARKERS_CUT: the markers of l are the rows of column l by ascending rank, up to the first row that ranks better in another
+ *                 column (all rows with a number for a score if there is none); a row may be a marker of several patterns
+ * Outputs, each of which may be NULL: ranks [nRows][L] (1-based), scores [nRows][L], markers [L][nRows] (row l: its markerCount[l]
+ * marker rows, 0-based, best rank first, then 0xFFFFFFFF), markerCount [L].  No output depends on the device, on the grid or on
+ * scheduling.  device: -1 for the calling thread's current one (it is restored before the call returns).  Refused, with a message:
+ * a or o NULL, a matrix without rows or columns, lp without nLp or nLp without lp, an lp entry above 1 or NaN, an unknown
+ * threshold, more rows than 32-bit ranks hold.
+ * ---------------------------------------------------------------------------------------------- */
+#define COGAPS_MARKERS_ALL 0
+#define COGAPS_MARKERS_CUT 1
+int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size_t aRowStride, size_t aColStride,
+                           const double *o, uint64_t oRows, size_t oRowStride, size_t oColStride,
+                           const double *lp, uint32_t nLp, int threshold, int device,
+                           uint32_t *ranks, double *scores, uint32_t *markers, uint32_t *markerCount);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
