@@ -75,6 +75,14 @@ class CogapsCooMatrixC(C.Structure):
     ]
 
 
+class CogapsResidualDataC(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("transposeData", C.c_int32), ("nrow", C.c_uint32), ("ncol", C.c_uint32),
+        ("dense", C.c_void_p), ("uncertainty", C.c_void_p), ("rowStride", C.c_size_t), ("colStride", C.c_size_t), ("onDevice", C.c_int32),
+        ("sparse", C.c_void_p), ("coo", C.c_void_p), ("deviceMatrix", C.c_void_p),
+    ]
+
+
 TRACE_DTYPE = np.dtype([
     ("pos", "<u8"), ("rng_state", "<u8"), ("atom1", "<u4"), ("atom2", "<u4"),
     ("r1", "<u4"), ("c1", "<u4"), ("r2", "<u4"), ("c2", "<u4"), ("type", "<u4"), ("batch", "<u4"),
@@ -98,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -223,6 +231,8 @@ def bind(L):
     L.cogaps_gene_set_stat.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     L.cogaps_debug_permutation_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p]
     L.cogaps_pattern_markers.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint64, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_int, C.c_int, u32p, dp, u32p, u32p]
+    L.cogaps_residuals.argtypes = [fp, C.c_uint32, C.c_size_t, C.c_size_t, fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(CogapsResidualDataC),
+                                   u32p, C.c_uint32, C.c_int, dp, dp, dp, dp, u64p]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -1029,6 +1039,86 @@ def pattern_markers(A, O, lp=None, threshold="all", device=-1, lib=None):
                                 ranks.ctypes.data_as(u32p), scores.ctypes.data_as(dp), markers.ctypes.data_as(u32p), count.ctypes.data_as(u32p)):
         raise _error(L)
     return ranks, scores, [markers[l, :int(count[l])].copy() for l in range(nL)]
+
+
+RESIDUAL_DATA_NONE, RESIDUAL_DATA_DENSE, RESIDUAL_DATA_SPARSE, RESIDUAL_DATA_COO, RESIDUAL_DATA_DEVICE_MATRIX = 0, 1, 2, 3, 4      # COGAPS_RESIDUAL_DATA_*
+
+
+def _strided_f32(x):
+    """x as a float32 matrix whose strides are whole, non-negative numbers of elements: as it lies where it is one, a contiguous copy otherwise"""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("a matrix is expected")
+    if any(st % 4 or st < 0 for st in x.strides):
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=-1, lib=None):
+    """cogaps_residuals: how well A (genes x K) and P (samples x K), float32 with any strides, fit `data`.  data: None (the
+    reconstruction A P^T alone), a dense matrix (numpy, any strides -- a column-major array goes in as it is; a torch tensor or a
+    DeviceDense on the GPU is read where it lies) with an optional `unc` of its shape, or a scipy.sparse matrix, SparseMatrix, CooMatrix
+    or DeviceMatrix (never densified; the default uncertainty only).  rows: 0-based genes whose rows of the residual matrix (of the
+    reconstruction without data) are wanted, any order, repeats allowed.  -> {"matrix": float64 [len(rows)][samples] or None,
+    "geneChiSq", "sampleChiSq": float64 vectors, "chiSq": float (the three are None without data), "peakDeviceBytes": int}"""
+    L = lib if lib is not None else load()
+    A, P = _strided_f32(A), _strided_f32(P)
+    if A.shape[1] != P.shape[1]:
+        raise ValueError("featureLoadings has %d patterns, sampleFactors %d" % (A.shape[1], P.shape[1]))
+    G, N, K = A.shape[0], P.shape[0], A.shape[1]
+    desc, keep = CogapsResidualDataC(), []
+    desc.kind, desc.transposeData = RESIDUAL_DATA_NONE, int(bool(transposeData))
+    if data is not None:
+        data, unc, kw = device_input(data, unc, {"device": device})
+        device = kw["device"]
+        if is_sparse(data):
+            data = SparseMatrix.from_scipy(data)
+        if isinstance(data, (SparseMatrix, CooMatrix, DeviceMatrix)):
+            if unc is not None:
+                raise ValueError("a sparse matrix takes no uncertainty matrix: the default uncertainty only")
+            if isinstance(data, DeviceMatrix):
+                desc.kind, desc.deviceMatrix = RESIDUAL_DATA_DEVICE_MATRIX, data._handle()
+            else:
+                m = data.c_struct()
+                keep.append(m)
+                if isinstance(data, CooMatrix):
+                    desc.kind, desc.coo = RESIDUAL_DATA_COO, C.addressof(m)
+                else:
+                    desc.kind, desc.sparse = RESIDUAL_DATA_SPARSE, C.addressof(m)
+        elif isinstance(data, DeviceDense):
+            desc.kind, desc.onDevice = RESIDUAL_DATA_DENSE, 1
+            desc.nrow, desc.ncol = data.shape
+            desc.dense, desc.uncertainty = data.data_addr, data.unc_addr
+            desc.rowStride, desc.colStride = data.shape[1], 1
+        else:
+            d = _strided_f32(data)
+            u = None if unc is None else _strided_f32(unc)
+            if u is not None:
+                if u.shape != d.shape:
+                    raise ValueError("the uncertainty matrix must have the shape of the data")
+                if u.strides != d.strides:      # one pair of strides serves both
+                    d, u = np.ascontiguousarray(d), np.ascontiguousarray(u)
+            keep += [d, u]
+            desc.kind, desc.onDevice = RESIDUAL_DATA_DENSE, 0
+            desc.nrow, desc.ncol = d.shape
+            desc.dense, desc.uncertainty = d.ctypes.data, None if u is None else u.ctypes.data
+            desc.rowStride, desc.colStride = d.strides[0] // 4, d.strides[1] // 4
+    elif unc is not None:
+        raise ValueError("an uncertainty matrix without data")
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    n_out = 0 if idx is None else idx.size
+    out = np.zeros((n_out, N), dtype=np.float64) if n_out else None
+    have = desc.kind != RESIDUAL_DATA_NONE
+    gene, sample, chi = np.zeros(G if have else 0), np.zeros(N if have else 0), C.c_double(0.0)
+    peak = C.c_uint64(0)
+    if L.cogaps_residuals(_fp(A), G, A.strides[0] // 4, A.strides[1] // 4, _fp(P), N, P.strides[0] // 4, P.strides[1] // 4, K,
+                          C.byref(desc) if have else None, idx.ctypes.data_as(u32p) if n_out else None, n_out, int(device),
+                          gene.ctypes.data_as(dp) if have else None, sample.ctypes.data_as(dp) if have else None, C.byref(chi) if have else None,
+                          out.ctypes.data_as(dp) if n_out else None, C.byref(peak)):
+        raise _error(L)
+    return {"matrix": out, "geneChiSq": gene if have else None, "sampleChiSq": sample if have else None,
+            "chiSq": float(chi.value) if have else None, "peakDeviceBytes": int(peak.value)}
 
 
 def device_memory(device=-1, lib=None):

@@ -21,6 +21,30 @@ from .params import CogapsParams
 from .result import CogapsResult
 
 
+def check_values(data, uncertainty):
+    """checkDataMatrix's rules for the values (R/HelperFunctions.R:194-207): no NA, nothing negative in the data or the uncertainty"""
+    # a scipy.sparse matrix: its stored entries (the rest are zeros); triplets read from a file: their values
+    if isinstance(data, _capi.DeviceMatrix):
+        # a device-resident matrix: what its host values showed when it was built (nothing is known of arrays that were on the device already)
+        has_na, has_negative = bool(data.has_na), bool(data.has_negative)
+    else:
+        values = data.values if isinstance(data, (_capi.CooMatrix, _capi.SparseMatrix)) else data.data if _capi.is_sparse(data) else data
+        if getattr(data, "on_device", False):
+            values = np.zeros(0, np.float32)                     # (device arrays given by address: never seen here)
+        # (a tensor on the GPU: torch evaluates the same tests there, one flag each comes to the host)
+        has_na = bool(values.isnan().any()) if _capi.is_tensor(values) else np.isnan(values).any()
+        has_negative = bool((values < 0).any())
+    if has_na:
+        raise ValueError("NA values in data")
+    if has_negative or (uncertainty is not None and bool((uncertainty < 0).any())):
+        raise ValueError("negative values in data and/or uncertainty matrix")
+
+
+def warn_small_uncertainty(uncertainty):
+    if uncertainty is not None and bool((uncertainty < 1e-5).any()):
+        warnings.warn("small values in uncertainty matrix detected")
+
+
 def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots=0, checkpointInFile=None, nThreads=1):
     """R/HelperFunctions.R:194-249 (checkDataMatrix + checkInputs)"""
     if uncertainty is not None and params.sparseOptimization:
@@ -31,23 +55,10 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
         raise ValueError("snapshotPhase must be either equilibration, sampling, or all")
     if params.distributed is not None and nThreads > 1:
         warnings.warn("can't run multi-threaded and distributed CoGAPS at the same time, ignoring nThreads")
-    # a scipy.sparse matrix: its stored entries (the rest are zeros); triplets read from a file: their values
-    if isinstance(data, _capi.DeviceMatrix):
-        # a device-resident matrix: what its host values showed when it was built (nothing is known of arrays that were on the device already)
-        has_na, has_negative = bool(data.has_na), bool(data.has_negative)
-    else:
-        values = data.values if isinstance(data, _capi.CooMatrix) else data.data if _capi.is_sparse(data) else data
-        # (a tensor on the GPU: torch evaluates the same tests there, one flag each comes to the host)
-        has_na = bool(values.isnan().any()) if _capi.is_tensor(values) else np.isnan(values).any()
-        has_negative = bool((values < 0).any())
-    if has_na:
-        raise ValueError("NA values in data")
-    if has_negative or (uncertainty is not None and bool((uncertainty < 0).any())):
-        raise ValueError("negative values in data and/or uncertainty matrix")
+    check_values(data, uncertainty)
     if data.shape[0] <= params.nPatterns or data.shape[1] <= params.nPatterns:
         raise ValueError("nPatterns must be less than dimensions of data")
-    if uncertainty is not None and bool((uncertainty < 1e-5).any()):
-        warnings.warn("small values in uncertainty matrix detected")
+    warn_small_uncertainty(uncertainty)
 
 
 def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputFrequency=1000, uncertainty=None,

@@ -22,6 +22,7 @@
 #include "state_file.h"
 #include "geneset_kernel.h"
 #include "markers_kernel.h"
+#include "residual_kernel.h"
 
 #include <math.h>
 #include <cmath>
@@ -484,17 +485,18 @@ static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha)
     h.partial = dalloc<float>(d.M);
 }
 
-// side[w].ptr holds the kept entries per vector: their exclusive scan, the packed values' allocation, the prefix counts; returns the
-// number of kept entries
-static uint32_t spb_scan_and_allocate(cogaps_session *s, SpbSide *side, HostSampler **hs)
+// side[w].ptr holds the kept entries per vector: their exclusive scan, the packed values' allocation (allocVals(w, count): the side's
+// owner makes it), the prefix counts; returns the number of kept entries
+template <class AllocVals>
+static uint32_t spb_scan_and_allocate(rt_stream_t stream, SpbSide *side, int nSides, AllocVals &&allocVals)
 {
     uint32_t kept[2] = {0, 0};
-    for (int w = 0; w < 2; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, s->stream); }
-    rt_sync(s->stream);
-    if (kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
-    for (int w = 0; w < 2; ++w) {
-        side[w].vals = dalloc<float>((size_t)kept[w] + 1); hs[w]->d.dvals = side[w].vals;
-        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
+    for (int w = 0; w < nSides; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, stream); }
+    rt_sync(stream);
+    if (nSides == 2 && kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
+    for (int w = 0; w < nSides; ++w) {
+        side[w].vals = allocVals(w, (size_t)kept[w] + 1);
+        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, side[w]);
     }
     return kept[0];
 }
@@ -631,6 +633,35 @@ template <class Place> static void spb_triplets(SpbMatrix &d, const cogaps_coo_m
     rt_sync(stream);
 }
 
+// The builder's passes over a checked matrix in device memory (sparse_build.h, passes 3 to 5 of the mapped route): the flag bits, the
+// counts, their scan, the prefix counts and the packed values of the sides given, whose flags / prefix / ptr arrays are allocated and
+// zero.  Two sides: a session's samplers.  One side: the gene side alone, which is all the residuals of a result read
+// (cogaps_residuals) -- the mapped kernels then get that side for both of theirs, see that the two are one (spb_mapped_entry) and
+// set every bit, and store every value, once.  mapped: the map repeats indices, so the kept entries are counted in 64 bits before the 32-bit scan (without a map
+// they cannot exceed nnz).  Returns the number of kept entries.
+template <class AllocVals>
+static uint32_t spb_build_sides(const SpbMatrix &dm, const SpbMap &mp, bool mapped, SpbSide *side, int nSides, unsigned computeUnits, rt_stream_t stream, AllocVals &&allocVals)
+{
+    const SpbSide &a = side[0], &b = side[nSides - 1];
+    SpbIn in; CooIn cin;
+    in.nMajor = dm.nMajor(); in.nMinor = dm.nMinor(); in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
+    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
+    const uint32_t sliceGrid = (in.nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, computeUnits, COO_BS);
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, stream, cin, dm.keep, mp, a, b);
+    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, stream, in, mp, a, b);
+    for (int w = 0; w < nSides; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, side[w]);
+    if (mapped) {
+        std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, stream); rt_sync(stream);
+        uint64_t total = 0; for (uint32_t c : counts) total += c;
+        spb_check_entries(total);
+    }
+    const uint32_t kept = spb_scan_and_allocate(stream, side, nSides, allocVals);
+    // (the sides now carry their vals: the references above see them)
+    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, stream, cin, dm.keep, mp, a, b);
+    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, stream, in, mp, a, b);
+    return kept;
+}
+
 // Both samplers of a sparse-model session from a checked matrix in device memory, with or without a subset of its rows or columns
 // (sparse_build.h, the map and the mapped passes): THE builder of the sparse model, whatever form the input had.  subset: subsetData's
 // 1-based indices, or null -- also for a caller that has applied them already.  One read of the entries per mapped pass; the session's
@@ -657,23 +688,8 @@ static void build_samplers_device_matrix(cogaps_session *s, const SpbMatrix &dm,
         RT_LAUNCH(spb_map_fill_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, (const uint32_t *)start, cursor, list);
         mp.start = start; mp.list = list;
     }
-    SpbIn in; CooIn cin;
-    in.nMajor = dm.nMajor(); in.nMinor = dm.nMinor(); in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
-    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
-    const uint32_t sliceGrid = (in.nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, s->computeUnits, COO_BS);
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, s->stream, cin, dm.keep, mp, side[0], side[1]);
-    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
-    for (int w = 0; w < 2; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, s->stream, side[w]);
-    if (subset) {
-        // an entry has as many images as its index repeats in the subset: the total in 64 bits before the 32-bit scan (without a
-        // subset it cannot exceed nnz)
-        std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, s->stream); rt_sync(s->stream);
-        uint64_t total = 0; for (uint32_t c : counts) total += c;
-        spb_check_entries(total);
-    }
-    const uint32_t kept = spb_scan_and_allocate(s, side, hs);
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, s->stream, cin, dm.keep, mp, side[0], side[1]);
-    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, s->stream, in, mp, side[0], side[1]);
+    const uint32_t kept = spb_build_sides(dm, mp, subset != nullptr, side, 2, s->computeUnits, s->stream,
+                                          [&](int w, size_t n) { float *v = dalloc<float>(n); hs[w]->d.dvals = v; return v; });
     spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
 }
 
@@ -1569,6 +1585,141 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
         if (markers) rt_d2h(markers, p.markers, nOut * 4, g.st);
         if (markerCount) rt_d2h(markerCount, p.markerCount, (size_t)L * 4, g.st);
         rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result statistics: residuals and the chi-square of every gene and sample (residual_kernel.h)
+// ------------------------------------------------------------------------------------------------
+} // extern "C"
+
+static std::string rs_dims(const char *what, uint64_t has, const char *of, uint64_t wants)
+{
+    return std::string("cogaps_residuals: the data has ") + std::to_string(has) + " " + what + ", " + of + " has " + std::to_string(wants) + " rows";
+}
+
+extern "C" {
+
+int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t aColStride,
+                     const float *p, uint32_t nSamples, size_t pRowStride, size_t pColStride, uint32_t nPatterns,
+                     const cogaps_residual_data *data, const uint32_t *rows, uint32_t nRowsOut, int device,
+                     double *geneChiSq, double *sampleChiSq, double *chiSq, double *matrixOut, uint64_t *peakDeviceBytes)
+{
+    try {
+        const uint32_t G = nGenes, N = nSamples, K = nPatterns;
+        if (!a || !p) return fail("cogaps_residuals: null argument");
+        if (G == 0u || N == 0u || K == 0u) return fail("cogaps_residuals: a matrix is empty");
+        if (G > 0xFFFFFF00u) return fail("cogaps_residuals: " + std::to_string(G) + " genes are more than the blocks of 64 count in 32 bits");
+        if ((rows == nullptr) != (nRowsOut == 0u) || (nRowsOut != 0u && !matrixOut)) return fail("cogaps_residuals: rows, their number and matrixOut must be given together");
+        for (uint32_t x = 0; x < nRowsOut; ++x)
+            if (rows[x] >= G) return fail("cogaps_residuals: output row " + std::to_string(x) + " asks for gene " + std::to_string(rows[x]) + ", the result has " + std::to_string(G));
+        const int kind = data ? data->kind : COGAPS_RESIDUAL_DATA_NONE;
+        if (kind == COGAPS_RESIDUAL_DATA_NONE && nRowsOut == 0u) return fail("cogaps_residuals: neither data nor rows: nothing to compute");
+        const cogaps_device_matrix *handle = nullptr;
+        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
+            uint32_t dr = 0, dc = 0;
+            if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
+                if (!data->dense) return fail("cogaps_residuals: null argument: dense");
+                dr = data->nrow; dc = data->ncol;
+            } else if (kind == COGAPS_RESIDUAL_DATA_SPARSE || kind == COGAPS_RESIDUAL_DATA_COO) {
+                const cogaps_sparse_matrix *sp = kind == COGAPS_RESIDUAL_DATA_SPARSE ? data->sparse : nullptr;
+                const cogaps_coo_matrix *coo = kind == COGAPS_RESIDUAL_DATA_COO ? data->coo : nullptr;
+                if (!sp && !coo) return fail("cogaps_residuals: null argument: the matrix");
+                if (const char *refusal = sparse_args_refusal(sp, coo)) return fail(refusal);
+                dr = sp ? sp->nrow : coo->nrow; dc = sp ? sp->ncol : coo->ncol;
+            } else if (kind == COGAPS_RESIDUAL_DATA_DEVICE_MATRIX) {
+                handle = data->deviceMatrix;
+                if (!handle) return fail("cogaps_residuals: null argument: deviceMatrix");
+                if (device != -1 && device != handle->device)
+                    return fail("cogaps_residuals: the matrix resides on device " + std::to_string(handle->device) + ", the call was given device " + std::to_string(device));
+                device = handle->device;
+                dr = handle->m.nrow; dc = handle->m.ncol;
+            } else return fail("cogaps_residuals: unknown kind of data " + std::to_string(kind));
+            if (kind != COGAPS_RESIDUAL_DATA_DENSE && data->uncertainty)
+                return fail("cogaps_residuals: a sparse matrix takes the default uncertainty only (no uncertainty matrix)");
+            const uint32_t dG = data->transposeData ? dc : dr, dN = data->transposeData ? dr : dc;
+            if (dG != G) return fail(rs_dims("genes", dG, "featureLoadings", G));
+            if (dN != N) return fail(rs_dims("samples", dN, "sampleFactors", N));
+        }
+        const uint32_t nSteps = (uint32_t)(((uint64_t)N + 63u) / 64u), nBlocks = (G + (uint32_t)RS_BLOCK - 1u) / (uint32_t)RS_BLOCK;
+        const size_t ldp = (size_t)nSteps * 64u;
+        // A widened row by row (rows of zeros up to whole blocks), P widened and transposed (zeros past the last sample); the output rows that want each gene
+        std::vector<double> a64((size_t)nBlocks * RS_BLOCK * K, 0.0), pt64((size_t)K * ldp, 0.0);
+        for (size_t i = 0; i < G; ++i)
+            for (size_t k = 0; k < K; ++k) a64[i * K + k] = (double)a[i * aRowStride + k * aColStride];
+        for (size_t j = 0; j < N; ++j)
+            for (size_t k = 0; k < K; ++k) pt64[k * ldp + j] = (double)p[j * pRowStride + k * pColStride];
+        std::vector<uint32_t> outStart, outList(nRowsOut);
+        if (nRowsOut) {
+            outStart.assign((size_t)G + 1u, 0u);
+            for (uint32_t x = 0; x < nRowsOut; ++x) ++outStart[(size_t)rows[x] + 1u];
+            for (size_t i = 0; i < G; ++i) outStart[i + 1u] += outStart[i];
+            std::vector<uint32_t> cursor(outStart.begin(), outStart.end() - 1);
+            for (uint32_t x = 0; x < nRowsOut; ++x) outList[cursor[rows[x]]++] = x;
+        }
+
+        rt_alloc_meter meter;                                                // (outlives everything the call allocates)
+        rt_meter_scope metered(&meter);
+        GsScratch g(device);
+        rt_alloc_scope allocOn(g.st);
+        SpbTemps tmp;
+        RsArgs r;
+        memset(&r, 0, sizeof(r));
+        r.G = G; r.N = N; r.K = K; r.nSteps = nSteps; r.ldp = ldp; r.source = RS_DATA_NONE;
+        double *da = g.get<double>(a64.size()), *dp = g.get<double>(pt64.size());
+        rt_h2d(da, a64.data(), a64.size() * 8, g.st); rt_h2d(dp, pt64.data(), pt64.size() * 8, g.st);
+        r.a64 = da; r.pt64 = dp;
+        if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
+            r.source = RS_DATA_DENSE;
+            r.rowStride = data->transposeData ? data->colStride : data->rowStride;
+            r.colStride = data->transposeData ? data->rowStride : data->colStride;
+            r.data = data->dense; r.unc = data->uncertainty;
+            if (!data->onDevice) {      // the caller's arrays as they lie, from the first element to the last the strides reach
+                const size_t span = (size_t)(G - 1u) * r.rowStride + (size_t)(N - 1u) * r.colStride + 1u;
+                float *dd = g.get<float>(span); rt_h2d(dd, data->dense, span * 4, g.st); r.data = dd;
+                if (data->uncertainty) { float *du = g.get<float>(span); rt_h2d(du, data->uncertainty, span * 4, g.st); r.unc = du; }
+            }
+        } else if (kind != COGAPS_RESIDUAL_DATA_NONE) {
+            // the gene side of the sparse model's packed form, by the one builder; nothing of size genes x samples exists
+            SpbMatrix staged; const SpbMatrix *src = &staged;
+            const unsigned cu = rt_compute_units();
+            if (kind == COGAPS_RESIDUAL_DATA_SPARSE) {
+                const cogaps_sparse_matrix &m = *data->sparse;
+                spb_compressed(staged, m, g.st, [&](auto *from, size_t n) { return tmp.stage(from, n, m.onDevice != 0, g.st); });
+            } else if (kind == COGAPS_RESIDUAL_DATA_COO) {
+                const cogaps_coo_matrix &m = *data->coo;
+                spb_triplets(staged, m, tmp.alloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), cu, g.st,
+                             [&](auto *from, size_t n) { return tmp.stage(from, n, m.onDevice != 0, g.st); });
+            } else src = &handle->m;
+            SpbSide side;
+            side.M = G; side.Wn = N / 64u + 1u; side.vals = nullptr;
+            side.swap = (data->transposeData == 0) == src->majorIsRow ? 0u : 1u;      // genes are the data's rows unless transposeData
+            side.flags = g.get<unsigned long long>((size_t)G * side.Wn); side.prefix = g.get<uint32_t>((size_t)G * side.Wn); side.ptr = g.get<uint32_t>((size_t)G + 1u);
+            SpbMap identity; identity.start = identity.list = nullptr; identity.onMajor = 0u;
+            spb_build_sides(*src, identity, false, &side, 1, cu, g.st, [&](int, size_t n) { return g.get<float>(n); });
+            r.source = RS_DATA_PACKED; r.side = side;
+        }
+        double *dSample = nullptr, *dChi = nullptr;
+        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
+            r.geneChiSq = g.get<double>(G); r.partial = g.get<double>((size_t)nBlocks * ldp);
+            dSample = g.get<double>(N); dChi = g.get<double>(1);
+        }
+        if (nRowsOut) {
+            uint32_t *dStart = g.get<uint32_t>(outStart.size()), *dList = g.get<uint32_t>(nRowsOut);
+            rt_h2d(dStart, outStart.data(), outStart.size() * 4, g.st); rt_h2d(dList, outList.data(), (size_t)nRowsOut * 4, g.st);
+            r.outStart = dStart; r.outList = dList; r.matrixOut = g.get<double>((size_t)nRowsOut * N);
+        }
+        RT_LAUNCH(rs_main_kernel, gs_grid(nBlocks), RS_THREADS, g.st, r);
+        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
+            RT_LAUNCH(rs_fold_kernel, (uint32_t)(((uint64_t)N + RS_THREADS - 1u) / RS_THREADS) + 1u, RS_THREADS, g.st, r, dSample, dChi);
+            if (geneChiSq) rt_d2h(geneChiSq, r.geneChiSq, (size_t)G * 8, g.st);
+            if (sampleChiSq) rt_d2h(sampleChiSq, dSample, (size_t)N * 8, g.st);
+            if (chiSq) rt_d2h(chiSq, dChi, 8, g.st);
+        }
+        if (nRowsOut) rt_d2h(matrixOut, r.matrixOut, (size_t)nRowsOut * N * 8, g.st);
+        rt_sync(g.st);
+        if (peakDeviceBytes) *peakDeviceBytes = meter.peak.load();
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

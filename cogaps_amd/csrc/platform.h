@@ -12,6 +12,15 @@
 #if defined(COGAPS_EMUL)
 #include "emul_runtime.h"   // tests/emul/
 inline uint32_t cg_load_l2_u32(const uint32_t *p) { return *p; }      // beside emul_runtime.h's cg_load_l2_u64: one thread, plain loads
+// the fp64 counterpart of emul_runtime.h's cg_shfl_xor_f32: the two halves as bit patterns, one 32-bit exchange each (as its
+// cg_wave_sum_u32 carries integers through the float exchange)
+inline double cg_shfl_xor_f64(double v, int mask)
+{
+    uint32_t w[2]; memcpy(w, &v, 8);
+    for (int h = 0; h < 2; ++h) { float f; memcpy(&f, &w[h], 4); const float g = cgemu::wave_exchange_f32(f, mask); memcpy(&w[h], &g, 4); }
+    double r; memcpy(&r, w, 8); return r;
+}
+inline double cg_fma_f64(double a, double b, double c) { return __builtin_fma(a, b, c); }      // a * b + c rounded once
 #else
 #include <hip/hip_runtime.h>
 
@@ -155,6 +164,9 @@ CG_DEVICE unsigned long long cg_realtime() { return __builtin_amdgcn_s_memrealti
 CG_DEVICE bool cg_poll_expired(uint32_t spins) { return spins > (1u << 22); }
 CG_DEVICE float cg_shfl_xor_f32(float v, int mask) { return __shfl_xor(v, mask, 64); }
 CG_DEVICE float cg_shfl_f32(float v, int lane) { return __shfl(v, lane, 64); }
+CG_DEVICE double cg_shfl_xor_f64(double v, int mask) { return __shfl_xor(v, mask, 64); }
+// a * b + c rounded once (the build contracts nothing by itself: -ffp-contract=off)
+CG_DEVICE double cg_fma_f64(double a, double b, double c) { return __builtin_fma(a, b, c); }
 // the value lane `lane` holds (lane: the same in every lane of the wave) -- a lane read instead of an LDS-crossbar permute
 CG_DEVICE float cg_lane_read_f32(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
 // Sum over the 64 lanes in the order of the ascending xor butterfly (x += x[lane ^ 1], ^ 2, ... ^ 32), the same

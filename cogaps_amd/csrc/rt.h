@@ -116,20 +116,34 @@ inline const char *rt_platform_name() { return "HIP gfx950"; }
 // Device memory with an owner (cogaps_session_device_bytes): an allocation made while the calling thread has announced a byte counter
 // (rt_owner_scope: a session's) adds its size to that counter, its release takes it off again -- whichever thread releases it.  Sizes are
 // the requested ones.  The counter must outlive the allocations it owns (a session frees its memory before it goes).
-struct rt_alloc_book { std::mutex m; std::unordered_map<void *, std::pair<size_t, std::atomic<uint64_t> *>> live; };
+// A meter (cogaps_residuals' peakDeviceBytes) sees every allocation its thread makes while it is announced (rt_meter_scope), owned or not:
+// the bytes held now and the most held at once.  Like an owner's counter, the meter must outlive the allocations it has seen: their
+// release reaches it through the book, whichever thread releases them (cogaps_residuals declares it before everything that allocates).
+struct rt_alloc_meter { std::atomic<uint64_t> held{0}, peak{0}; };
+struct rt_alloc_entry { size_t bytes; std::atomic<uint64_t> *owner; rt_alloc_meter *meter; };
+struct rt_alloc_book { std::mutex m; std::unordered_map<void *, rt_alloc_entry> live; };
 inline rt_alloc_book &rt_book() { static rt_alloc_book b; return b; }
 inline std::atomic<uint64_t> *&rt_owner_slot() { static thread_local std::atomic<uint64_t> *o = nullptr; return o; }
+inline rt_alloc_meter *&rt_meter_slot() { static thread_local rt_alloc_meter *m = nullptr; return m; }
 struct rt_owner_scope {
     std::atomic<uint64_t> *prev;
     explicit rt_owner_scope(std::atomic<uint64_t> *o) : prev(rt_owner_slot()) { rt_owner_slot() = o; }
     ~rt_owner_scope() { rt_owner_slot() = prev; }
 };
+struct rt_meter_scope {
+    rt_alloc_meter *prev;
+    explicit rt_meter_scope(rt_alloc_meter *m) : prev(rt_meter_slot()) { rt_meter_slot() = m; }
+    ~rt_meter_scope() { rt_meter_slot() = prev; }
+};
 inline void *rt_malloc(size_t n)
 {
     void *p = rt_malloc_raw(n);
-    if (std::atomic<uint64_t> *o = rt_owner_slot()) {
+    std::atomic<uint64_t> *o = rt_owner_slot(); rt_alloc_meter *mt = rt_meter_slot();
+    if (o || mt) {
         std::lock_guard<std::mutex> g(rt_book().m);
-        rt_book().live[p] = {n, o}; o->fetch_add(n);
+        rt_book().live[p] = {n, o, mt};
+        if (o) o->fetch_add(n);
+        if (mt) { const uint64_t now = mt->held.fetch_add(n) + n; if (now > mt->peak.load()) mt->peak.store(now); }
     }
     return p;
 }
@@ -139,7 +153,11 @@ inline void rt_free(void *p)
     {
         std::lock_guard<std::mutex> g(rt_book().m);
         auto it = rt_book().live.find(p);
-        if (it != rt_book().live.end()) { it->second.second->fetch_sub(it->second.first); rt_book().live.erase(it); }
+        if (it != rt_book().live.end()) {
+            if (it->second.owner) it->second.owner->fetch_sub(it->second.bytes);
+            if (it->second.meter) it->second.meter->held.fetch_sub(it->second.bytes);
+            rt_book().live.erase(it);
+        }
     }
     rt_free_raw(p);
 }

@@ -225,16 +225,17 @@ template <bool STORE>
 CG_DEVICE void spb_mapped_entry(const SpbMap &mp, const SpbSide &a, const SpbSide &b, uint32_t major, uint32_t minor, float v)
 {
     const bool mapped = mp.start != nullptr;
+    const bool two = b.flags != a.flags;      // (one side alone is given as both: cogaps_residuals' gene side)
     const uint32_t c = mp.onMajor ? major : minor;
     const uint32_t lo = mapped ? mp.start[c] : 0u, hi = mapped ? mp.start[c + 1u] : 1u;
     for (uint32_t q = lo; q < hi; ++q) {
         const uint32_t img = mapped ? mp.list[q] : c;
         const uint32_t mj = mp.onMajor ? img : major, mn = mp.onMajor ? minor : img;
-        if (STORE) { spb_store(a, mj, mn, v); spb_store(b, mj, mn, v); }
+        if (STORE) { spb_store(a, mj, mn, v); if (two) spb_store(b, mj, mn, v); }
         else {
             uint32_t vec, el;
             spb_place(a, mj, mn, vec, el); cg_atomic_or_u64(a.flags + (size_t)vec * a.Wn + (el >> 6), 1ull << (el & 63u));
-            spb_place(b, mj, mn, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u));
+            if (two) { spb_place(b, mj, mn, vec, el); cg_atomic_or_u64(b.flags + (size_t)vec * b.Wn + (el >> 6), 1ull << (el & 63u)); }
         }
     }
 }

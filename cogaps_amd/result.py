@@ -6,7 +6,11 @@ come from the library's keyed draw, not from R's sample() stream; a set none of 
 set with one matching row uses that row where R fails), and patternMarkers -- every gene (or sample) ranked by its distance to each
 pattern, and the marker lists, on the GPU as well (cogaps_pattern_markers; DESIGN.md 4.9: all-zero rows rank last and mark nothing
 where R breaks on their NA, a column none of whose rows ranks better elsewhere gives every row where R fails, a wrong lp length is an
-error).  calcGeneGSStat, computeGeneGSProb, getPatternGeneSet and the plots are out of scope."""
+error), and reconstructGene, residuals -- plotResiduals' matrix, with the chi-square of every gene, every sample and the whole fit
+beside it -- and binaryA: how well the result fits its data, on the GPU for dense and for sparse data, which is never densified
+(cogaps_residuals; DESIGN.md 4.10: fp64 on the widened fp32 factors in fixed orders; the default uncertainty is R's pmax(0.1 * data,
+0.1) in double; genes select rows in the order given where R's NULL means all).  calcGeneGSStat, computeGeneGSProb, getPatternGeneSet
+and the plots themselves are out of scope."""
 import warnings
 
 import numpy as np
@@ -178,6 +182,92 @@ class CogapsResult:
         else:
             lists = [[int(i) + 1 for i in r] for r in rows]
         return {"PatternMarkers": dict(zip(labels, lists)), "PatternRanks": ranks.astype(np.int64), "PatternScores": scores, "patterns": labels}
+
+    def _gene_rows(self, genes):
+        """-> (0-based rows in the order given, their labels); genes: names or 1-based indices, never both; None: every gene"""
+        G = np.asarray(self.featureLoadings).shape[0]
+        if genes is None:
+            rows = np.arange(G, dtype=np.int64)
+        else:
+            if isinstance(genes, (str, bytes)) or not hasattr(genes, "__iter__"):
+                genes = [genes]
+            flat = [x.item() if isinstance(x, np.generic) else x for x in genes]
+            by_name = [isinstance(x, str) for x in flat]
+            if not flat:
+                raise ValueError("genes is empty")
+            if all(by_name):
+                if self.geneNames is None:
+                    raise ValueError("genes holds names but the result carries no geneNames")
+                lookup = {}
+                for i, nm in enumerate(self.geneNames):
+                    lookup.setdefault(nm, i)
+                for x in flat:
+                    if x not in lookup:
+                        raise ValueError("unknown gene name: %s" % x)
+                rows = np.array([lookup[x] for x in flat], dtype=np.int64)
+            elif all(_is_index(x) for x in flat):
+                if any(x < 1 or x > G for x in flat):
+                    raise ValueError("genes holds an index outside 1 .. %d" % G)
+                rows = np.array(flat, dtype=np.int64) - 1
+            else:
+                raise ValueError("genes must be all indices or all names")
+        labels = [self.geneNames[i] for i in rows] if self.geneNames is not None else [int(i) + 1 for i in rows]
+        return rows, labels
+
+    def reconstructGene(self, genes=None, lib=None):
+        """R/methods-CogapsResult.R:233-244 on the GPU: featureLoadings %*% t(sampleFactors) in float64, the rows of `genes` (names or
+        1-based indices, in the order given, repeats allowed; None: all) -> float64 [rows][samples].  DESIGN.md 4.10 fixes the order
+        of the sum."""
+        from . import _capi
+        rows, _ = self._gene_rows(genes)
+        return _capi.residuals(self.featureLoadings, self.sampleFactors, rows=rows, lib=lib)["matrix"]
+
+    def residuals(self, data, uncertainty=None, genes=None, matrix=True, transposeData=False, lib=None):
+        """The matrix of R/methods-CogapsResult.R:265-286 (plotResiduals, without the plot) on the GPU: (data - M) / uncertainty in
+        float64, the uncertainty defaulting to pmax(0.1 * data, 0.1), and what the library adds to it: the sum of the squared
+        residuals of every gene, of every sample and of the whole fit (DESIGN.md 4.10 fixes every order).  data: whatever CoGAPS()
+        takes -- a numpy array, a torch tensor (one on the GPU stays there), a scipy.sparse matrix or a DeviceMatrix (neither is
+        densified; the default uncertainty only), a file path (.mtx: read as triplets and kept sparse) -- genes x samples unless
+        transposeData, under CoGAPS()'s input checks.  genes: the rows of the residual matrix to return, as for reconstructGene;
+        matrix=False: none.  -> {"residuals": float64 [rows][samples] or None, "geneChiSq", "sampleChiSq", "chiSq", "genes": the
+        rows' labels}"""
+        from . import _capi
+        from .api import check_values, warn_small_uncertainty
+        from .io import read_matrix
+        if isinstance(data, str):
+            data = _capi.read_mtx_triplets(data, lib=lib) if data.lower().endswith(".mtx") else read_matrix(data)
+        if isinstance(uncertainty, str):
+            uncertainty = read_matrix(uncertainty)
+        sparse = isinstance(data, (_capi.SparseMatrix, _capi.CooMatrix, _capi.DeviceMatrix)) or _capi.is_sparse(data)
+        if sparse and uncertainty is not None:
+            raise ValueError("a sparse matrix takes no uncertainty matrix: the default uncertainty only")
+        if _capi.is_sparse(data):
+            data = data.astype(np.float32)
+        elif not sparse and not _capi.is_tensor(data):
+            data = np.asarray(data, dtype=np.float32)
+        if uncertainty is not None and not _capi.is_tensor(uncertainty):
+            uncertainty = np.asarray(uncertainty, dtype=np.float32)
+        check_values(data, uncertainty)               # CoGAPS()'s own: NA, negative values ...
+        warn_small_uncertainty(uncertainty)           # ... and the warning for uncertainties below 1e-5
+        rows, labels = self._gene_rows(genes) if matrix else (None, [])
+        out = _capi.residuals(self.featureLoadings, self.sampleFactors, data=data, unc=uncertainty, rows=rows, transposeData=transposeData, lib=lib)
+        return {"residuals": out["matrix"], "geneChiSq": out["geneChiSq"], "sampleChiSq": out["sampleChiSq"], "chiSq": out["chiSq"], "genes": labels}
+
+    def binaryA(self, threshold):
+        """R/methods-CogapsResult.R:246-263 without the heatmap: 1 where calcZ() of featureLoadings exceeds threshold, 0 elsewhere"""
+        return (self.calcZ() > threshold).astype(np.int8)
+
+
+def reconstructGene(result, genes=None, **kw):
+    return result.reconstructGene(genes, **kw)
+
+
+def residuals(result, data, uncertainty=None, genes=None, matrix=True, transposeData=False, **kw):
+    return result.residuals(data, uncertainty=uncertainty, genes=genes, matrix=matrix, transposeData=transposeData, **kw)
+
+
+def binaryA(result, threshold):
+    return result.binaryA(threshold)
 
 
 def patternMarkers(result, threshold="all", lp=None, axis=1, **kw):

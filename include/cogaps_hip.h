@@ -526,6 +526,63 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
                            const double *lp, uint32_t nLp, int threshold, int device,
                            uint32_t *ranks, double *scores, uint32_t *markers, uint32_t *markerCount);
 
+/* ------------------------------------------------------------------------------------------------
+ * Result statistics: residuals -- the reference's reconstructGene and the matrix of its plotResiduals (R/methods-CogapsResult.R:233-286;
+ * DESIGN.md 4.10) -- and the chi-square of every gene, of every sample and of the whole fit.
+ *
+ * a: featureLoadings, nGenes x nPatterns floats in host memory, element (i, k) at a[i * aRowStride + k * aColStride]; p: sampleFactors,
+ * nSamples x nPatterns, through its own strides (rowStride = nPatterns, colStride = 1 for a row-major matrix; rowStride = 1, colStride
+ * = rows for R's column-major one).  All arithmetic is fp64 on the exactly widened floats, D the data, S the uncertainty:
+ *   M[i][j] = sum over k, ascending from +0.0, of A[i][k] * P[j][k], one fused multiply-add each (the product of two widened floats
+ *             is exact in fp64, so a multiply followed by an add gives the same bits)
+ *   s[i][j] = S[i][j], or max(0.1 * D[i][j], 0.1) in double without an uncertainty (R's pmax; not the sampler's fp32 fill)
+ *   r[i][j] = (D[i][j] - M[i][j]) / s[i][j]                 q = r * r
+ *   geneChiSq[i]   = the 64 sums t[L] = q[i][L] + q[i][L + 64] + ... (ascending j, from +0.0), folded by the ascending xor butterfly:
+ *                    t[L] += t[L ^ 1], then ^ 2, ^ 4, ^ 8, ^ 16, ^ 32
+ *   sampleChiSq[j] = the sums of q[i][j] over the genes of block b = i / 64 (ascending i, from +0.0), added in ascending b from +0.0
+ *   chiSq          = geneChiSq[0] + geneChiSq[1] + ... from +0.0
+ * No output depends on the device, on the grid or on scheduling; each can be recomputed bit for bit.
+ *
+ * data: what the fit is compared with, or NULL / kind COGAPS_RESIDUAL_DATA_NONE for M alone (the three chi-square outputs are then
+ * left untouched).  transposeData: the data's rows are samples.  The data's dimensions must be those of a and p: a message names both
+ * numbers otherwise.
+ *   _DENSE          dense (and uncertainty, or NULL for the default): element (row, col) at [row * rowStride + col * colStride], both
+ *                   through the same strides, nrow x ncol; onDevice = 1: device pointers of `device`, read where they lie
+ *   _SPARSE / _COO  sparse / coo (host or device pointers, as their own onDevice says): the entries > 0, absent positions are 0, the
+ *                   latest triplet of a position decides; validated as for a session
+ *   _DEVICE_MATRIX  deviceMatrix: a handle's matrix, on the handle's device (device: -1 or that one)
+ * The three sparse kinds take the default uncertainty only (a given one is refused).  They go through the sparse model's one builder
+ * (csrc/sparse_build.h) for the gene side of its packed form -- flag words, prefix counts, pointers, packed values -- which the kernel
+ * reads: without output rows such a call allocates nothing of the size nGenes x nSamples.
+ *
+ * rows: nRowsOut 0-based genes, any order, repeats allowed; matrixOut [nRowsOut][nSamples] doubles receives their rows of r (of M
+ * without data).  NULL with 0: no rows.  geneChiSq [nGenes], sampleChiSq [nSamples], chiSq [1]: each may be NULL.  peakDeviceBytes
+ * (may be NULL): the most device memory the call held at once beyond the caller's own device arrays and handle.  device: -1 for the
+ * calling thread's current one (it is restored before the call returns).  Refused, with a message: a or p NULL, an empty matrix, rows
+ * without matrixOut, a row that is no gene, neither data nor rows, an unknown kind, a NULL matrix of the stated kind, dimensions
+ * that disagree, an uncertainty beside a sparse kind, a device other than the handle's, and what the sparse entries refuse.
+ * ---------------------------------------------------------------------------------------------- */
+#define COGAPS_RESIDUAL_DATA_NONE 0
+#define COGAPS_RESIDUAL_DATA_DENSE 1
+#define COGAPS_RESIDUAL_DATA_SPARSE 2
+#define COGAPS_RESIDUAL_DATA_COO 3
+#define COGAPS_RESIDUAL_DATA_DEVICE_MATRIX 4
+typedef struct cogaps_residual_data {
+    int32_t  kind;                        /* COGAPS_RESIDUAL_DATA_* */
+    int32_t  transposeData;               /* 0: genes x samples, 1: samples x genes */
+    uint32_t nrow, ncol;                  /* dense: of the data as the caller holds it */
+    const float *dense, *uncertainty;     /* dense: the data; its uncertainty or NULL */
+    size_t   rowStride, colStride;        /* dense: of both, in elements */
+    int32_t  onDevice;                    /* dense: 0 host pointers, 1 device pointers */
+    const cogaps_sparse_matrix *sparse;
+    const cogaps_coo_matrix *coo;
+    const cogaps_device_matrix *deviceMatrix;
+} cogaps_residual_data;
+int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t aColStride,
+                     const float *p, uint32_t nSamples, size_t pRowStride, size_t pColStride, uint32_t nPatterns,
+                     const cogaps_residual_data *data, const uint32_t *rows, uint32_t nRowsOut, int device,
+                     double *geneChiSq, double *sampleChiSq, double *chiSq, double *matrixOut, uint64_t *peakDeviceBytes);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
