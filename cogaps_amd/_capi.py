@@ -99,7 +99,7 @@ EXPORTS = [
     "cogaps_session_get_atoms", "cogaps_session_dims", "cogaps_session_avg_queue",
     "cogaps_session_finish", "cogaps_session_set_timing", "cogaps_session_perf",
     "cogaps_session_perf_sampler", "cogaps_session_chained", "cogaps_session_chain_recoveries", "cogaps_session_generator_window", "cogaps_session_launch_clock", "cogaps_session_launch_period", "cogaps_session_get_rows", "cogaps_sparse_width", "cogaps_reduction_width", "cogaps_session_debug_prof", "cogaps_session_debug_replay",
-    "cogaps_run_from_file", "cogaps_read_matrix_file", "cogaps_read_matrix_file_subset", "cogaps_matrix_free", "cogaps_file_info", "cogaps_debug_math", "cogaps_current_device", "cogaps_device_memory",
+    "cogaps_run_from_file", "cogaps_read_matrix_file", "cogaps_read_matrix_file_subset", "cogaps_matrix_free", "cogaps_file_info", "cogaps_debug_math", "cogaps_debug_udiv64", "cogaps_debug_uniform64", "cogaps_current_device", "cogaps_device_memory",
     "cogaps_session_create_sparse", "cogaps_run_sparse", "cogaps_session_device_bytes", "cogaps_session_sparse_build_ms", "cogaps_session_debug_sparse_data",
     "cogaps_session_create_coo", "cogaps_run_coo", "cogaps_read_mtx_triplets", "cogaps_triplets_free",
     "cogaps_device_matrix_create_sparse", "cogaps_device_matrix_create_coo", "cogaps_device_matrix_destroy", "cogaps_device_matrix_info",
@@ -219,6 +219,9 @@ def bind(L):
     L.cogaps_matrix_free.restype = None
     L.cogaps_file_info.argtypes = [C.c_char_p, u32p, u32p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cogaps_debug_math.argtypes = [C.c_int, C.c_int, fp, fp, C.c_uint32, C.c_int]
+    if hasattr(L, "cogaps_debug_udiv64"):      # (an A/B build of an older source tree lacks the two)
+        L.cogaps_debug_udiv64.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.c_uint32, C.c_int]
+        L.cogaps_debug_uniform64.argtypes = [C.POINTER(C.c_uint64)] * 5 + [C.c_uint32, C.c_int]
     L.cogaps_current_device.argtypes = [C.POINTER(C.c_int)]
     L.cogaps_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.cogaps_session_debug_check_domain.argtypes = [vp, C.c_char, u32p]
@@ -960,6 +963,32 @@ def debug_math(fn, x, mathMode="portable", on_device=False, lib=None):
     if L.cogaps_debug_math({"log": 0, "exp": 1}[fn], _MATH[mathMode] if isinstance(mathMode, str) else int(mathMode), _fp(xs), _fp(ys), xs.size, int(on_device)):
         raise _error(L)
     return ys
+
+
+def debug_udiv64(a, b, on_device=False, lib=None):
+    """gm_udiv64(a[i], b[i]) (csrc/gaps_math.h; every b >= 1), on the device or from the same source on the host -> uint64 array"""
+    L = lib if lib is not None else load()
+    u64p = C.POINTER(C.c_uint64)
+    a, b = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1), np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("one divisor per dividend")
+    q = np.zeros_like(a)
+    if L.cogaps_debug_udiv64(a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), q.ctypes.data_as(u64p), a.size, int(on_device)):
+        raise _error(L)
+    return q
+
+
+def debug_uniform64(state, lo, hi, on_device=False, lib=None):
+    """pcg_uniform64(state[i], lo[i], hi[i]) (csrc/gaps_math.h) -> (values, generator states after the draw), uint64 arrays"""
+    L = lib if lib is not None else load()
+    u64p = C.POINTER(C.c_uint64)
+    s, lo, hi = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (state, lo, hi))
+    if not (s.size == lo.size == hi.size):
+        raise ValueError("one state per range")
+    v, after = np.zeros_like(s), np.zeros_like(s)
+    if L.cogaps_debug_uniform64(s.ctypes.data_as(u64p), lo.ctypes.data_as(u64p), hi.ctypes.data_as(u64p), v.ctypes.data_as(u64p), after.ctypes.data_as(u64p), s.size, int(on_device)):
+        raise _error(L)
+    return v, after
 
 
 def gene_set_stat(z, members, sizes, numPerm, seed=0, device=-1, lib=None):

@@ -1338,6 +1338,18 @@ CG_KERNEL void debug_math_kernel(int fn, uint32_t mode, const float *x, float *y
     if (i < n) y[i] = fn ? gm_expf_m(x[i], mode) : gm_logf_m(x[i], mode);
 }
 
+CG_KERNEL void debug_udiv64_kernel(const uint64_t *a, const uint64_t *b, uint64_t *q, uint32_t n)
+{
+    const uint32_t i = cg_bid() * cg_bdim() + cg_tid();
+    if (i < n) q[i] = gm_udiv64(a[i], b[i]);
+}
+
+CG_KERNEL void debug_uniform64_kernel(const uint64_t *state, const uint64_t *lo, const uint64_t *hi, uint64_t *value, uint64_t *stateAfter, uint32_t n)
+{
+    const uint32_t i = cg_bid() * cg_bdim() + cg_tid();
+    if (i < n) { uint64_t s = state[i]; value[i] = pcg_uniform64(s, lo[i], hi[i]); stateAfter[i] = s; }
+}
+
 extern "C" {
 
 int cogaps_debug_math(int fn, int mathMode, const float *x, float *y, uint32_t n, int on_device)
@@ -1352,6 +1364,43 @@ int cogaps_debug_math(int fn, int mathMode, const float *x, float *y, uint32_t n
         RT_LAUNCH(debug_math_kernel, (n + 255u) / 256u, 256, st, fn, (uint32_t)mathMode, (const float *)dx, dy, n);
         rt_d2h(y, dy, (size_t)n * 4, st); rt_sync(st);
         rt_free(dx); rt_free(dy); rt_stream_destroy(st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+int cogaps_debug_udiv64(const uint64_t *a, const uint64_t *b, uint64_t *q, uint32_t n, int on_device)
+{
+    try {
+        if (!a || !b || !q) return fail("null argument");
+        for (uint32_t i = 0; i < n; ++i) if (b[i] == 0ull) return fail("gm_udiv64 needs a divisor >= 1");
+        if (!on_device) { for (uint32_t i = 0; i < n; ++i) q[i] = gm_udiv64(a[i], b[i]); return 0; }
+        if (n == 0u) return 0;
+        rt_stream_t st = rt_stream_create();
+        rt_alloc_scope allocOn(st);
+        uint64_t *da = dalloc<uint64_t>(n), *db = dalloc<uint64_t>(n), *dq = dalloc<uint64_t>(n);
+        rt_h2d(da, a, (size_t)n * 8, st); rt_h2d(db, b, (size_t)n * 8, st);
+        RT_LAUNCH(debug_udiv64_kernel, (n + 255u) / 256u, 256, st, (const uint64_t *)da, (const uint64_t *)db, dq, n);
+        rt_d2h(q, dq, (size_t)n * 8, st); rt_sync(st);
+        rt_free(da); rt_free(db); rt_free(dq); rt_stream_destroy(st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+int cogaps_debug_uniform64(const uint64_t *state, const uint64_t *lo, const uint64_t *hi, uint64_t *value, uint64_t *stateAfter, uint32_t n, int on_device)
+{
+    try {
+        if (!state || !lo || !hi || !value || !stateAfter) return fail("null argument");
+        // (a range of 0 values after the wrap would be divided by, and its rejection loop would never end)
+        for (uint32_t i = 0; i < n; ++i) if (hi[i] < lo[i] || hi[i] + 1ull - lo[i] == 0ull) return fail("pcg_uniform64 needs lo <= hi and fewer than 2^64 values");
+        if (!on_device) { for (uint32_t i = 0; i < n; ++i) { uint64_t s = state[i]; value[i] = pcg_uniform64(s, lo[i], hi[i]); stateAfter[i] = s; } return 0; }
+        if (n == 0u) return 0;
+        rt_stream_t st = rt_stream_create();
+        rt_alloc_scope allocOn(st);
+        uint64_t *ds = dalloc<uint64_t>(n), *dl = dalloc<uint64_t>(n), *dh = dalloc<uint64_t>(n), *dv = dalloc<uint64_t>(n), *dso = dalloc<uint64_t>(n);
+        rt_h2d(ds, state, (size_t)n * 8, st); rt_h2d(dl, lo, (size_t)n * 8, st); rt_h2d(dh, hi, (size_t)n * 8, st);
+        RT_LAUNCH(debug_uniform64_kernel, (n + 255u) / 256u, 256, st, (const uint64_t *)ds, (const uint64_t *)dl, (const uint64_t *)dh, dv, dso, n);
+        rt_d2h(value, dv, (size_t)n * 8, st); rt_d2h(stateAfter, dso, (size_t)n * 8, st); rt_sync(st);
+        rt_free(ds); rt_free(dl); rt_free(dh); rt_free(dv); rt_free(dso); rt_stream_destroy(st);
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

@@ -473,6 +473,12 @@ int cogaps_session_debug_check_domain(cogaps_session *s, char which, uint32_t *v
 /* test hook for the math modes: y[i] = fn(x[i]) with fn 0 = logf, 1 = expf in math mode `mathMode`, evaluated by a kernel on
  * the current device (on_device != 0) or by the same source compiled for the host */
 int cogaps_debug_math(int fn, int mathMode, const float *x, float *y, uint32_t n, int on_device);
+/* test hooks for the 64-bit integer draws (csrc/gaps_math.h), evaluated like cogaps_debug_math: q[i] = gm_udiv64(a[i], b[i]) (every
+ * b[i] >= 1), and value[i] = pcg_uniform64(s, lo[i], hi[i]) from the generator state s = state[i], with stateAfter[i] = s after the
+ * draw.  A range lo .. hi needs hi >= lo and fewer than 2^64 values: hi + 1 - lo wraps to 0 for the whole 64-bit range, by which the
+ * reference's GapsRng::uniform64 divides (Random.cpp:112-114) -- no caller asks for it, and the hook refuses it. */
+int cogaps_debug_udiv64(const uint64_t *a, const uint64_t *b, uint64_t *q, uint32_t n, int on_device);
+int cogaps_debug_uniform64(const uint64_t *state, const uint64_t *lo, const uint64_t *hi, uint64_t *value, uint64_t *stateAfter, uint32_t n, int on_device);
 
 /* ------------------------------------------------------------------------------------------------
  * Result statistics: the gene-set permutation test of the reference's calcCoGAPSStat (R/methods-CogapsResult.R:499-531).

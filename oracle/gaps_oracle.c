@@ -1,7 +1,8 @@
 /*
  * gaps_oracle.c -- CPU restatement (plain C) of the CoGAPS asynchronous Gibbs sampler:
  * ProposalQueue / ConcurrentAtomicDomain / DenseNormalModel / AsynchronousGibbsSampler /
- * runOnePhase / GapsStatistics, following the reference v3.27.4 under /root/reference/src.
+ * runOnePhase / GapsStatistics, following the reference v3.27.4 under /root/reference/src --
+ * and of its sequential one, SingleThreadedGibbsSampler over AtomicDomain (go_params.sampler).
  *
  * TEST INFRASTRUCTURE ONLY (see gaps_oracle.h).  The product never links this file.
  *
@@ -936,6 +937,9 @@ typedef struct go_sampler {
     const struct go_sampler *oth;       /* mOtherMatrix */
     float *Z1, *Z2;                     /* lookup tables, Z2 column-major K x K */
     float beta;
+    /* ---- sequential sampler: proposals that evaluated alpha parameters -- births (with canUseGibbs), deaths, moves and exchanges
+     * across matrix elements, and of the last two those across two rows; a position past the last bin was drawn ---- */
+    uint64_t seqCount[5]; int seqError;
 } go_sampler;
 
 /* lane-strided reduction (generalises SIMD.h PackedFloat: SIMD_INC lanes, here W lanes with G
@@ -1409,6 +1413,154 @@ static void sampler_update(go_sampler *sm, unsigned nSteps, unsigned nThreads, g
     }
 }
 
+/* ======================================================================================
+ * SingleThreadedGibbsSampler<DenseNormalModel> (gibbs_sampler/SingleThreadedGibbsSampler.h) over
+ * AtomicDomain (atomic/AtomicDomain.cpp): the reference's other sampler.  Every draw -- update type, site, masses,
+ * accept tests -- comes from the sampler's one generator (mRng, here queue.rng: seeded where the asynchronous
+ * sampler's queue seeds its own, one seeder output per sampler), and every change is applied at once: no queue, no
+ * conflict sets, no erase cache.  AtomicDomain is go_domain used without the cache: insert appends to `vec`
+ * (push_back, AtomicDomain.cpp:56-78), erase moves the last entry of `vec` into the hole at once (:80-111); atoms
+ * are addressed by handle here and by index there, which go_get_atoms translates.  mBinLength, mNumPatterns,
+ * mDomainLength, mNumBins and mAlpha (SingleThreadedGibbsSampler.h:73-79) are the queue's fields of the same
+ * values.  The model's functions (alpha_one / alpha_two, gibbs_mass, change_matrix / safely_change_matrix) are the
+ * asynchronous part's.
+ *
+ * One deviation, shared with the library: a position in the domain's last, partial stretch
+ * (uniform64's upper bound is inclusive) has the bin index nElements, with which the reference indexes past its
+ * matrix.  Here the update stops and go_seq_error() reports it.
+ * ====================================================================================== */
+
+/* (pos / mBinLength) / mNumPatterns and % mNumPatterns (:135-136, :158-159, :203-206, :236-239) */
+static int seq_site(go_sampler *sm, uint64_t pos, uint32_t *row, uint32_t *col)
+{
+    const go_queue *q = &sm->queue;
+    const uint64_t bin = pos / q->binLength;
+    if (bin >= (uint64_t)sm->M * sm->K) { sm->seqError = 1; return 0; }
+    *row = (uint32_t)(bin / q->numCols); *col = (uint32_t)(bin % q->numCols);
+    return 1;
+}
+/* SingleThreadedGibbsSampler.h:95-111 */
+static char seq_update_type(go_sampler *sm)
+{
+    go_queue *q = &sm->queue;
+    if (sm->dom.n < 2) return 'B';
+    float u1 = rng_uniform(&q->rng);
+    if (u1 < 0.5f) {
+        float deathProb = queue_death_prob(q, (double)sm->dom.n);
+        return rng_uniform(&q->rng) < deathProb ? 'D' : 'B';
+    }
+    return u1 < 0.75f ? 'M' : 'E';
+}
+/* SingleThreadedGibbsSampler.h:131-149 */
+static void seq_birth(go_sampler *sm)
+{
+    go_rng *rng = &sm->queue.rng;
+    uint64_t pos = dom_random_free_position(&sm->dom, rng);   /* AtomicDomain.cpp:41-49 */
+    uint32_t row, col;
+    if (!seq_site(sm, pos, &row, &col)) return;
+    optf mass;
+    if (can_use_gibbs(sm, col)) {
+        float s, smu; alpha_one(sm, row, col, NULL, &s, &smu);        /* sampleBirth, DenseNormalModel.cpp:132-136 */
+        s *= sm->annealTemp; smu *= sm->annealTemp;
+        mass = gibbs_mass(s, smu, 0.f, sm->maxGibbsMass, rng, 1, sm->lambda);
+        ++sm->seqCount[0];
+    } else {
+        mass = optf_some(rng_exponential(rng, sm->lambda));
+    }
+    if (mass.has && mass.v > GO_EPSILON) {
+        dom_insert(&sm->dom, pos, mass.v);
+        change_matrix(sm, row, col, mass.v);
+    }
+}
+/* SingleThreadedGibbsSampler.h:154-188 */
+static void seq_death(go_sampler *sm)
+{
+    go_rng *rng = &sm->queue.rng;
+    uint32_t h = sm->dom.vec[rng_uniform32(rng, 0, sm->dom.n - 1)];   /* randomAtom, AtomicDomain.cpp:24-29 */
+    go_atom *a = &sm->dom.pool[h];
+    uint32_t row, col;
+    if (!seq_site(sm, a->pos, &row, &col)) return;
+    float rebirthMass = a->mass;
+    float ch = -1.f * a->mass;
+    float s, smu; alpha_one(sm, row, col, &ch, &s, &smu);
+    s *= sm->annealTemp; smu *= sm->annealTemp;
+    ++sm->seqCount[1];
+    if (can_use_gibbs(sm, col)) {
+        optf g = gibbs_mass(s, smu, 0.f, sm->maxGibbsMass, rng, 1, sm->lambda);
+        if (g.has) rebirthMass = g.v;
+    }
+    float deltaLL = rebirthMass * (smu - s * rebirthMass / 2.f);
+    if (go_logf(rng->rs, rng_uniform(rng)) < deltaLL) {
+        if (rebirthMass != a->mass) {
+            safely_change_matrix(sm, row, col, rebirthMass - a->mass);
+            a->mass = rebirthMass;
+        }
+    } else {
+        safely_change_matrix(sm, row, col, -1.f * a->mass);
+        dom_erase(&sm->dom, h);                                        /* AtomicDomain.cpp:80-111 */
+    }
+}
+/* SingleThreadedGibbsSampler.h:192-223 */
+static void seq_move(go_sampler *sm)
+{
+    go_rng *rng = &sm->queue.rng;
+    uint32_t h = sm->dom.vec[rng_uniform32(rng, 0, sm->dom.n - 1)];   /* randomAtomWithNeighbors, AtomicDomain.cpp:31-39 */
+    go_atom *a = &sm->dom.pool[h];
+    uint64_t lbound = a->left != GO_NONE ? sm->dom.pool[a->left].pos : 0;
+    uint64_t rbound = a->right != GO_NONE ? sm->dom.pool[a->right].pos : u64_from_double_x86(sm->queue.domainLength);
+    uint64_t pos = rng_uniform64(rng, lbound + 1, rbound - 1);
+    uint32_t r1, c1, r2, c2;
+    if (!seq_site(sm, a->pos, &r1, &c1) || !seq_site(sm, pos, &r2, &c2)) return;
+    if (r1 == r2 && c1 == c2) { dom_move(&sm->dom, h, pos); return; }
+    float s, smu; alpha_two(sm, r1, c1, r2, c2, &s, &smu);              /* deltaLogLikelihood, DenseNormalModel.cpp:125-130 */
+    s *= sm->annealTemp; smu *= sm->annealTemp;
+    ++sm->seqCount[2]; if (r1 != r2) ++sm->seqCount[4];
+    float mass = a->mass;
+    float deltaLL = -1.f * mass * (smu + s * mass / 2.f);
+    if (go_logf(rng->rs, rng_uniform(rng)) < deltaLL) {
+        dom_move(&sm->dom, h, pos);
+        safely_change_matrix(sm, r1, c1, -a->mass);
+        change_matrix(sm, r2, c2, a->mass);
+    }
+}
+/* SingleThreadedGibbsSampler.h:228-257 */
+static void seq_exchange(go_sampler *sm)
+{
+    go_rng *rng = &sm->queue.rng;
+    uint32_t h1 = sm->dom.vec[rng_uniform32(rng, 0, sm->dom.n - 1)];
+    go_atom *a1 = &sm->dom.pool[h1];
+    uint32_t h2 = a1->right != GO_NONE ? a1->right : dom_front(&sm->dom);   /* AtomicDomain.cpp:18-22 */
+    go_atom *a2 = &sm->dom.pool[h2];
+    uint32_t r1, c1, r2, c2;
+    if (!seq_site(sm, a1->pos, &r1, &c1) || !seq_site(sm, a2->pos, &r2, &c2)) return;
+    if ((r1 != r2 || c1 != c2) && (can_use_gibbs(sm, c1) || can_use_gibbs(sm, c2))) {
+        float s, smu; alpha_two(sm, r1, c1, r2, c2, &s, &smu);          /* sampleExchange, DenseNormalModel.cpp:154-159 */
+        s *= sm->annealTemp; smu *= sm->annealTemp;
+        ++sm->seqCount[3]; if (r1 != r2) ++sm->seqCount[4];
+        optf mass = gibbs_mass(s, smu, -a1->mass, a2->mass, rng, 0, 0.f);
+        float newMass1 = a1->mass + mass.v;
+        float newMass2 = a2->mass - mass.v;
+        if (mass.has && newMass1 > GO_EPSILON && newMass2 > GO_EPSILON) {
+            safely_change_matrix(sm, r1, c1, newMass1 - a1->mass);
+            safely_change_matrix(sm, r2, c2, newMass2 - a2->mass);
+            a1->mass = newMass1;
+            a2->mass = newMass2;
+        }
+    }
+}
+/* SingleThreadedGibbsSampler.h:113-126 */
+static void seq_sampler_update(go_sampler *sm, unsigned nSteps)
+{
+    for (unsigned i = 0; i < nSteps && !sm->seqError; ++i) {
+        switch (seq_update_type(sm)) {
+            case 'B': seq_birth(sm); break;
+            case 'D': seq_death(sm); break;
+            case 'M': seq_move(sm); break;
+            case 'E': seq_exchange(sm); break;
+        }
+    }
+}
+
 /* ---- sampler construction: Matrix(mat, genesInCols, subsetGenes, indices) (Matrix.cpp:30-69) into
  * D[vector j][element i], then DenseNormalModel ctor (DenseNormalModel.h:66-88) ---- */
 static void sampler_init(go_sampler *sm, const float *data, uint32_t nrow, uint32_t ncol, const float *unc,
@@ -1556,11 +1708,13 @@ void go_default_params(go_params *p)
     memset(p, 0, sizeof(*p));
     p->nPatterns = 3; p->nIterations = 1000; p->seed = 0; p->outputFrequency = 500; p->maxThreads = 1;
     p->alphaA = 0.01f; p->alphaP = 0.01f; p->maxGibbsMassA = 100.f; p->maxGibbsMassP = 100.f;
-    p->whichMatrixFixed = 'N'; p->math_mode = GO_MATH_LIBM; p->redW_A = 1; p->redW_P = 1; p->redG = 1;
+    p->whichMatrixFixed = 'N'; p->math_mode = GO_MATH_LIBM; p->redW_A = 1; p->redW_P = 1; p->redG = 1; p->sampler = GO_SAMPLER_ASYNC;
 }
 
 go_session *go_create(const float *data, uint32_t nrow, uint32_t ncol, const go_params *p, const float *unc)
 {
+    if (p->sampler != GO_SAMPLER_ASYNC && p->sampler != GO_SAMPLER_SEQUENTIAL) return NULL;
+    if (p->sampler == GO_SAMPLER_SEQUENTIAL && p->useSparseOptimization) return NULL;   /* the dense model only, as the library */
     go_session *s = (go_session *)calloc(1, sizeof(go_session));
     s->p = *p;
     s->rs = (go_randstate *)malloc(sizeof(go_randstate));
@@ -1612,7 +1766,11 @@ void go_draw_steps(go_session *s, uint32_t *nA, uint32_t *nP)
     *nA = (uint32_t)rng_poisson(&s->rng, (double)a);
     *nP = (uint32_t)rng_poisson(&s->rng, (double)p);
 }
-void go_update(go_session *s, char which, uint32_t nSteps, go_trace *trace) { sampler_update(pick(s, which), nSteps, s->p.maxThreads ? s->p.maxThreads : 1, trace); }
+void go_update(go_session *s, char which, uint32_t nSteps, go_trace *trace)
+{
+    if (s->p.sampler == GO_SAMPLER_SEQUENTIAL) { seq_sampler_update(pick(s, which), nSteps); return; }   /* (no queue: nothing to trace) */
+    sampler_update(pick(s, which), nSteps, s->p.maxThreads ? s->p.maxThreads : 1, trace);
+}
 void go_sync(go_session *s, char which) { if (which == 'A') sampler_sync(&s->A, &s->P); else sampler_sync(&s->P, &s->A); }
 
 /* updateSampler, GapsRunner.cpp:201-222 */
@@ -1694,7 +1852,9 @@ void go_get_atoms(const go_session *s, char which, uint64_t *pos, float *mass, u
 void go_get_dims(const go_session *s, char which, uint32_t *M, uint32_t *N, uint32_t *K) { const go_sampler *sm = pickc(s, which); *M = sm->M; *N = sm->N; *K = sm->K; }
 float go_lambda(const go_session *s, char which) { return pickc(s, which)->lambda; }
 float go_max_gibbs_mass(const go_session *s, char which) { return pickc(s, which)->maxGibbsMass; }
-float go_avg_queue(const go_session *s, char which) { return pickc(s, which)->avgQueue; }
+float go_avg_queue(const go_session *s, char which) { return pickc(s, which)->avgQueue; }   /* stays 0 for the sequential sampler (getAverageQueueLength, SingleThreadedGibbsSampler.h:89-92) */
+void go_seq_counts(const go_session *s, char which, uint64_t *out5) { memcpy(out5, pickc(s, which)->seqCount, sizeof(pickc(s, which)->seqCount)); }
+int go_seq_error(const go_session *s) { return s->A.seqError || s->P.seqError; }
 void go_get_luts(const go_session *s, float *e, float *ei, float *qg)
 {
     memcpy(e, s->rs->erf, sizeof(s->rs->erf)); memcpy(ei, s->rs->erfinv, sizeof(s->rs->erfinv)); memcpy(qg, s->rs->qgamma, sizeof(s->rs->qgamma));
@@ -1844,13 +2004,15 @@ void go_finish(go_session *s, go_result *out)
 int go_run(const float *data, uint32_t nrow, uint32_t ncol, const go_params *p, const float *unc, go_result *out)
 {
     go_session *s = go_create(data, nrow, ncol, p, unc);
+    if (!s) return 1;
     double t0 = now_s();
     run_phase(s, 1);
     run_phase(s, 2);
     s->samplerSeconds = now_s() - t0;
     go_finish(s, out);
+    const int err = go_seq_error(s);
     go_destroy(s);
-    return 0;
+    return err ? 2 : 0;
 }
 void go_result_free(go_result *r)
 {

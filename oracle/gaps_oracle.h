@@ -1,5 +1,5 @@
 /*
- * gaps_oracle.h -- CPU restatement of the CoGAPS asynchronous Gibbs sampler hot path.
+ * gaps_oracle.h -- CPU restatement of the CoGAPS Gibbs samplers' hot path: the asynchronous one and the sequential one.
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing under cogaps_amd/ (the product) may include, link or
  * call this.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it,
@@ -25,6 +25,9 @@ extern "C" {
 #define GO_MATH_GLIBC_FMA 2  /* glibc 2.35 logf/expf restated, the -mfma ifunc variant (what GO_MATH_LIBM resolves to on an FMA-capable x86-64) */
 #define GO_MATH_GLIBC_SSE2 3 /* ... the generic variant (separate multiply and add) */
 
+#define GO_SAMPLER_ASYNC      0
+#define GO_SAMPLER_SEQUENTIAL 1
+
 typedef struct go_params {
     uint32_t nPatterns;        /* GapsParameters.h:88  default 3 */
     uint32_t nIterations;      /* :89 default 1000 (per phase) */
@@ -48,6 +51,7 @@ typedef struct go_params {
     int32_t takePumpSamples;       /* GapsStatistics::updatePump per sampling iteration (GapsRunner.cpp:310-313) */
     uint32_t snapshotFrequency;    /* GapsRunner.cpp:316-322; 0 = none */
     int32_t snapshotPhase;         /* 0 = all phases (the default, GapsParameters.h:98), 1 = equilibration, 2 = sampling */
+    int32_t sampler;               /* GO_SAMPLER_*: AsynchronousGibbsSampler (the default) or SingleThreadedGibbsSampler (the dense model only) */
 } go_params;
 
 typedef struct go_result {
@@ -86,7 +90,8 @@ typedef struct go_session go_session;
 
 void go_default_params(go_params *p);
 
-/* data: row-major [nrow][ncol] fp32; unc: same shape or NULL (default uncertainty) */
+/* data: row-major [nrow][ncol] fp32; unc: same shape or NULL (default uncertainty).  NULL: an unknown sampler, or the sequential
+ * sampler with the sparse model */
 go_session *go_create(const float *data, uint32_t nrow, uint32_t ncol, const go_params *p,
                       const float *unc);
 void go_destroy(go_session *s);
@@ -124,6 +129,12 @@ void go_get_dims(const go_session *s, char which, uint32_t *M, uint32_t *N, uint
 float go_lambda(const go_session *s, char which);
 float go_max_gibbs_mass(const go_session *s, char which);
 float go_avg_queue(const go_session *s, char which);
+/* sequential sampler: how many proposals of sampler `which` evaluated alpha parameters so far -- out5 = births, deaths, moves,
+ * exchanges, and the moves and exchanges among them that span two rows (r1 != r2) */
+void go_seq_counts(const go_session *s, char which, uint64_t *out5);
+/* sequential sampler: non-zero once a position past the last bin was drawn (the reference would index past its matrix; the update
+ * stopped there, and go_run returns 2) */
+int go_seq_error(const go_session *s);
 /* the three lookup tables (Random.cpp:269-295): 3001 + 5001 + 5001 floats */
 void go_get_luts(const go_session *s, float *erf, float *erfinv, float *qgamma);
 void go_finish(go_session *s, go_result *out);

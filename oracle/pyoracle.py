@@ -29,8 +29,12 @@ class GoParams(C.Structure):
         ("fixedRows", C.c_uint32), ("math_mode", C.c_int32),
         ("redW_A", C.c_uint32), ("redW_P", C.c_uint32), ("redG", C.c_uint32),
         ("useSparseOptimization", C.c_int32), ("takePumpSamples", C.c_int32),
-        ("snapshotFrequency", C.c_uint32), ("snapshotPhase", C.c_int32),
+        ("snapshotFrequency", C.c_uint32), ("snapshotPhase", C.c_int32), ("sampler", C.c_int32),
     ]
+
+
+SAMPLER_ASYNC, SAMPLER_SEQUENTIAL = 0, 1
+_SAMPLER = {"async": SAMPLER_ASYNC, "sequential": SAMPLER_SEQUENTIAL}
 
 
 class GoResult(C.Structure):
@@ -121,6 +125,8 @@ def lib(omp=False):
     for n in ("go_lambda", "go_max_gibbs_mass", "go_avg_queue"):
         getattr(L, n).restype = C.c_float
         getattr(L, n).argtypes = [C.c_void_p, C.c_char]
+    L.go_seq_counts.argtypes = [C.c_void_p, C.c_char, C.POINTER(C.c_uint64)]
+    L.go_seq_error.argtypes = [C.c_void_p]
     L.go_get_luts.argtypes = [C.c_void_p, fp, fp, fp]
     L.go_finish.argtypes = [C.c_void_p, C.POINTER(GoResult)]
     L.go_run_iterations.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -153,7 +159,7 @@ def make_params(nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, maxT
                 transposeData=False, subsetIndices=None, subsetDim=0,
                 whichMatrixFixed="N", fixedPatterns=None, math_mode=MATH_LIBM,
                 redW_A=1, redW_P=1, redG=1, sparseOptimization=False, takePumpSamples=False,
-                snapshotFrequency=0, snapshotPhase=0):
+                snapshotFrequency=0, snapshotPhase=0, sampler="async"):
     p = GoParams()
     lib().go_default_params(C.byref(p))
     p.nPatterns, p.nIterations, p.seed = nPatterns, nIterations, seed
@@ -179,6 +185,7 @@ def make_params(nPatterns=3, nIterations=1000, seed=0, outputFrequency=500, maxT
     p.useSparseOptimization = int(bool(sparseOptimization))
     p.takePumpSamples = int(bool(takePumpSamples))
     p.snapshotFrequency, p.snapshotPhase = int(snapshotFrequency), int(snapshotPhase)
+    p.sampler = _SAMPLER[sampler] if isinstance(sampler, str) else int(sampler)
     p._keep = keep
     return p
 
@@ -216,7 +223,11 @@ def run(data, unc=None, omp=False, **kw):
     u = None if unc is None else np.ascontiguousarray(unc, dtype=np.float32)
     p = make_params(**kw)
     r = GoResult()
-    L.go_run(_fp(d), d.shape[0], d.shape[1], C.byref(p), None if u is None else _fp(u), C.byref(r))
+    rc = L.go_run(_fp(d), d.shape[0], d.shape[1], C.byref(p), None if u is None else _fp(u), C.byref(r))
+    if rc:
+        if rc == 2:
+            L.go_result_free(C.byref(r))
+        raise RuntimeError("go_run: the sequential sampler takes the dense model only" if rc == 1 else "go_run: a position past the last bin was drawn")
     out = _result_to_dict(r)
     L.go_result_free(C.byref(r))
     return out
@@ -232,6 +243,8 @@ class Session:
         self.p = make_params(**kw)
         self.h = self.L.go_create(_fp(self.d), self.d.shape[0], self.d.shape[1], C.byref(self.p),
                                   None if self.u is None else _fp(self.u))
+        if not self.h:
+            raise RuntimeError("go_create: the sequential sampler takes the dense model only")
 
     def close(self):
         if self.h:
@@ -352,6 +365,16 @@ class Session:
 
     def avg_queue(self, which):
         return self.L.go_avg_queue(self.h, which.encode())
+
+    def seq_counts(self, which):
+        """sequential sampler: proposals of `which` that evaluated alpha parameters, by kind; twoRow: the moves / exchanges with r1 != r2"""
+        out = (C.c_uint64 * 5)()
+        self.L.go_seq_counts(self.h, which.encode(), out)
+        return dict(zip(("birth", "death", "move", "exchange", "twoRow"), (int(v) for v in out)))
+
+    def seq_error(self):
+        """sequential sampler: whether a position past the last bin was drawn (the update stopped there)"""
+        return bool(self.L.go_seq_error(self.h))
 
     def finish(self):
         r = GoResult()

@@ -9,7 +9,8 @@ import pyoracle as po
 
 
 def make_pair(lib, data, oracle_data=None, **kw):
-    """oracle_data: the matrix of the subset, taken outside the oracle -- it then gets that matrix and no subsetIndices / subsetDim"""
+    """oracle_data: the matrix of the subset, taken outside the oracle -- it then gets that matrix and no subsetIndices / subsetDim.
+    sampler ("async" / "sequential") goes to both sides as it is."""
     S = _capi.Session(data, lib=lib, **kw)
     wA = lib.cogaps_reduction_width(S.dims("A")[1])
     wP = lib.cogaps_reduction_width(S.dims("P")[1])
@@ -55,6 +56,51 @@ def assert_state_equal(S, O, tag, chisq=True, ap=True):
         assert S.check_domain(w) == 0, "%s %s: the atomic domain's cached neighbour positions / masses or links are inconsistent" % (tag, w)
         if chisq:
             assert S.chisq(w) == O.chisq(w), "%s %s: chi2 differs" % (tag, w)
+
+
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view(np.uint32) if x.dtype == np.float32 else x
+
+
+def assert_seq_state_equal(S, O, tag):
+    """the sequential sampler's form of assert_state_equal, bit for bit (a float as its 32 bits): both samplers' atoms in the order of
+    AtomicDomain's vector (position, mass, neighbours by index), factor matrix, A*P cache and chi2; the library's domain consistent;
+    no queue on either side; the oracle never drew a position past the last bin"""
+    assert not O.seq_error(), tag + ": the oracle drew a position past the last bin"
+    for w in "AP":
+        a, b = S.atoms(w), O.atoms(w)
+        assert a["pos"].size == b["pos"].size, "%s %s: %d atoms, the oracle has %d" % (tag, w, a["pos"].size, b["pos"].size)
+        for f in ("pos", "mass", "left", "right"):
+            assert np.array_equal(_bits(a[f]), _bits(b[f])), "%s %s: atom %s differs" % (tag, w, f)
+        assert np.array_equal(_bits(S.matrix(w)), _bits(O.matrix(w))), "%s %s: factor matrix differs" % (tag, w)
+        assert np.array_equal(_bits(S.ap(w)), _bits(O.ap(w))), "%s %s: AP cache differs" % (tag, w)
+        assert S.check_domain(w) == 0, "%s %s: the atomic domain's cached neighbour positions / masses or links are inconsistent" % (tag, w)
+        assert np.float32(S.chisq(w)).tobytes() == np.float32(O.chisq(w)).tobytes(), "%s %s: chi2 differs: %r, the oracle has %r" % (tag, w, S.chisq(w), O.chisq(w))
+        assert S.avg_queue(w) == 0.0 and O.avg_queue(w) == 0.0, "%s %s: a sequential sampler has no queue" % (tag, w)
+
+
+def run_stepwise_seq(lib, data, n_iter, total_iter=None, check_every=1, **kw):
+    """n_iter equilibration iterations of a sequential-sampler session of `lib` and of the oracle's, side by side: the Poisson step
+    counts of every update and the state after every check_every-th iteration (and the last).  -> the oracle's counts of the proposals
+    that evaluated alpha parameters per sampler (pyoracle.Session.seq_counts), the atoms per sampler, and the largest update's steps"""
+    total_iter = total_iter or max(n_iter, 2)
+    kw.setdefault("nIterations", total_iter)
+    S, O = make_pair(lib, data, sampler="sequential", **kw)
+    try:
+        longest = 0
+        for it in range(n_iter):
+            t = min(1.0, 2.0 * it / total_iter)
+            S.set_annealing(t), O.set_annealing(t)
+            nA, nP = S.draw_steps()
+            assert (nA, nP) == O.draw_steps(), "Poisson step counts differ at iteration %d" % it
+            longest = max(longest, nA, nP)
+            S.iterate(nA, nP), O.iterate(nA, nP)
+            if (it + 1) % check_every == 0 or it == n_iter - 1:
+                assert_seq_state_equal(S, O, "it%d" % it)
+        return {"counts": {w: O.seq_counts(w) for w in "AP"}, "atoms": {w: S.natoms(w) for w in "AP"}, "longest": longest}
+    finally:
+        S.close(), O.close()
 
 
 STRUCT_FIELDS = ("flags", "prefix", "ptr", "vals")
