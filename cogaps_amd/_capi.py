@@ -106,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -234,6 +234,7 @@ def bind(L):
     L.cogaps_gene_set_stat.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     L.cogaps_debug_permutation_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p]
     L.cogaps_pattern_markers.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint64, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_int, C.c_int, u32p, dp, u32p, u32p]
+    L.cogaps_pattern_gsea.argtypes = [fp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, dp, u32p, u32p, u64p, u32p]
     L.cogaps_residuals.argtypes = [fp, C.c_uint32, C.c_size_t, C.c_size_t, fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(CogapsResidualDataC),
                                    u32p, C.c_uint32, C.c_int, dp, dp, dp, dp, u64p]
     L.cogaps_batch_create.restype = vp
@@ -1068,6 +1069,36 @@ def pattern_markers(A, O, lp=None, threshold="all", device=-1, lib=None):
                                 ranks.ctypes.data_as(u32p), scores.ctypes.data_as(dp), markers.ctypes.data_as(u32p), count.ctypes.data_as(u32p)):
         raise _error(L)
     return ranks, scores, [markers[l, :int(count[l])].copy() for l in range(nL)]
+
+
+GSEA_MAX_SET = 4096                   # COGAPS_GSEA_MAX_SET
+
+
+def pattern_gsea(stat, members, numPerm, seed=0, device=-1, ranks=False, lib=None):
+    """cogaps_pattern_gsea: the enrichment score of every set in every column of stat (n x K; float32, any strides: a column-major
+    array goes in as it is), and its permutation null.  members: per set the 0-based member rows, ascending.
+    -> {"es" float64, "peak" uint32, "nGe" uint32, "permSum" uint64: [nSets][K]; with ranks=True "rank": uint32 [K][n], 0-based}"""
+    L = lib if lib is not None else load()
+    stat = _strided_f32(stat)
+    members = [np.asarray(m, dtype=np.uint32).reshape(-1) for m in members]
+    off = np.zeros(len(members) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([m.size for m in members], dtype=np.uint64)
+    mem = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), dtype=np.uint32)
+    if mem.size == 0:
+        mem = np.zeros(1, dtype=np.uint32)      # (an address to hand over; nothing of it is read)
+    n, K = stat.shape
+    shape = (len(members), K)
+    out = {"es": np.zeros(shape, dtype=np.float64), "peak": np.zeros(shape, dtype=np.uint32), "nGe": np.zeros(shape, dtype=np.uint32),
+           "permSum": np.zeros(shape, dtype=np.uint64)}
+    if ranks:
+        out["rank"] = np.zeros((K, n), dtype=np.uint32)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    if L.cogaps_pattern_gsea(stat.ctypes.data_as(C.POINTER(C.c_float)), n, K, stat.strides[0] // 4, stat.strides[1] // 4, len(members),
+                             off.ctypes.data_as(u64p), mem.ctypes.data_as(u32p), int(numPerm), int(seed) & 0xFFFFFFFF, int(device),
+                             out["es"].ctypes.data_as(C.POINTER(C.c_double)), out["peak"].ctypes.data_as(u32p), out["nGe"].ctypes.data_as(u32p),
+                             out["permSum"].ctypes.data_as(u64p), out["rank"].ctypes.data_as(u32p) if ranks else None):
+        raise _error(L)
+    return out
 
 
 RESIDUAL_DATA_NONE, RESIDUAL_DATA_DENSE, RESIDUAL_DATA_SPARSE, RESIDUAL_DATA_COO, RESIDUAL_DATA_DEVICE_MATRIX = 0, 1, 2, 3, 4      # COGAPS_RESIDUAL_DATA_*

@@ -22,6 +22,7 @@
 #include "state_file.h"
 #include "geneset_kernel.h"
 #include "markers_kernel.h"
+#include "gsea_kernel.h"
 #include "residual_kernel.h"
 
 #include <math.h>
@@ -1552,6 +1553,32 @@ static uint64_t pm_test_override(const char *name, uint64_t natural)
     return e && *e ? (uint64_t)strtoull(e, nullptr, 10) : natural;
 }
 
+// the ranking's form for p.n rows: true for the one-workgroup form, else the radix sort's tile is set (p.tileRows, p.nTiles)
+static bool pm_sort_plan(PmArgs &p)
+{
+    uint64_t smallRows = pm_test_override("COGAPS_TEST_MARKERS_SMALL_ROWS", PM_SMALL_ROWS);
+    if (smallRows > (uint64_t)PM_SMALL_ROWS) smallRows = PM_SMALL_ROWS;      // (what the kernel's LDS holds)
+    uint64_t tileRows = pm_test_override("COGAPS_TEST_MARKERS_TILE_ROWS", PM_TILE_ROWS);
+    tileRows = (tileRows + PM_THREADS - 1u) / PM_THREADS * PM_THREADS;
+    if (tileRows < (uint64_t)PM_THREADS) tileRows = PM_THREADS;
+    if (tileRows > (uint64_t)PM_TILE_ROWS) tileRows = PM_TILE_ROWS;
+    p.tileRows = (uint32_t)tileRows; p.nTiles = (uint32_t)(((uint64_t)p.n + tileRows - 1u) / tileRows);
+    return (uint64_t)p.n <= smallRows;
+}
+// ranks the L columns of keys[0] / order[0] (stable, ascending): rankT, and order[0] the rows in rank order
+static void pm_rank_launch(PmArgs &p, bool small, rt_stream_t st)
+{
+    const unsigned long long rowBlocks = ((unsigned long long)p.n + PM_THREADS - 1ull) / PM_THREADS, tiles = (unsigned long long)p.L * p.nTiles;
+    if (small) { RT_LAUNCH(pm_rank_small_kernel, gs_grid(p.L), PM_THREADS, st, p); return; }
+    for (int pass = 0; pass < PM_PASSES; ++pass) {
+        p.shift = (uint32_t)pass * PM_DIGIT_BITS;
+        RT_LAUNCH(pm_hist_kernel, gs_grid(tiles), PM_THREADS, st, p, pass & 1);
+        RT_LAUNCH(pm_hist_scan_kernel, gs_grid(p.L), PM_THREADS, st, p);
+        RT_LAUNCH(pm_scatter_kernel, gs_grid(tiles), PM_THREADS, st, p, pass & 1);
+    }
+    RT_LAUNCH(pm_rank_scatter_kernel, gs_grid(rowBlocks * p.L), PM_THREADS, st, p);
+}
+
 extern "C" {
 
 int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size_t aRowStride, size_t aColStride,
@@ -1570,12 +1597,6 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
         if (threshold != COGAPS_MARKERS_ALL && threshold != COGAPS_MARKERS_CUT) return fail("cogaps_pattern_markers: unknown threshold " + std::to_string(threshold));
         const uint32_t n = (uint32_t)nRows, m = (uint32_t)oRows, K = nCols, L = lp ? nLp : nCols;
         const size_t ldn = ((size_t)n + 15u) & ~(size_t)15u, ldm = ((size_t)m + 15u) & ~(size_t)15u;
-        uint64_t smallRows = pm_test_override("COGAPS_TEST_MARKERS_SMALL_ROWS", PM_SMALL_ROWS);
-        if (smallRows > (uint64_t)PM_SMALL_ROWS) smallRows = PM_SMALL_ROWS;      // (what the kernel's LDS holds)
-        uint64_t tileRows = pm_test_override("COGAPS_TEST_MARKERS_TILE_ROWS", PM_TILE_ROWS);
-        tileRows = (tileRows + PM_THREADS - 1u) / PM_THREADS * PM_THREADS;
-        if (tileRows < (uint64_t)PM_THREADS) tileRows = PM_THREADS;
-        if (tileRows > (uint64_t)PM_TILE_ROWS) tileRows = PM_TILE_ROWS;
         std::vector<double> at, ot;
         pm_transpose(at, ldn, a, n, K, aRowStride, aColStride);
         pm_transpose(ot, ldm, o, m, K, oRowStride, oColStride);
@@ -1586,8 +1607,7 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
         PmArgs p;
         memset(&p, 0, sizeof(p));
         p.ldn = ldn; p.ldm = ldm; p.n = n; p.m = m; p.K = K; p.L = L; p.threshold = threshold;
-        p.tileRows = (uint32_t)tileRows; p.nTiles = (uint32_t)(((uint64_t)n + tileRows - 1u) / tileRows);
-        const bool small = (uint64_t)n <= smallRows;
+        const bool small = pm_sort_plan(p);
         double *dat = g.get<double>(at.size()), *dot = g.get<double>(ot.size());
         p.at = dat; p.ot = dot;                                              // (everything below is zero-filled)
         rt_h2d(dat, at.data(), at.size() * 8, g.st);
@@ -1612,16 +1632,7 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
         RT_LAUNCH(pm_colmax_kernel, gs_grid((unsigned long long)K * ((m + PM_TILE_ROWS - 1ull) / PM_TILE_ROWS)), PM_THREADS, g.st, p);
         RT_LAUNCH(pm_normalise_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
         RT_LAUNCH(pm_score_kernel, gs_grid(rowBlocks * ((L + PM_LBLOCK - 1u) / PM_LBLOCK)), PM_THREADS, g.st, p);
-        if (small) RT_LAUNCH(pm_rank_small_kernel, gs_grid(L), PM_THREADS, g.st, p);
-        else {
-            for (int pass = 0; pass < PM_PASSES; ++pass) {
-                p.shift = (uint32_t)pass * PM_DIGIT_BITS;
-                RT_LAUNCH(pm_hist_kernel, gs_grid(tiles), PM_THREADS, g.st, p, pass & 1);
-                RT_LAUNCH(pm_hist_scan_kernel, gs_grid(L), PM_THREADS, g.st, p);
-                RT_LAUNCH(pm_scatter_kernel, gs_grid(tiles), PM_THREADS, g.st, p, pass & 1);
-            }
-            RT_LAUNCH(pm_rank_scatter_kernel, gs_grid(rowBlocks * L), PM_THREADS, g.st, p);
-        }
+        pm_rank_launch(p, small, g.st);
         RT_LAUNCH(pm_rowmin_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
         if (markers || markerCount) {
             if (threshold == COGAPS_MARKERS_CUT) RT_LAUNCH(pm_cutpos_kernel, gs_grid(rowBlocks * L), PM_THREADS, g.st, p);
@@ -1634,6 +1645,108 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
         if (markers) rt_d2h(markers, p.markers, nOut * 4, g.st);
         if (markerCount) rt_d2h(markerCount, p.markerCount, (size_t)L * 4, g.st);
         rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result statistics: the enrichment of gene sets in every pattern (gsea_kernel.h)
+// ------------------------------------------------------------------------------------------------
+int cogaps_pattern_gsea(const float *stat, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                        uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members,
+                        uint32_t numPerm, uint32_t seed, int device,
+                        double *es, uint32_t *peak, uint32_t *nGe, uint64_t *permSum, uint32_t *rankOut)
+{
+    static_assert(COGAPS_GSEA_MAX_SET == GSEA_MAX_SET, "the header's cap is the kernel's");
+    try {
+        const std::string me = "cogaps_pattern_gsea: ";
+        if (!stat || !memberOffsets || !members || !es || !peak || !nGe || !permSum) return fail(me + "null argument");
+        if (nRows == 0u || nCols == 0u) return fail(me + "the stat matrix is empty");
+        if (nSets == 0u) return fail(me + "nSets must be at least 1");
+        if (numPerm == 0u) return fail(me + "numPerm must be at least 1");
+        if (numPerm == 0xFFFFFFFFu) return fail(me + "numPerm must be below 2^32 - 1");
+        const uint32_t n = nRows, K = nCols;
+        // the values transposed (one column = one run of rows, as the sort wants them); -0 becomes +0, which is the same number
+        const size_t ldn = ((size_t)n + 15u) & ~(size_t)15u, ldk = ((size_t)K + 15u) & ~(size_t)15u;
+        std::vector<float> vt(ldn * K, 0.f);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t k = 0; k < K; ++k) {
+                const float v = stat[(size_t)i * rowStride + (size_t)k * colStride];
+                if (!(v >= 0.f)) return fail(me + "stat holds a NaN or a negative value (row " + std::to_string(i) + ", column " + std::to_string(k) + "): factor matrices are non-negative");
+                vt[(size_t)k * ldn + i] = v + 0.f;
+            }
+        for (uint32_t t = 0; t < nSets; ++t) {
+            const std::string set = me + "set " + std::to_string(t);
+            if (memberOffsets[t + 1u] < memberOffsets[t]) return fail(set + ": memberOffsets decrease");
+            const uint64_t m = memberOffsets[t + 1u] - memberOffsets[t];
+            if (m == 0u) return fail(set + ": a set without members is not tested");
+            if (m > (uint64_t)GSEA_MAX_SET) return fail(set + ": " + std::to_string(m) + " members are more than GSEA_MAX_SET = " + std::to_string(GSEA_MAX_SET));
+            for (uint64_t i = memberOffsets[t]; i < memberOffsets[t + 1u]; ++i) {
+                if (members[i] >= nRows) return fail(set + ": member " + std::to_string(members[i]) + " is not a row of stat (nRows = " + std::to_string(nRows) + ")");
+                if (i > memberOffsets[t] && members[i] <= members[i - 1u]) return fail(set + ": members are not ascending");
+            }
+            if (m >= (uint64_t)nRows) return fail(set + ": " + std::to_string(m) + " members are not fewer than nRows = " + std::to_string(nRows));
+        }
+
+        GsScratch g(device);
+        rt_alloc_scope allocOn(g.st);
+        // ranks: the markers' stable sort on the descending keys, then (rank, value) of a row's columns side by side
+        float *dvt = g.get<float>(vt.size());
+        rt_h2d(dvt, vt.data(), vt.size() * 4, g.st);
+        PmArgs p;
+        memset(&p, 0, sizeof(p));
+        p.ldn = ldn; p.n = n; p.K = K; p.L = K;
+        const bool small = pm_sort_plan(p);
+        const size_t nCol = ldn * K;
+        p.keys[0] = g.get<unsigned long long>(nCol); p.order[0] = g.get<uint32_t>(nCol); p.rankT = g.get<uint32_t>(nCol);
+        if (!small) {
+            p.keys[1] = g.get<unsigned long long>(nCol); p.order[1] = g.get<uint32_t>(nCol);
+            p.hist = g.get<uint32_t>((size_t)K * PM_THREADS * p.nTiles); p.digitBase = g.get<uint32_t>((size_t)K * PM_THREADS);
+        }
+        const unsigned long long rowBlocks = ((unsigned long long)n + PM_THREADS - 1ull) / PM_THREADS;
+        RT_LAUNCH(gsea_key_kernel, gs_grid(rowBlocks * K), PM_THREADS, g.st, (const float *)dvt, p);
+        pm_rank_launch(p, small, g.st);
+        unsigned long long *pk = g.get<unsigned long long>((size_t)n * ldk);
+        RT_LAUNCH(gsea_pack_kernel, gs_grid(((unsigned long long)n * K + PM_THREADS - 1ull) / PM_THREADS), PM_THREADS, g.st,
+                  (const float *)dvt, (const uint32_t *)p.rankT, ldn, n, K, pk, ldk);
+        if (rankOut) {
+            std::vector<uint32_t> r(nCol);
+            rt_d2h(r.data(), p.rankT, nCol * 4, g.st); rt_sync(g.st);
+            for (uint32_t k = 0; k < K; ++k)
+                for (uint32_t i = 0; i < n; ++i) rankOut[(size_t)k * n + i] = r[(size_t)k * ldn + i] - 1u;
+        }
+
+        // scores: the sets in chunks whose outputs and members stay within a fixed amount of device memory
+        uint64_t chunkSets = pm_test_override("COGAPS_TEST_GSEA_CHUNK_SETS", ((uint64_t)1 << 22) / K);
+        if (chunkSets < 1u) chunkSets = 1u;
+        if (chunkSets > nSets) chunkSets = nSets;
+        const size_t nOut = (size_t)chunkSets * K, maxMem = (size_t)chunkSets * GSEA_MAX_SET < (size_t)(memberOffsets[nSets] - memberOffsets[0]) ? (size_t)chunkSets * GSEA_MAX_SET : (size_t)(memberOffsets[nSets] - memberOffsets[0]);
+        GseaArgs a;
+        memset(&a, 0, sizeof(a));
+        a.pk = pk; a.ldk = ldk; a.nRows = n; a.K = K; a.seed = seed;
+        unsigned long long *dOff = g.get<unsigned long long>(chunkSets + 1u);
+        uint32_t *dMem = g.get<uint32_t>(maxMem);
+        a.memberOffsets = dOff; a.members = dMem;
+        a.es = g.get<double>(nOut); a.peak = g.get<uint32_t>(nOut); a.nGe = g.get<uint32_t>(nOut); a.permSum = g.get<unsigned long long>(nOut);
+        std::vector<unsigned long long> off(chunkSets + 1u);
+        const unsigned long long kBlocks = (K + GSEA_BLOCK - 1u) / GSEA_BLOCK;
+        for (uint64_t t0 = 0; t0 < nSets; t0 += chunkSets) {
+            const uint32_t here = (uint32_t)(nSets - t0 < chunkSets ? nSets - t0 : chunkSets);
+            const uint64_t first = memberOffsets[t0], nMem = memberOffsets[t0 + here] - first;
+            for (uint32_t t = 0; t <= here; ++t) off[t] = memberOffsets[t0 + t] - first;
+            const size_t nHere = (size_t)here * K;
+            rt_h2d(dOff, off.data(), ((size_t)here + 1u) * 8, g.st);
+            rt_h2d(dMem, members + first, (size_t)nMem * 4, g.st);
+            rt_memset(a.nGe, 0, nHere * 4, g.st); rt_memset(a.permSum, 0, nHere * 8, g.st);
+            a.nSets = here; a.setBase = (uint32_t)t0;
+            a.slot0 = 0u; a.nSlots = 1u;                                         // the sets themselves ...
+            RT_LAUNCH(gsea_score_kernel, gs_grid((unsigned long long)here * kBlocks), GSEA_THREADS, g.st, a);
+            a.slot0 = 1u; a.nSlots = numPerm;                                    // ... then their permutations, which compare with them
+            RT_LAUNCH(gsea_score_kernel, gs_grid((unsigned long long)here * ((numPerm + GSEA_PERMS - 1ull) / GSEA_PERMS) * kBlocks), GSEA_THREADS, g.st, a);
+            rt_d2h(es + (size_t)t0 * K, a.es, nHere * 8, g.st); rt_d2h(peak + (size_t)t0 * K, a.peak, nHere * 4, g.st);
+            rt_d2h(nGe + (size_t)t0 * K, a.nGe, nHere * 4, g.st); rt_d2h(permSum + (size_t)t0 * K, a.permSum, nHere * 8, g.st);
+            rt_sync(g.st);                                                       // (off is rewritten for the next chunk)
+        }
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

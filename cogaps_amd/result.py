@@ -9,8 +9,11 @@ where R breaks on their NA, a column none of whose rows ranks better elsewhere g
 error), and reconstructGene, residuals -- plotResiduals' matrix, with the chi-square of every gene, every sample and the whole fit
 beside it -- and binaryA: how well the result fits its data, on the GPU for dense and for sparse data, which is never densified
 (cogaps_residuals; DESIGN.md 4.10: fp64 on the widened fp32 factors in fixed orders; the default uncertainty is R's pmax(0.1 * data,
-0.1) in double; genes select rows in the order given where R's NULL means all).  calcGeneGSStat, computeGeneGSProb, getPatternGeneSet
-and the plots themselves are out of scope."""
+0.1) in double; genes select rows in the order given where R's NULL means all), and getPatternGeneSet -- which gene sets go with which
+pattern: the pre-ranked enrichment analysis of every set in every pattern with its permutation null on the GPU (cogaps_pattern_gsea;
+DESIGN.md 4.11: ties rank in row order, the permutations are the keyed draw, the p-value is the simple one, a set that is not tested
+is a NaN row where fgsea drops it), or the hypergeometric test of every set against patternMarkers' lists.  calcGeneGSStat,
+computeGeneGSProb, plotPatternGeneSet and the plots themselves are out of scope."""
 import warnings
 
 import numpy as np
@@ -59,6 +62,16 @@ def _resolve_sets(sets, names, n, which):
         if sz > n:
             raise ValueError("set %s has %d entries, the matrix %d rows: no draw without replacement" % (lab, sz, n))
     return labels, members, sizes
+
+
+def _benjamini_hochberg(p):
+    """p.adjust(p, "BH") over the entries that are not NaN (a set that was not tested stays NaN and does not count)"""
+    out = np.full(p.shape, np.nan)
+    ok = np.flatnonzero(~np.isnan(p))
+    if ok.size:
+        down = ok[np.argsort(-p[ok], kind="stable")]
+        out[down] = np.minimum(1.0, np.minimum.accumulate(p[down] * ok.size / np.arange(ok.size, 0, -1)))
+    return out
 
 
 class CogapsResult:
@@ -146,6 +159,10 @@ class CogapsResult:
         None: the unit vectors, one per pattern.  threshold "all": every row marks the pattern it ranks best in; "cut": a pattern's
         markers are its best rows up to the first that ranks better elsewhere.  -> {"PatternMarkers": label -> list of row names (1-based
         indices if the result carries no names), "PatternRanks": int [rows][L], "PatternScores": float64 [rows][L], "patterns": the labels}"""
+        return self._pattern_markers(threshold, lp, axis, lib)[0]
+
+    def _pattern_markers(self, threshold, lp, axis, lib):
+        """-> (what patternMarkers returns, per label the markers' 0-based rows)"""
         from . import _capi
         if axis == 1:
             A, O, names = self.featureLoadings, self.sampleFactors, self.geneNames
@@ -181,7 +198,103 @@ class CogapsResult:
             lists = [[names[i] for i in r] for r in rows]
         else:
             lists = [[int(i) + 1 for i in r] for r in rows]
-        return {"PatternMarkers": dict(zip(labels, lists)), "PatternRanks": ranks.astype(np.int64), "PatternScores": scores, "patterns": labels}
+        return {"PatternMarkers": dict(zip(labels, lists)), "PatternRanks": ranks.astype(np.int64), "PatternScores": scores, "patterns": labels}, rows
+
+    def getPatternGeneSet(self, sets=None, method="enrichment", whichMatrix="featureLoadings", numPerm=1000, minSize=1, maxSize=None,
+                          seed=None, lib=None, **patternMarkerArgs):
+        """R/methods-CogapsResult.R:300-344: which gene sets go with which pattern.  sets: as for calcCoGAPSStat (names or 1-based
+        indices; a set's size is the number of its members that are rows).  A set of fewer than minSize or more than maxSize rows is
+        not tested: NaN in every array, its size kept, no part in the adjustment.  DESIGN.md 4.11 has the definition and the
+        deviations from fgsea.
+        method "enrichment": the pre-ranked enrichment analysis (fgsea, scoreType = "pos") of every column of the chosen matrix, on the
+        GPU, with numPerm keyed permutations per set (seed: default the run's).  maxSize: at most, and by default, the kernel's 4096; a
+        set of all the rows is not tested either.  -> {"ES", "NES", "pval", "padj", "negLogPadj", "nMoreExtreme": [nPatterns][nSets];
+        "size": [nSets]; "leadingEdge": [nPatterns][nSets] lists of row names (1-based indices if the result carries none) in rank
+        order; "sets": the set names; "method"}.
+        method "overrepresentation": the hypergeometric test (fgsea::fora) of every set against the marker list of every pattern;
+        patternMarkerArgs (threshold, lp) go to patternMarkers, which runs on the GPU.  maxSize: default the reference's 2038.
+        -> {"overlap", "pval", "padj", "negLogPadj", "k/K": [L][nSets]; "size"; "overlapGenes": [L][nSets] lists; "sets"; "patterns":
+        the marker lists' labels; "method"}."""
+        from . import _capi
+        if method not in ("enrichment", "overrepresentation"):
+            raise ValueError("method must be 'enrichment' or 'overrepresentation'")
+        if whichMatrix not in _WHICH:
+            raise ValueError("whichMatrix must be either 'featureLoadings' or 'sampleFactors'")
+        for name, v in (("minSize", minSize), ("maxSize", maxSize)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0):
+                raise ValueError("%s must be a whole number" % name)
+        stat = np.asarray(getattr(self, _WHICH[whichMatrix][0]), dtype=np.float32)
+        names = getattr(self, _WHICH[whichMatrix][2])
+        n = stat.shape[0]
+        labels, members, _ = _resolve_sets(sets, names, n, whichMatrix)
+        size = np.array([m.size for m in members], dtype=np.int64)
+        label_of = (lambda i: names[i]) if names is not None else (lambda i: int(i) + 1)
+        nSets = len(members)
+
+        if method == "overrepresentation":
+            if "axis" in patternMarkerArgs:
+                raise ValueError("whichMatrix chooses the axis of patternMarkers")
+            if maxSize is None:
+                maxSize = 2038
+            tested = (size >= max(int(minSize), 1)) & (size <= int(maxSize))
+            pm, rows = self._pattern_markers(patternMarkerArgs.pop("threshold", "all"), patternMarkerArgs.pop("lp", None),
+                                             1 if whichMatrix == "featureLoadings" else 2, lib)
+            if patternMarkerArgs:
+                raise TypeError("getPatternGeneSet: unexpected argument %s" % sorted(patternMarkerArgs)[0])
+            L = len(rows)
+            lf = np.concatenate([[0.0], np.cumsum(np.log(np.arange(1, n + 1, dtype=np.float64)))])      # lf[j] = log(j!)
+            overlap, pval = np.full((L, nSets), np.nan), np.full((L, nSets), np.nan)
+            genes = [[[] for _ in range(nSets)] for _ in range(L)]
+            for l, marked in enumerate(rows):
+                is_marker = np.zeros(n, dtype=bool)
+                is_marker[marked] = True
+                M = int(marked.size)
+                for t in np.flatnonzero(tested):
+                    hit = members[t][is_marker[members[t]]]
+                    x, m = int(hit.size), int(size[t])
+                    i = np.arange(max(x, m - (n - M)), min(M, m) + 1)                                 # the tail P(X >= x), term by term
+                    logs = (lf[M] - lf[i] - lf[M - i]) + (lf[n - M] - lf[m - i] - lf[n - M - (m - i)]) - (lf[n] - lf[m] - lf[n - m])
+                    terms = -np.sort(-np.exp(logs))                                                   # from the largest to the smallest
+                    overlap[l, t], pval[l, t] = x, min(1.0, float(np.add.accumulate(terms)[-1])) if terms.size else 0.0
+                    genes[l][t] = [label_of(g) for g in hit]
+            padj = np.stack([_benjamini_hochberg(pval[l]) for l in range(L)])
+            with np.errstate(divide="ignore"):
+                return {"overlap": overlap, "pval": pval, "padj": padj, "negLogPadj": -10.0 * np.log10(padj), "k/K": overlap / size[None, :],
+                        "size": size, "overlapGenes": genes, "sets": labels, "patterns": pm["patterns"], "method": method}
+
+        if patternMarkerArgs:
+            raise TypeError("getPatternGeneSet: unexpected argument %s (the enrichment method takes no patternMarkers arguments)" % sorted(patternMarkerArgs)[0])
+        if isinstance(numPerm, bool) or not isinstance(numPerm, (int, np.integer)) or numPerm < 1 or numPerm >= 0xFFFFFFFF:
+            raise ValueError("numPerm must be a whole number of at least 1")
+        if maxSize is None:
+            maxSize = _capi.GSEA_MAX_SET
+        if maxSize > _capi.GSEA_MAX_SET:
+            raise ValueError("maxSize = %d is above the %d members the enrichment kernel holds of one set" % (maxSize, _capi.GSEA_MAX_SET))
+        if stat.size and not (stat >= 0).all():
+            raise ValueError("the %s hold a NaN or a negative value: factor matrices are non-negative" % whichMatrix)
+        if seed is None:
+            seed = self.metadata.get("seed") or 0
+        K = stat.shape[1]
+        tested = np.flatnonzero((size >= max(int(minSize), 1)) & (size <= int(maxSize)) & (size < n))
+        out = {k: np.full((K, nSets), np.nan) for k in ("ES", "NES", "pval", "padj", "negLogPadj", "nMoreExtreme")}
+        edges = [[[] for _ in range(nSets)] for _ in range(K)]
+        if tested.size:
+            dev = _capi.pattern_gsea(stat, [members[t] for t in tested], int(numPerm), seed=int(seed), ranks=True, lib=lib)
+            es, nGe = dev["es"].T, dev["nGe"].T.astype(np.float64)
+            mean = dev["permSum"].T.astype(np.float64) / 2.0 ** 40 / float(numPerm)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                nes = np.where(dev["permSum"].T == 0, np.nan, es / mean)
+            pval = (nGe + 1.0) / (float(numPerm) + 1.0)
+            out["ES"][:, tested], out["NES"][:, tested], out["pval"][:, tested], out["nMoreExtreme"][:, tested] = es, nes, pval, nGe
+            out["padj"] = np.stack([_benjamini_hochberg(out["pval"][k]) for k in range(K)])
+            out["negLogPadj"] = -10.0 * np.log10(out["padj"])
+            for j, t in enumerate(tested):
+                r = dev["rank"][:, members[t]]                                   # [K][m]
+                by_rank = np.argsort(r, axis=1)
+                for k in range(K):
+                    edges[k][t] = [label_of(g) for g in members[t][by_rank[k, :int(dev["peak"][j, k]) + 1]]]
+        out.update({"size": size, "leadingEdge": edges, "sets": labels, "method": method})
+        return out
 
     def _gene_rows(self, genes):
         """-> (0-based rows in the order given, their labels); genes: names or 1-based indices, never both; None: every gene"""
@@ -272,6 +385,10 @@ def binaryA(result, threshold):
 
 def patternMarkers(result, threshold="all", lp=None, axis=1, **kw):
     return result.patternMarkers(threshold=threshold, lp=lp, axis=axis, **kw)
+
+
+def getPatternGeneSet(result, sets=None, method="enrichment", **kw):
+    return result.getPatternGeneSet(sets, method=method, **kw)
 
 
 def calcZ(result, whichMatrix="featureLoadings"):

@@ -533,6 +533,32 @@ int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size
                            uint32_t *ranks, double *scores, uint32_t *markers, uint32_t *markerCount);
 
 /* ------------------------------------------------------------------------------------------------
+ * Result statistics: the enrichment of gene sets in every pattern -- the "enrichment" method of the reference's getPatternGeneSet
+ * (R/methods-CogapsResult.R:300-344), a pre-ranked gene-set enrichment analysis with scoreType = "pos" (DESIGN.md 4.11).
+ *
+ * stat: a factor matrix (featureLoadings or sampleFactors), nRows x nCols floats in host memory, element (i, k) at
+ * stat[i * rowStride + k * colStride] -- rowStride = nCols, colStride = 1 for a row-major matrix, rowStride = 1, colStride = nRows
+ * for R's column-major one.  It is uploaded once per call.  Column k ranks the rows by decreasing value, equal values in row order;
+ * rankOut[k][i] (may be NULL) is the 0-based rank of row i.  Set t has the member rows members[memberOffsets[t] ..
+ * memberOffsets[t + 1]), 0-based and ascending, m_t of them.  All outputs are laid out [nSets][nCols]; for set t and column k:
+ *   es[t][k]      = max over the members in rank order, i = 0 .. m-1, of cum_i / cum_(m-1) - (rank_i - i) / (nRows - m), cum_i the
+ *                   fp64 sum of the first i + 1 members' values in that order ((i + 1) / m where cum_(m-1) is 0)
+ *   peak[t][k]    = the first i that attains it
+ *   nGe[t][k]     = the number of permutations p < numPerm whose score is >= es[t][k], the score of permutation p being that of the
+ *                   first m_t rows of draw (seed, t, p) -- cogaps_gene_set_stat's keyed draw; one subset serves every column
+ *   permSum[t][k] = the sum over the permutations of floor(score * 2^40)
+ * None of them depends on the device, on how the work was divided or on how many sets a call holds.  device: -1 for the calling
+ * thread's current one (it is restored before the call returns).  Refused, with a message: null arguments (rankOut may be NULL),
+ * nSets == 0, numPerm == 0, an empty matrix, a NaN or negative value in stat, a set without members, with nRows or more members or
+ * with more than COGAPS_GSEA_MAX_SET of them, a member that is no row or not above its predecessor, memberOffsets that decrease.
+ * ---------------------------------------------------------------------------------------------- */
+#define COGAPS_GSEA_MAX_SET 4096
+int cogaps_pattern_gsea(const float *stat, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                        uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members,
+                        uint32_t numPerm, uint32_t seed, int device,
+                        double *es, uint32_t *peak, uint32_t *nGe, uint64_t *permSum, uint32_t *rankOut);
+
+/* ------------------------------------------------------------------------------------------------
  * Result statistics: residuals -- the reference's reconstructGene and the matrix of its plotResiduals (R/methods-CogapsResult.R:233-286;
  * DESIGN.md 4.10) -- and the chi-square of every gene, of every sample and of the whole fit.
  *
