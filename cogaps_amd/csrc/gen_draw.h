@@ -170,9 +170,10 @@ CG_DEVICE void gen_draw_a(const SamplerDev &S, const GenRoundCtx &c, const GenSp
 }
 // second part: the staged dependent loads (B: bitmap word -> bin head -> atom; D/M/E: vec -> atom record, which carries the neighbours'
 // positions and the right neighbour's mass -> matrix entries) and what follows from them.  underTrip(): the caller's work for the
-// first trip's shadow.  AHEAD: drawn before the previous batch's decisions are in -- the long ways are not taken, the lane is marked.
+// first trip's shadow.  AHEAD: drawn before the previous batch's decisions are in -- the long ways are not taken, the lane is marked
+// (soft, per lane: the same for a pick's one long way, front() as an exchange partner).
 template <int WIN, bool AHEAD, class F>
-CG_DEVICE void gen_draw_b(const SamplerDev &S, GenShared<WIN> &sh, const GenRoundCtx &c, const uint32_t type, GenDraw &d, F underTrip, const uint32_t keepH1 = CG_NONE)
+CG_DEVICE void gen_draw_b(const SamplerDev &S, GenShared<WIN> &sh, const GenRoundCtx &c, const uint32_t type, GenDraw &d, F underTrip, const uint32_t keepH1 = CG_NONE, const bool soft = false)
 {
     const uint32_t K = c.K;
     const bool isB = d.isB, pick = d.pick;
@@ -227,7 +228,7 @@ CG_DEVICE void gen_draw_b(const SamplerDev &S, GenShared<WIN> &sh, const GenRoun
             else { h2 = sh.g.front; frontE = true; }
         }
     }
-    if (AHEAD && frontE) { d.redo = true; frontE = false; h2 = h1; }      // (front() may be another atom behind the decisions: drawn again)
+    if ((AHEAD || soft) && frontE) { d.redo = true; frontE = false; h2 = h1; }      // (front() may be another atom behind the decisions: drawn again; soft: a moved pick beside the flush, which may be rewriting front() -- gen_round)
     // the scalars the evaluation starts from travel in the queue record (consumed at commit)
     float old1 = 0.f, old2 = 0.f; uint32_t gib1 = 0, gib2 = 0;
     uint64_t lposB = 0, rposB = 0; float rmassB = 0.f;        // birth: what the new atom's record caches of its neighbours
@@ -300,7 +301,7 @@ CG_DEVICE void gen_draw_b(const SamplerDev &S, GenShared<WIN> &sh, const GenRoun
             r2 = gen_div_k(S, bin2); c2 = bin2 - r2 * K;
             old2 = c.sparse ? S.rows[(size_t)r2 * S.Kpad + c2] : S.mat[(size_t)c2 * S.Mpad + r2]; gib2 = S.otherColPos[c2];
         }
-        if (r1 == r2 && c1 == c2 && !(AHEAD && d.redo)) {
+        if (r1 == r2 && c1 == c2 && !((AHEAD || soft) && d.redo)) {
             flags |= GEN_F_INLINE;
             const float m1 = a.mass, m2 = m2x;
 #if defined(EXP_NO_GAMMA)
@@ -335,10 +336,15 @@ CG_DEVICE GenCheck gen_draw_check(const GenSpec &sp, const GenDraw &d, const uin
     return c;
 }
 // Returns 0: the draw holds; 1: the lane draws again and reads nothing the flush changes -- a pick whose index and vector slot stand, whose
-// record or matrix cells the DECISIONS rewrote (it keeps its pick and need not wait for the flush); 2: it draws again behind the flush.
+// record or matrix cells the DECISIONS rewrote (it keeps its pick and need not wait for the flush), or (`moved`) a pick that only moved with
+// the domain's size (it picks again, see below); 2: it draws again behind the flush.
+#ifndef GEN_MOVED_PICK_ATOMS_PER_ERASED
+#define GEN_MOVED_PICK_ATOMS_PER_ERASED 10240u      // (0xFFFFFFFFu: a moved pick always waits for the flush, the classification up to round 6 -- A/B builds; 0: test variants of the emulator build)
+#endif
 template <int WIN>
-CG_DEVICE uint32_t gen_draw_valid(const SamplerDev &S, GenShared<WIN> &sh, const GenSpec &sp, const GenDraw &d, const GenCheck &ck, const uint32_t nR, const uint32_t m)
+CG_DEVICE uint32_t gen_draw_valid(const SamplerDev &S, GenShared<WIN> &sh, const GenSpec &sp, const GenDraw &d, const GenCheck &ck, const uint32_t nR, const uint32_t m, uint32_t &moved)
 {
+    moved = 0u;
     const uint32_t type = sp.info & 0xFFu, bBefore = sp.info >> 8;
     uint32_t bad = d.redo ? 1u : 0u, light = 0u;      // bad: behind the flush; light: the decisions' notes alone
 #if defined(GEN_AHEAD_BAD_EVERY)
@@ -348,14 +354,19 @@ CG_DEVICE uint32_t gen_draw_valid(const SamplerDev &S, GenShared<WIN> &sh, const
     const bool reads = isB || d.pick;       // (a lane without an attempt, or whose pick fell on an atom born in this window, read nothing)
     const uint32_t nA = gen_note_get(sh.dAtom, ck.atomA), nB = gen_note_get(sh.dAtom, ck.atomB), nS = gen_note_get(sh.dAtom, ck.slot);
     const uint32_t cA = gen_note_get(sh.dCell, ck.cellA), cB = gen_note_get(sh.dCell, ck.cellB);
-    // (a birth reads the bitmap, bin heads and may walk along its bin: it always waits for the flush; a pick reads its atom's record
-    // -- the flush rewrites the records of an erased atom's neighbours: dErase -- and matrix cells, which the flush never touches)
+    // (a birth reads the bitmap, bin heads and may walk along its bin: it always waits for the flush -- a birth with a noted record or cell
+    // and nothing the flush stores to is the only cause in 0.4 % of the launches, profiles/redraw_levels_cause_table.txt: not worth a way of
+    // its own; a pick reads its atom's record -- the flush rewrites the records of an erased atom's neighbours: dErase -- and matrix
+    // cells, which the flush never touches)
     if (isB) { if (reads) bad |= nA | cA; if (d.v3 != CG_NONE) bad |= nB; }
     else if (d.pick) {
         const uint32_t nE = gen_note_get(sh.dErase, ck.eraseA);
         light |= nA | cA | ((type == 'M' || type == 'E') ? cB : 0u);
         bad |= nA & nE;
     }
+#if defined(GEN_TIMELINE)
+    uint32_t tlSame = 1u, tlQ = 0u, tlRem = 0u, tlDirty = 0u;      // dev: what the cause word below is made from
+#endif
     if (isB) {
         // the bitmap words it read -- the bin's own, the next, and every further one up to the successor bin's
         const uint32_t wFirst = d.bin >> 6;
@@ -368,6 +379,9 @@ CG_DEVICE uint32_t gen_draw_valid(const SamplerDev &S, GenShared<WIN> &sh, const
             w += take;
         }
         bad |= dd ? 1u : 0u;
+#if defined(GEN_TIMELINE)
+        tlDirty = dd;
+#endif
     } else if (m != 0u && type != 0u) {
         // the pick again, from the size the flush leaves; its slot must not be one the flush refills from the vector's tail
         const uint32_t nT = nR + bBefore;
@@ -376,24 +390,61 @@ CG_DEVICE uint32_t gen_draw_valid(const SamplerDev &S, GenShared<WIN> &sh, const
         q += up; rem -= up ? nT : 0u;
         const uint32_t lo = d.i1 * q;                                   // (i1 < nT: no overflow)
         const uint32_t same = (uint32_t)(rem < nT) & (uint32_t)(d.xPick < 0xFFFFFFFFu - rem) & (uint32_t)(d.xPick >= lo) & (uint32_t)(d.xPick - lo < q) & (uint32_t)(!(d.pick && d.i1 >= nR));
-        bad |= (same ^ 1u) | (d.pick ? nS : 0u);
+        // A pick whose ONLY fault is that its index moved with the domain's size picks again beside the flush (gen_round, movedPick): it
+        // reads its new slot of the vector and the record it finds there, and where either is one the flush stores to -- the slot's note,
+        // the record's erase note: both complete at the join --, or the pick needs front(), the window is cut at that attempt like at any
+        // hazard and the attempt is drawn again in a second round, behind the flush.  Such a cut costs a round (~10 us) where the join
+        // costs ~4 us, and one of the window's ~WIN / 2 picks meets one of the 4 m noted keys among n with probability ~2 m WIN / n:
+        // the way is taken where that stays below a few per cent (n >= GEN_MOVED_PICK_ATOMS_PER_ERASED * m), and small domains keep the join.
+        const uint32_t nSp = d.pick ? nS : 0u;
+        moved = (uint32_t)((uint64_t)nR >= (uint64_t)(GEN_MOVED_PICK_ATOMS_PER_ERASED) * (uint64_t)m) & (same ^ 1u) & (uint32_t)(bad == 0u) & (nSp ^ 1u);
+        bad |= ((same ^ 1u) & (moved ^ 1u)) | nSp;
+        light |= moved;
+#if defined(GEN_TIMELINE)
+        tlSame = same; tlQ = q; tlRem = rem;
+#endif
     }
     const bool ok = !(d.go != 0u && (bad | light) != 0u);
-    const uint32_t level = d.go == 0u ? 0u : (bad ? 2u : (light && d.pick ? 1u : (light ? 2u : 0u)));
+    const uint32_t level = d.go == 0u ? 0u : (bad ? 2u : (light && (d.pick || moved) ? 1u : (light ? 2u : 0u)));
 #if defined(GEN_TIMELINE)
     // dev: why lanes draw again -- [0] lanes with an attempt, [1] drew again, [2] the pick moved (iPart / rejection / beyond the size), [3] its slot refilled,
     // [4] a noted atom record, [5] a noted matrix cell, [6] a birth's bitmap words, [7] one of the long ways (redo flag)
     if (d.go) {
-        const uint32_t moved = (!isB && m != 0u && type != 0u) ? (uint32_t)(((bad & 1u) != 0u) && !(d.redo) && !((reads ? (nA | cA) : 0u) & 1u)) : 0u;
+        const uint32_t movedL = (!isB && m != 0u && type != 0u) ? (uint32_t)(((bad & 1u) != 0u) && !(d.redo) && !((reads ? (nA | cA) : 0u) & 1u)) : 0u;
         cg_atomic_add_u64(&g_ahead_why[0], 1ull);
         if (!ok) cg_atomic_add_u64(&g_ahead_why[1], 1ull);
-        if (moved) cg_atomic_add_u64(&g_ahead_why[2], 1ull);
+        if (movedL | moved) cg_atomic_add_u64(&g_ahead_why[2], 1ull);
         if (d.pick && m != 0u && nS) cg_atomic_add_u64(&g_ahead_why[3], 1ull);
         if (reads && (nA | ((isB && d.v3 != CG_NONE) ? nB : 0u))) cg_atomic_add_u64(&g_ahead_why[4], 1ull);
         if (reads && (cA | ((d.pick && (type == 'M' || type == 'E')) ? cB : 0u))) cg_atomic_add_u64(&g_ahead_why[5], 1ull);
         if (isB && !ok && !d.redo && !(nA | cA)) cg_atomic_add_u64(&g_ahead_why[6], 1ull);
         if (d.redo) cg_atomic_add_u64(&g_ahead_why[7], 1ull);
     }
+    // dev, per LAUNCH (sh.rtCause, logged with the launch's phases -- tools/dev_chain_log.py): what put a lane behind the flush.
+    // 1 a birth with a noted record or cell and no erase note on the records it read, 2 ... with an erase note on a
+    // record, 4 a birth's bitmap words, 8 a pick that moved with the domain's size to a slot the flush leaves alone, 16 ... to a slot the flush
+    // refills / beyond the size / drawn a second time, 32 a pick's record with an erase note, 64 one of the long ways, 128 a standing pick's slot refilled
+    if (level == 2u) {
+        uint32_t cause = d.redo ? 64u : 0u;
+        if (isB) {
+            const uint32_t hasB = (uint32_t)(d.v3 != CG_NONE);
+            const uint32_t ers = (nA & gen_note_get(sh.dErase, gen_note_pos<GEN_DIRTY_ERASE>(d.v2))) | (hasB & nB & gen_note_get(sh.dErase, gen_note_pos<GEN_DIRTY_ERASE>(d.v3)));
+            if (tlDirty) cause |= 4u;
+            if (ers) cause |= 2u; else if (nA | cA | (hasB & nB)) cause |= 1u;
+        } else {
+            if (d.pick && (nA & gen_note_get(sh.dErase, ck.eraseA))) cause |= 32u;
+            if (tlSame == 0u) {
+                uint32_t clear = 0u;
+                if (!d.redo && tlQ != 0u && tlRem < nR + bBefore && d.xPick < 0xFFFFFFFFu - tlRem) {
+                    const uint32_t iNew = d.xPick / tlQ;
+                    clear = (uint32_t)(iNew < nR) & (gen_note_get(sh.dAtom, gen_note_pos<GEN_DIRTY_ATOMS>(~iNew)) ^ 1u);
+                }
+                cause |= clear ? 8u : 16u;
+            } else if (d.pick && m != 0u && nS) cause |= 128u;
+        }
+        if (cause) cg_atomic_or_u32(&sh.rtCause, cause);
+    }
+    if (moved) cg_atomic_or_u32(&sh.rtCause, 256u);      // (256: a moved pick that picks again beside the flush if the window stays at level 1; 512: one of them was cut -- gen_round)
 #endif
 #if defined(COGAPS_EMUL)
     if (d.go) cg_atomic_add_u64(&S.gs->prof[level == 0u ? 8 : (level == 1u ? 10 : 9)], 1ull);      // test-only build: lanes whose draw ahead held / that drew again behind the flush / keeping their pick

@@ -41,7 +41,7 @@ __device__ unsigned long long g_chain_gen[8];      // the chained launch's gener
 __device__ unsigned long long g_chain_log[GEN_LOG_N * 8]; __device__ unsigned int g_chain_log_n;      // one record per chained launch of a well filled queue
 #define GEN_RT_DUMP() do { if (t == 0u && sh.rtOn) { for (int i_ = 0; i_ < 8; ++i_) g_chain_gen[i_] = sh.rt[i_]; } \
     if (t == 0u && sh.rtLog) { const unsigned int k_ = atomicAdd(&g_chain_log_n, 1u) % GEN_LOG_N; for (int i_ = 0; i_ < 6; ++i_) g_chain_log[k_ * 8 + i_] = sh.rt[i_]; \
-        g_chain_log[k_ * 8 + 6] = sh.rtInfo; g_chain_log[k_ * 8 + 7] = (unsigned long long)roundNo; } } while (0)
+        g_chain_log[k_ * 8 + 6] = sh.rtInfo; g_chain_log[k_ * 8 + 7] = (unsigned long long)roundNo | ((unsigned long long)sh.rtCause << 32); } } while (0)
 #else
 #define GEN_TS(id) do { } while (0)
 #define GEN_TS_INIT() do { } while (0)
@@ -121,7 +121,7 @@ struct GenShared {
     uint32_t freeTop[16];                // the free-handle stack's top entries as the launch found them (below what its own flush pushes): a committing birth's handle without a memory trip
 #if defined(GEN_TIMELINE)
     unsigned long long ts[8 * 64];
-    unsigned long long rt[8]; uint32_t rtOn, rtLog; unsigned long long rtInfo;
+    unsigned long long rt[8]; uint32_t rtOn, rtLog; unsigned long long rtInfo; uint32_t rtCause;      // rtCause: what put lanes of the window drawn ahead behind the flush (gen_draw_valid)
 #endif
     alignas(16) uint32_t bkey[4 * GEN_TAB_NB];      // conflict sets of round 1: keys, bucket-major
     alignas(16) GenTabVal bval[4 * GEN_TAB_NB];     // ... and the ordinals registered under each key

@@ -117,11 +117,11 @@ CG_DEVICE void gen_body_sh(const SamplerDev CG_CONSTANT *sp, const GenHot hot, G
     uint64_t epoch0 = 0;
     GenDraw drawKeep; gen_draw_clear(drawKeep);      // chained launch: the lane's attempt of the next window, drawn ahead of the decisions
     GenCheck checkKeep; checkKeep.atomA.a = checkKeep.atomA.b = checkKeep.atomB.a = checkKeep.atomB.b = checkKeep.slot.a = checkKeep.slot.b = 0u;
-    checkKeep.cellA.a = checkKeep.cellA.b = checkKeep.cellB.a = checkKeep.cellB.b = 0u; checkKeep.iPartS = 1u;
+    checkKeep.cellA.a = checkKeep.cellA.b = checkKeep.cellB.a = checkKeep.cellB.b = checkKeep.eraseA.a = checkKeep.eraseA.b = 0u; checkKeep.iPartS = 1u;
     if (!CHAIN) {
         GEN_TS_ZERO(7u, 13u);
 #if defined(GEN_TIMELINE)
-        if (t == 0u) { sh.rtOn = 0u; sh.rtLog = 0u; }
+        if (t == 0u) { sh.rtOn = 0u; sh.rtLog = 0u; sh.rtCause = 0u; }
 #endif
         if (attempt) {   // roofline bookkeeping: add up the traffic units the evaluation kernel left per queue slot (the helper wave adds
             // the sum to evalBytes at the end of the batch)
@@ -142,7 +142,7 @@ CG_DEVICE void gen_body_sh(const SamplerDev CG_CONSTANT *sp, const GenHot hot, G
         GEN_TS(30);
         GEN_RT(1);
 #if defined(GEN_TIMELINE)
-        if (t == 0u) { sh.rtOn = (e_prevQ >= 140u && e_nSteps - e_nDone >= 512u) ? 1u : 0u; sh.rt[6] = 0ull; sh.rt[7] = 0ull; sh.rtLog = (WIN == 256 && e_prevQ >= 100u && e_nSteps - e_nDone >= 512u) ? 1u : 0u; }
+        if (t == 0u) { sh.rtOn = (e_prevQ >= 140u && e_nSteps - e_nDone >= 512u) ? 1u : 0u; sh.rt[6] = 0ull; sh.rt[7] = 0ull; sh.rtCause = 0u; sh.rtLog = (WIN == 256 && e_prevQ >= 100u && e_nSteps - e_nDone >= 512u) ? 1u : 0u; }
 #endif
 #if defined(GEN_TEST_APPLIER_LANES)
         const uint32_t NA = (uint32_t)GEN_TEST_APPLIER_LANES, al = t - (uint32_t)WIN;      // test-only variant of the emulator build: few applier lanes, so that short queues take several passes
@@ -346,7 +346,8 @@ CG_DEVICE void gen_body_sh(const SamplerDev CG_CONSTANT *sp, const GenHot hot, G
     if (CHAIN && specDone) {
         // which lanes drew what they would draw now (gen_draw_valid).  If every lane of the window did, the round goes straight into its
         // conflict phases and the helper wave's flush runs beside them (gen_helper); otherwise the join with the flush first
-        const uint32_t again = gen_draw_valid<WIN>(S, sh, specKeep, drawKeep, checkKeep, n0, e_m);
+        uint32_t movedPick = 0u;
+        const uint32_t again = gen_draw_valid<WIN>(S, sh, specKeep, drawKeep, checkKeep, n0, e_m, movedPick);
         const bool valid = again == 0u;
         {   // the window's level: 2 if some lane waits for the flush, else 1 if some lane draws again at all
             const uint32_t lv = cg_ballot(again == 2u) != 0ull ? 2u : (cg_ballot(again == 1u) != 0ull ? 1u : 0u);
@@ -359,14 +360,16 @@ CG_DEVICE void gen_body_sh(const SamplerDev CG_CONSTANT *sp, const GenHot hot, G
 #endif
         cg_sync_lds();
         // (level 1: the barrier only acknowledges the appliers' stores -- the lanes that draw again keep their picks and read records and
-        // matrix cells the flush leaves alone, which runs beside them as it does when no lane draws again; level 2: the join with the flush)
+        // matrix cells the flush leaves alone -- a pick that only moved with the domain's size reads its new slot and record and is cut
+        // where the flush stores to either, gen_round --, and it runs beside them as it does when no lane draws again; level 2: the join
+        // with the flush)
         const uint32_t redoLevel = cg_uniform_u32(sh.anyRedo);
         if (redoLevel != 0u) cg_sync();
         GEN_TS(38);
 #if defined(GEN_TIMELINE)
         if (t == 0u) { sh.rt[7] = __builtin_amdgcn_s_memrealtime(); sh.rtInfo |= ((sh.rt[6] & 0xFFull) << 40) | (((sh.rt[7] - sh.rt[4]) & 0xFFFFull) << 48) | ((unsigned long long)(redoLevel & 3u) << 36); }
 #endif
-        if (gen_round<WIN, true, true, true>(S, sh, rc, 1u, &specKeep, &drawKeep, valid, redoLevel == 1u)) return;
+        if (gen_round<WIN, true, true, true>(S, sh, rc, 1u, &specKeep, &drawKeep, valid, redoLevel == 1u, movedPick != 0u)) return;
     }
     else if (gen_round<WIN, true>(S, sh, rc, 1u)) return;
     for (uint32_t roundNo = 2; ; ++roundNo) {

@@ -1,7 +1,7 @@
 // gen_round.h -- one round of a batch for the attempt lanes: draws, registration, look-ups, commit.  (part of the generator: included from gen_populate.h, which documents the method)
 #pragma once
 template <int WIN, bool FIRST, bool SPEC = false, bool AHEAD = false>
-CG_DEVICE bool gen_round(const SamplerDev &S, GenShared<WIN> &sh, const GenRoundCtx &c, const uint32_t roundNo, const GenSpec *spec = nullptr, const GenDraw *ahead = nullptr, const bool aheadValid = true, const bool keepPick = false)
+CG_DEVICE bool gen_round(const SamplerDev &S, GenShared<WIN> &sh, const GenRoundCtx &c, const uint32_t roundNo, const GenSpec *spec = nullptr, const GenDraw *ahead = nullptr, const bool aheadValid = true, const bool keepPick = false, const bool movedPick = false)
 {
     static_assert(FIRST || !SPEC, "only a batch's first window is classified ahead of the decisions");
     static_assert(SPEC || !AHEAD, "only a window classified ahead is drawn ahead");
@@ -95,8 +95,28 @@ CG_DEVICE bool gen_round(const SamplerDev &S, GenShared<WIN> &sh, const GenRound
         if (cg_ballot(again) != 0ull) {      // (wave-uniform: the wave's other lanes walk through with nothing to draw, as lanes without an attempt do)
             // (keepPick -- wave-uniform: the whole window draws again without waiting for the flush -- the index vector is not read again: the
             // pick and its slot were validated, only the record and the matrix cells are read anew)
+            // (movedPick -- per lane: a pick whose index moved with the domain's size and nothing else -- picks again beside the flush: its
+            // new slot and the record there are read while the flush may be storing to them, and checked BEHIND the reads against the
+            // notes of what the flush stores to -- the slots it refills, the records it relinks: complete since the join --; front() is
+            // not followed.  Every word it can have read is a valid handle or position, old or new; where a note is set the attempt is a
+            // hazard: the window is cut there, and the second round draws it again behind the flush.)
+            const bool soft = again && keepPick && movedPick;
             GenDraw r; gen_draw_a<WIN, SPEC>(S, c, spec, again, type, bBefore, SPEC ? spec->rng : 0ull, nR, r);
-            gen_draw_b<WIN, false>(S, sh, c, type, r, [&]() {}, keepPick ? ahead->h1 : CG_NONE);
+            gen_draw_b<WIN, false>(S, sh, c, type, r, [&]() {}, (keepPick && !movedPick) ? ahead->h1 : CG_NONE, soft);
+            if (cg_ballot(soft) != 0ull) {
+                uint32_t cut = (soft && r.redo) ? 1u : 0u;
+                if (soft && r.pick) cut |= gen_note_get(sh.dAtom, gen_note_pos<GEN_DIRTY_ATOMS>(~r.i1)) | gen_note_get(sh.dErase, gen_note_pos<GEN_DIRTY_ERASE>(r.h1));
+#if defined(GEN_TEST_MOVED_PICK_FLAG_EVERY)
+                if (soft && ((ct + (uint32_t)batchEpoch) % (uint32_t)GEN_TEST_MOVED_PICK_FLAG_EVERY) == 0u) cut = 1u;      // test-only variant: the cut, regularly
+#endif
+                if (cut) r.flags |= GEN_F_HAZARD;
+#if defined(GEN_TIMELINE)
+                if (cut) cg_atomic_or_u32(&sh.rtCause, 512u);
+#endif
+#if defined(COGAPS_EMUL)
+                if (soft) cg_atomic_add_u64(&gs->prof[cut ? 3 : 1], 1ull);      // test-only build: moved picks that picked again beside the flush / that were cut
+#endif
+            }
             if (again) d = r;
         }
 #endif

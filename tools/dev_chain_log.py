@@ -23,11 +23,13 @@ a = np.array(buf, dtype=np.int64).reshape(N, 8)[:min(n.value, N)]
 a = a[a[:, 0] > 0]
 t = (a[:, 1:6] - a[:, 0:5]) / 100.0            # phase lengths, us
 tot = (a[:, 5] - a[:, 0]) / 100.0
-prevq = a[:, 6] & 0xFFFF; em = (a[:, 6] >> 16) & 0xFFFF; spec = (a[:, 6] >> 32) & 1; rounds = a[:, 7]
+prevq = a[:, 6] & 0xFFFF; em = (a[:, 6] >> 16) & 0xFFFF; spec = (a[:, 6] >> 32) & 1; rounds = a[:, 7] & 0xFFFFFFFF
+cause = (a[:, 7] >> 32) & 0xFF      # what put lanes of the window drawn ahead behind the flush (gen_draw_valid, sh.rtCause)
+mvd = ((a[:, 7] >> 40) & 1) == 1; cut = ((a[:, 7] >> 41) & 1) == 1      # the window held a moved pick that may pick again beside the flush; one of them was cut (gen_round)
 level = (a[:, 6] >> 36) & 3; bad = (a[:, 6] >> 40) & 0xFF; vj = ((a[:, 6] >> 48) & 0xFFFF) / 100.0      # lanes that drew again; applied -> validated + joined with the flush, us
 names = ['entry -> first barrier', 'first barrier -> window drawn ahead (attempt lane 0)', 'drawn ahead -> granules in (helper lane 0; may be negative)', 'granules in -> applied + barrier', 'round(s) of the next batch']
 def line(name, v): print('  %-32s mean %6.2f  p10 %6.2f  p50 %6.2f  p75 %6.2f  p90 %6.2f  p99 %6.2f' % (name, v.mean(), *np.percentile(v, [10, 50, 75, 90, 99])))
-print('%d launches logged (queue >= 100); rounds: %s; classified ahead: %.3f' % (len(a), dict(zip(*np.unique(rounds, return_counts=True))), spec.mean()))
+print('%d launches logged (queue >= 100); rounds: %s; classified ahead: %.3f' % (len(a), {int(k): int(v) for k, v in zip(*np.unique(rounds, return_counts=True))}, spec.mean()))
 for sel, nm in ((rounds >= 1, 'all'), (rounds == 1, 'one round'), (rounds == 2, 'two rounds')):
     if sel.sum() < 10: continue
     print(nm, '(%d)' % sel.sum())
@@ -47,6 +49,33 @@ print('lanes that drew again per launch: mean %.2f; launches with none %.3f; wit
 for nm, sel in (('no lane drew again, nothing erased', (bad == 0) & (em == 0) & one), ('no lane drew again, atoms erased', (bad == 0) & (em > 0) & one), ('some lane drew again', (bad > 0) & one),
                 ('... keeping their picks (level 1)', (level == 1) & one), ('... behind the flush (level 2)', (level == 2) & one)):
     if sel.sum() > 5: print('  one round, %-36s %5d launches: whole %.2f  round %.2f  validate + join %.2f us' % (nm, sel.sum(), tot[sel].mean(), t[sel, 4].mean(), vj[sel].mean()))
+
+# The cause table: per launch, which causes put it at level 2 (a launch may have several; `alone`: it was the launch's only cause -- the
+# launches a mechanism for that cause alone would move to level 1), for one-round launches and for the first round of two-round launches
+CAUSES = ((1, 'a birth, noted record or cell, no erase note'), (2, 'a birth, erase note on a record it read'), (4, 'a birth, dirty bitmap words'),
+          (8, 'a moved pick, its new slot left alone'), (16, 'a moved pick, new slot refilled / beyond the size'), (32, 'a pick, erase note on its record'),
+          (64, 'a long way (redo)'), (128, 'a standing pick, its slot refilled'))
+for nm, cls in (('one-round launches', rounds == 1), ('two-round launches (first round)', rounds == 2)):
+    if cls.sum() < 10: continue
+    print('cause table, %s: %d' % (nm, cls.sum()))
+    for lv in (0, 1, 2):
+        sel = cls & (level == lv) & (spec == 1)
+        if sel.sum(): print('  level %d: %6d launches (%.4f)  whole %.2f  validate + join %.2f  round(s) %.2f us' % (lv, sel.sum(), sel.sum() / cls.sum(), tot[sel].mean(), vj[sel].mean(), t[sel, 4].mean()))
+    for cn, sel in (('level 1 without a moved pick (the class as it was before moved picks joined it)', cls & (level == 1) & (spec == 1) & ~mvd),
+                    ('level 1 with moved picks picking again beside the flush', cls & (level == 1) & (spec == 1) & mvd)):
+        if sel.sum(): print('    %-88s %6d launches (%.4f)  whole %.2f  validate + join %.2f  round(s) %.2f us' % (cn, sel.sum(), sel.sum() / cls.sum(), tot[sel].mean(), vj[sel].mean(), t[sel, 4].mean()))
+    if (cls & cut).sum() or (rounds >= 2).sum():
+        print('    launches in which a moved pick was cut (logged under the rounds their batch then took): %d of %d launches with moved picks at level 1, all rounds' % ((cut & (level == 1)).sum(), (mvd & (level == 1)).sum()))
+    sel = cls & (spec == 0)
+    if sel.sum(): print('  not drawn ahead: %6d launches (%.4f)  whole %.2f us' % (sel.sum(), sel.sum() / cls.sum(), tot[sel].mean()))
+    l2 = cls & (level == 2) & (spec == 1)
+    for bit, cn in CAUSES:
+        has = l2 & ((cause & bit) != 0); alone = l2 & (cause == bit)
+        print('    level 2 by cause: %-52s %6d launches (%.4f of the class)  whole %.2f | alone %6d (%.4f)  whole %.2f' % (
+            cn, has.sum(), has.sum() / cls.sum(), tot[has].mean() if has.sum() else 0.0, alone.sum(), alone.sum() / cls.sum(), tot[alone].mean() if alone.sum() else 0.0))
+    for bits, cn in ((1, 'births the flush does not touch'), (8, 'moved picks to a slot left alone'), (9, 'both')):
+        only = l2 & (cause != 0) & ((cause & ~bits) == 0)
+        print('    level 2 only through %-36s %6d launches (%.4f of the class)  whole %.2f' % (cn, only.sum(), only.sum() / cls.sum(), tot[only].mean() if only.sum() else 0.0))
 
 why = (ctypes.c_uint64 * 8)()
 PL.cogaps_debug_ahead_why.argtypes = [ctypes.c_void_p]
