@@ -992,29 +992,41 @@ def debug_uniform64(state, lo, hi, on_device=False, lib=None):
     return v, after
 
 
-def gene_set_stat(z, members, sizes, numPerm, seed=0, device=-1, lib=None):
-    """cogaps_gene_set_stat: the permutation counts of the gene-set statistic.  z: the Z matrix (n x K; float64, any strides: a
-    column-major array goes in as it is), members: per set the 0-based member rows, ascending; sizes: per set the rows to draw.
-    -> (lessThanCount uint32 [nSets][K], actualMean float64 [nSets][K])"""
-    L = lib if lib is not None else load()
-    z = np.asarray(z, dtype=np.float64)
-    if z.ndim != 2:
-        raise ValueError("z must be a matrix")
-    if any(st % 8 or st < 0 for st in z.strides):
-        z = np.ascontiguousarray(z)
+def _strided(x, dtype, what="a matrix is expected"):
+    """x as a matrix of dtype whose strides are whole, non-negative numbers of elements: as it lies where it is one, a contiguous copy otherwise"""
+    x = np.asarray(x, dtype=dtype)
+    if x.ndim != 2:
+        raise ValueError(what)
+    if any(st % x.itemsize or st < 0 for st in x.strides):
+        x = np.ascontiguousarray(x)
+    return x
+
+
+def _pack_sets(members):
+    """per set the member rows -> (off uint64 [nSets + 1], mem uint32: the sets one after the other)"""
     members = [np.asarray(m, dtype=np.uint32).reshape(-1) for m in members]
     off = np.zeros(len(members) + 1, dtype=np.uint64)
     off[1:] = np.cumsum([m.size for m in members], dtype=np.uint64)
     mem = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), dtype=np.uint32)
     if mem.size == 0:
         mem = np.zeros(1, dtype=np.uint32)      # (an address to hand over; nothing of it is read)
+    return off, mem
+
+
+def gene_set_stat(z, members, sizes, numPerm, seed=0, device=-1, lib=None):
+    """cogaps_gene_set_stat: the permutation counts of the gene-set statistic.  z: the Z matrix (n x K; float64, any strides: a
+    column-major array goes in as it is), members: per set the 0-based member rows, ascending; sizes: per set the rows to draw.
+    -> (lessThanCount uint32 [nSets][K], actualMean float64 [nSets][K])"""
+    L = lib if lib is not None else load()
+    z = _strided(z, np.float64, "z must be a matrix")
+    off, mem = _pack_sets(members)
     sz = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
-    if sz.size != len(members):
+    if sz.size != off.size - 1:
         raise ValueError("one draw size per set")
-    cnt = np.zeros((len(members), z.shape[1]), dtype=np.uint32)
-    act = np.zeros((len(members), z.shape[1]), dtype=np.float64)
+    cnt = np.zeros((off.size - 1, z.shape[1]), dtype=np.uint32)
+    act = np.zeros((off.size - 1, z.shape[1]), dtype=np.float64)
     u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    if L.cogaps_gene_set_stat(z.ctypes.data_as(dp), z.shape[0], z.shape[1], z.strides[0] // 8, z.strides[1] // 8, len(members),
+    if L.cogaps_gene_set_stat(z.ctypes.data_as(dp), z.shape[0], z.shape[1], z.strides[0] // 8, z.strides[1] // 8, off.size - 1,
                               off.ctypes.data_as(C.POINTER(C.c_uint64)), mem.ctypes.data_as(u32p), sz.ctypes.data_as(u32p),
                               int(numPerm), int(seed) & 0xFFFFFFFF, int(device), cnt.ctypes.data_as(u32p), act.ctypes.data_as(dp)):
         raise _error(L)
@@ -1040,15 +1052,7 @@ def pattern_markers(A, O, lp=None, threshold="all", device=-1, lib=None):
     L = lib if lib is not None else load()
     if threshold not in ("all", "cut"):
         raise ValueError("threshold must be 'all' or 'cut'")
-    mats = []
-    for x in (A, O):
-        x = np.asarray(x, dtype=np.float64)
-        if x.ndim != 2:
-            raise ValueError("A and O must be matrices")
-        if any(st % 8 or st < 0 for st in x.strides):
-            x = np.ascontiguousarray(x)
-        mats.append(x)
-    A, O = mats
+    A, O = (_strided(x, np.float64, "A and O must be matrices") for x in (A, O))
     if A.shape[1] != O.shape[1]:
         raise ValueError("A and O must have the same number of columns")
     K = A.shape[1]
@@ -1079,21 +1083,16 @@ def pattern_gsea(stat, members, numPerm, seed=0, device=-1, ranks=False, lib=Non
     array goes in as it is), and its permutation null.  members: per set the 0-based member rows, ascending.
     -> {"es" float64, "peak" uint32, "nGe" uint32, "permSum" uint64: [nSets][K]; with ranks=True "rank": uint32 [K][n], 0-based}"""
     L = lib if lib is not None else load()
-    stat = _strided_f32(stat)
-    members = [np.asarray(m, dtype=np.uint32).reshape(-1) for m in members]
-    off = np.zeros(len(members) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([m.size for m in members], dtype=np.uint64)
-    mem = np.ascontiguousarray(np.concatenate(members) if members else np.zeros(0), dtype=np.uint32)
-    if mem.size == 0:
-        mem = np.zeros(1, dtype=np.uint32)      # (an address to hand over; nothing of it is read)
+    stat = _strided(stat, np.float32)
+    off, mem = _pack_sets(members)
     n, K = stat.shape
-    shape = (len(members), K)
+    shape = (off.size - 1, K)
     out = {"es": np.zeros(shape, dtype=np.float64), "peak": np.zeros(shape, dtype=np.uint32), "nGe": np.zeros(shape, dtype=np.uint32),
            "permSum": np.zeros(shape, dtype=np.uint64)}
     if ranks:
         out["rank"] = np.zeros((K, n), dtype=np.uint32)
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-    if L.cogaps_pattern_gsea(stat.ctypes.data_as(C.POINTER(C.c_float)), n, K, stat.strides[0] // 4, stat.strides[1] // 4, len(members),
+    if L.cogaps_pattern_gsea(stat.ctypes.data_as(C.POINTER(C.c_float)), n, K, stat.strides[0] // 4, stat.strides[1] // 4, off.size - 1,
                              off.ctypes.data_as(u64p), mem.ctypes.data_as(u32p), int(numPerm), int(seed) & 0xFFFFFFFF, int(device),
                              out["es"].ctypes.data_as(C.POINTER(C.c_double)), out["peak"].ctypes.data_as(u32p), out["nGe"].ctypes.data_as(u32p),
                              out["permSum"].ctypes.data_as(u64p), out["rank"].ctypes.data_as(u32p) if ranks else None):
@@ -1104,16 +1103,6 @@ def pattern_gsea(stat, members, numPerm, seed=0, device=-1, ranks=False, lib=Non
 RESIDUAL_DATA_NONE, RESIDUAL_DATA_DENSE, RESIDUAL_DATA_SPARSE, RESIDUAL_DATA_COO, RESIDUAL_DATA_DEVICE_MATRIX = 0, 1, 2, 3, 4      # COGAPS_RESIDUAL_DATA_*
 
 
-def _strided_f32(x):
-    """x as a float32 matrix whose strides are whole, non-negative numbers of elements: as it lies where it is one, a contiguous copy otherwise"""
-    x = np.asarray(x, dtype=np.float32)
-    if x.ndim != 2:
-        raise ValueError("a matrix is expected")
-    if any(st % 4 or st < 0 for st in x.strides):
-        x = np.ascontiguousarray(x)
-    return x
-
-
 def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=-1, lib=None):
     """cogaps_residuals: how well A (genes x K) and P (samples x K), float32 with any strides, fit `data`.  data: None (the
     reconstruction A P^T alone), a dense matrix (numpy, any strides -- a column-major array goes in as it is; a torch tensor or a
@@ -1122,7 +1111,7 @@ def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=
     reconstruction without data) are wanted, any order, repeats allowed.  -> {"matrix": float64 [len(rows)][samples] or None,
     "geneChiSq", "sampleChiSq": float64 vectors, "chiSq": float (the three are None without data), "peakDeviceBytes": int}"""
     L = lib if lib is not None else load()
-    A, P = _strided_f32(A), _strided_f32(P)
+    A, P = _strided(A, np.float32), _strided(P, np.float32)
     if A.shape[1] != P.shape[1]:
         raise ValueError("featureLoadings has %d patterns, sampleFactors %d" % (A.shape[1], P.shape[1]))
     G, N, K = A.shape[0], P.shape[0], A.shape[1]
@@ -1151,8 +1140,8 @@ def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=
             desc.dense, desc.uncertainty = data.data_addr, data.unc_addr
             desc.rowStride, desc.colStride = data.shape[1], 1
         else:
-            d = _strided_f32(data)
-            u = None if unc is None else _strided_f32(unc)
+            d = _strided(data, np.float32)
+            u = None if unc is None else _strided(unc, np.float32)
             if u is not None:
                 if u.shape != d.shape:
                     raise ValueError("the uncertainty matrix must have the shape of the data")

@@ -536,14 +536,15 @@ static void spb_sides(cogaps_session *s, uint32_t nrow, uint32_t ncol, bool majo
     }
 }
 
-// Device temporaries of a build: not the session's (allocated under a null owner scope), released when the build returns or throws
+// Device temporaries of a call -- a build's, a result statistic's (result_stats.h): not a session's (allocated under a null owner scope),
+// released when their owner goes, however the call ends
 struct SpbTemps {
-    void *p[12] = {}; int n = 0;
+    std::vector<void *> p;
     ~SpbTemps() { for (void *q : p) rt_free(q); }
     template <class T> T *alloc(size_t count)
     {
-        if (n == (int)(sizeof(p) / sizeof(p[0]))) throw std::runtime_error("internal: a build has more temporaries than SpbTemps holds");
-        rt_owner_scope notTheSessions(nullptr); T *q = dalloc<T>(count); p[n++] = q; return q;
+        p.push_back(nullptr);      // (the slot first: nothing is ever allocated that has no place here)
+        rt_owner_scope notTheSessions(nullptr); p.back() = dalloc<T>(count); return (T *)p.back();
     }
     // one of the caller's arrays where the kernels read it: uploaded, or used where it is
     template <class T> const T *stage(const T *src, size_t count, bool onDevice, rt_stream_t stream)
@@ -1424,467 +1425,12 @@ int cogaps_device_memory(int device, uint64_t *freeBytes, uint64_t *totalBytes)
     } catch (const std::exception &e) { return fail_exc(e); }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Result statistics: the gene-set permutation statistic (geneset_kernel.h)
-// ------------------------------------------------------------------------------------------------
 } // extern "C"
 
-// device memory of one call, released however the call ends
-struct GsScratch {
-    std::vector<void *> mem; rt_stream_t st; int before; bool moved;
-    explicit GsScratch(int device) : st(0), before(rt_get_device()), moved(device >= 0 && device != before)
-    {
-        if (moved) rt_set_device(device);
-        try { st = rt_stream_create(); } catch (...) { if (moved) rt_set_device(before); throw; }
-    }
-    template <class T> T *get(size_t n) { mem.push_back(nullptr); mem.back() = rt_malloc(n * sizeof(T)); return (T *)mem.back(); }
-    ~GsScratch()
-    {
-        for (void *p : mem) rt_free(p);
-        rt_stream_destroy(st);
-        if (moved) { try { rt_set_device(before); } catch (const std::exception &) {} }
-    }
-};
-// workgroups of a looping grid: eight of 256 threads fill a compute unit
-static uint32_t gs_grid(unsigned long long units)
-{
-    const unsigned long long room = (unsigned long long)rt_compute_units() * 8ull;
-    const unsigned long long g = units < room ? units : room;
-    return (uint32_t)(g < 1ull ? 1ull : (g > 0x7FFFFFFFull ? 0x7FFFFFFFull : g));
-}
-template <int SLOTS>
-static void gs_launch(const GsArgs &a, rt_stream_t st)
-{
-    const unsigned long long colBlocks = (a.K + 64u * SLOTS - 1u) / (64u * SLOTS), chunks = (a.numPerm + GS_PERMS - 1u) / GS_PERMS;
-    RT_LAUNCH(gs_actual_kernel<SLOTS>, gs_grid(((unsigned long long)a.nSets * colBlocks + GS_WAVES - 1ull) / GS_WAVES), GS_THREADS, st, a);
-    RT_LAUNCH(gs_count_kernel<SLOTS>, gs_grid((unsigned long long)a.nSets * chunks * colBlocks), GS_THREADS, st, a);
-}
+// the statistics of a finished run, at their place among the chapters: the kernels keep their order of first use
+#include "result_stats.h"
 
 extern "C" {
-
-int cogaps_gene_set_stat(const double *z, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
-                         uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members, const uint32_t *drawSizes,
-                         uint32_t numPerm, uint32_t seed, int device, uint32_t *lessThanCount, double *actualMean)
-{
-    try {
-        if (!z || !memberOffsets || !drawSizes || !lessThanCount) return fail("cogaps_gene_set_stat: null argument");
-        if (nRows == 0u || nCols == 0u) return fail("cogaps_gene_set_stat: the Z matrix is empty");
-        if (nSets == 0u) return fail("cogaps_gene_set_stat: nSets must be at least 1");
-        if (numPerm == 0u) return fail("cogaps_gene_set_stat: numPerm must be at least 1");
-        for (uint32_t t = 0; t < nSets; ++t) {
-            const std::string set = "cogaps_gene_set_stat: set " + std::to_string(t);
-            if (drawSizes[t] == 0u || drawSizes[t] > nRows) return fail(set + ": a draw of " + std::to_string(drawSizes[t]) + " rows is outside 1 .. nRows = " + std::to_string(nRows));
-            if (memberOffsets[t + 1u] < memberOffsets[t]) return fail(set + ": memberOffsets decrease");
-            if (memberOffsets[t + 1u] > memberOffsets[t] && !members) return fail("cogaps_gene_set_stat: null argument");
-            for (uint64_t i = memberOffsets[t]; i < memberOffsets[t + 1u]; ++i) {
-                if (members[i] >= nRows) return fail(set + ": member " + std::to_string(members[i]) + " is not a row of Z (nRows = " + std::to_string(nRows) + ")");
-                if (i > memberOffsets[t] && members[i] <= members[i - 1u]) return fail(set + ": members are not ascending");
-            }
-        }
-        // Z repacked row-major, rows of whole 128-byte lines
-        const size_t ld = ((size_t)nCols + 15u) & ~(size_t)15u;
-        std::vector<double> zp((size_t)nRows * ld, 0.0);
-        for (uint32_t i = 0; i < nRows; ++i)
-            for (uint32_t k = 0; k < nCols; ++k) zp[(size_t)i * ld + k] = z[(size_t)i * rowStride + (size_t)k * colStride];
-        const uint64_t first = memberOffsets[0], nMem = memberOffsets[nSets] - first;
-        std::vector<unsigned long long> off(nSets + 1u);
-        for (uint32_t t = 0; t <= nSets; ++t) off[t] = memberOffsets[t] - first;
-        const size_t nOut = (size_t)nSets * nCols;
-
-        GsScratch g(device);
-        rt_alloc_scope allocOn(g.st);
-        double *dz = g.get<double>(zp.size()), *dAct = g.get<double>(nOut);
-        unsigned long long *dOff = g.get<unsigned long long>(off.size());
-        uint32_t *dMem = g.get<uint32_t>(nMem), *dSize = g.get<uint32_t>(nSets), *dCnt = g.get<uint32_t>(nOut);      // (zero-filled)
-        rt_h2d(dz, zp.data(), zp.size() * 8, g.st);
-        rt_h2d(dOff, off.data(), off.size() * 8, g.st);
-        if (nMem) rt_h2d(dMem, members + first, nMem * 4, g.st);
-        rt_h2d(dSize, drawSizes, (size_t)nSets * 4, g.st);
-        GsArgs a;
-        a.z = dz; a.ld = ld; a.nRows = nRows; a.K = nCols; a.nSets = nSets; a.numPerm = numPerm; a.seed = seed;
-        a.memberOffsets = dOff; a.members = dMem; a.drawSizes = dSize; a.actual = dAct; a.counts = dCnt;
-        if (nCols <= 64u) gs_launch<1>(a, g.st);
-        else if (nCols <= 128u) gs_launch<2>(a, g.st);
-        else gs_launch<4>(a, g.st);
-        rt_d2h(lessThanCount, dCnt, nOut * 4, g.st);
-        if (actualMean) rt_d2h(actualMean, dAct, nOut * 8, g.st);
-        rt_sync(g.st);
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, uint32_t set, uint32_t perm, int device, uint32_t *out)
-{
-    try {
-        if (!out) return fail("cogaps_debug_permutation_draw: null argument");
-        if (size == 0u || size > nRows) return fail("cogaps_debug_permutation_draw: a draw of " + std::to_string(size) + " rows is outside 1 .. nRows = " + std::to_string(nRows));
-        GsScratch g(device);
-        rt_alloc_scope allocOn(g.st);
-        uint32_t *d = g.get<uint32_t>(size);
-        RT_LAUNCH(gs_draw_kernel, 1, 64, g.st, nRows, size, seed, set, perm, d);
-        rt_d2h(out, d, (size_t)size * 4, g.st); rt_sync(g.st);
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Result statistics: pattern markers (markers_kernel.h)
-// ------------------------------------------------------------------------------------------------
-} // extern "C"
-
-static_assert(COGAPS_MARKERS_ALL == PM_THRESHOLD_ALL && COGAPS_MARKERS_CUT == PM_THRESHOLD_CUT, "the header's thresholds are the kernels'");
-
-// a host matrix (element (i, k) at src[i * rowStride + k * colStride]) transposed: column k is the run dst[k * ld ..]; rows are taken a
-// block at a time so that a row-major source is read from the cache, not once per column
-static void pm_transpose(std::vector<double> &dst, size_t ld, const double *src, size_t rows, uint32_t cols, size_t rowStride, size_t colStride)
-{
-    dst.assign(ld * cols, 0.0);
-    for (size_t i0 = 0; i0 < rows; i0 += 1024u) {
-        const size_t i1 = rows - i0 < 1024u ? rows : i0 + 1024u;
-        for (uint32_t k = 0; k < cols; ++k)
-            for (size_t i = i0; i < i1; ++i) dst[(size_t)k * ld + i] = src[i * rowStride + (size_t)k * colStride];
-    }
-}
-// test-only: COGAPS_TEST_MARKERS_SMALL_ROWS / COGAPS_TEST_MARKERS_TILE_ROWS move the ranking's cutoff and the radix sort's tile, so
-// that a test reaches every form, and more than one tile, at a few hundred rows
-static uint64_t pm_test_override(const char *name, uint64_t natural)
-{
-    const char *e = getenv(name);
-    return e && *e ? (uint64_t)strtoull(e, nullptr, 10) : natural;
-}
-
-// the ranking's form for p.n rows: true for the one-workgroup form, else the radix sort's tile is set (p.tileRows, p.nTiles)
-static bool pm_sort_plan(PmArgs &p)
-{
-    uint64_t smallRows = pm_test_override("COGAPS_TEST_MARKERS_SMALL_ROWS", PM_SMALL_ROWS);
-    if (smallRows > (uint64_t)PM_SMALL_ROWS) smallRows = PM_SMALL_ROWS;      // (what the kernel's LDS holds)
-    uint64_t tileRows = pm_test_override("COGAPS_TEST_MARKERS_TILE_ROWS", PM_TILE_ROWS);
-    tileRows = (tileRows + PM_THREADS - 1u) / PM_THREADS * PM_THREADS;
-    if (tileRows < (uint64_t)PM_THREADS) tileRows = PM_THREADS;
-    if (tileRows > (uint64_t)PM_TILE_ROWS) tileRows = PM_TILE_ROWS;
-    p.tileRows = (uint32_t)tileRows; p.nTiles = (uint32_t)(((uint64_t)p.n + tileRows - 1u) / tileRows);
-    return (uint64_t)p.n <= smallRows;
-}
-// ranks the L columns of keys[0] / order[0] (stable, ascending): rankT, and order[0] the rows in rank order
-static void pm_rank_launch(PmArgs &p, bool small, rt_stream_t st)
-{
-    const unsigned long long rowBlocks = ((unsigned long long)p.n + PM_THREADS - 1ull) / PM_THREADS, tiles = (unsigned long long)p.L * p.nTiles;
-    if (small) { RT_LAUNCH(pm_rank_small_kernel, gs_grid(p.L), PM_THREADS, st, p); return; }
-    for (int pass = 0; pass < PM_PASSES; ++pass) {
-        p.shift = (uint32_t)pass * PM_DIGIT_BITS;
-        RT_LAUNCH(pm_hist_kernel, gs_grid(tiles), PM_THREADS, st, p, pass & 1);
-        RT_LAUNCH(pm_hist_scan_kernel, gs_grid(p.L), PM_THREADS, st, p);
-        RT_LAUNCH(pm_scatter_kernel, gs_grid(tiles), PM_THREADS, st, p, pass & 1);
-    }
-    RT_LAUNCH(pm_rank_scatter_kernel, gs_grid(rowBlocks * p.L), PM_THREADS, st, p);
-}
-
-extern "C" {
-
-int cogaps_pattern_markers(const double *a, uint64_t nRows, uint32_t nCols, size_t aRowStride, size_t aColStride,
-                           const double *o, uint64_t oRows, size_t oRowStride, size_t oColStride,
-                           const double *lp, uint32_t nLp, int threshold, int device,
-                           uint32_t *ranks, double *scores, uint32_t *markers, uint32_t *markerCount)
-{
-    try {
-        if (!a || !o) return fail("cogaps_pattern_markers: null argument");
-        if (nRows == 0u || nCols == 0u || oRows == 0u) return fail("cogaps_pattern_markers: a matrix is empty");
-        if (nRows > 0xFFFFFFFFull) return fail("cogaps_pattern_markers: " + std::to_string(nRows) + " rows are more than 32-bit ranks hold");
-        if (oRows > 0xFFFFFFFFull) return fail("cogaps_pattern_markers: " + std::to_string(oRows) + " rows of the other matrix are more than 32 bits hold");
-        if ((lp == nullptr) != (nLp == 0u)) return fail("cogaps_pattern_markers: lp and its length must be given together (NULL and 0: the unit vectors)");
-        for (size_t x = 0; lp && x < (size_t)nLp * nCols; ++x)
-            if (!(lp[x] <= 1.0)) return fail("cogaps_pattern_markers: lp should be a list of vectors with max value of 1");
-        if (threshold != COGAPS_MARKERS_ALL && threshold != COGAPS_MARKERS_CUT) return fail("cogaps_pattern_markers: unknown threshold " + std::to_string(threshold));
-        const uint32_t n = (uint32_t)nRows, m = (uint32_t)oRows, K = nCols, L = lp ? nLp : nCols;
-        const size_t ldn = ((size_t)n + 15u) & ~(size_t)15u, ldm = ((size_t)m + 15u) & ~(size_t)15u;
-        std::vector<double> at, ot;
-        pm_transpose(at, ldn, a, n, K, aRowStride, aColStride);
-        pm_transpose(ot, ldm, o, m, K, oRowStride, oColStride);
-        const size_t nOut = (size_t)n * L, nCol = ldn * L;
-
-        GsScratch g(device);
-        rt_alloc_scope allocOn(g.st);
-        PmArgs p;
-        memset(&p, 0, sizeof(p));
-        p.ldn = ldn; p.ldm = ldm; p.n = n; p.m = m; p.K = K; p.L = L; p.threshold = threshold;
-        const bool small = pm_sort_plan(p);
-        double *dat = g.get<double>(at.size()), *dot = g.get<double>(ot.size());
-        p.at = dat; p.ot = dot;                                              // (everything below is zero-filled)
-        rt_h2d(dat, at.data(), at.size() * 8, g.st);
-        rt_h2d(dot, ot.data(), ot.size() * 8, g.st);
-        if (lp) { double *dlp = g.get<double>((size_t)L * K); rt_h2d(dlp, lp, (size_t)L * K * 8, g.st); p.lp = dlp; }
-        p.colMax = g.get<unsigned long long>(K);
-        p.keys[0] = g.get<unsigned long long>(nCol); p.order[0] = g.get<uint32_t>(nCol);
-        if (!small) {
-            p.keys[1] = g.get<unsigned long long>(nCol); p.order[1] = g.get<uint32_t>(nCol);
-            p.hist = g.get<uint32_t>((size_t)L * PM_THREADS * p.nTiles); p.digitBase = g.get<uint32_t>((size_t)L * PM_THREADS);
-        }
-        p.rankT = g.get<uint32_t>(nCol); p.rowMin = g.get<uint32_t>(n); p.best = g.get<uint32_t>(n);
-        p.nanRows = g.get<uint32_t>(1); p.cutPos = g.get<uint32_t>(L); p.tileCount = g.get<uint32_t>((size_t)L * p.nTiles);
-        p.markerCount = g.get<uint32_t>(L);
-        if (scores) p.scores = g.get<double>(nOut);
-        if (ranks) p.ranks = g.get<uint32_t>(nOut);
-        const std::vector<uint32_t> noCut(L, n);
-        rt_h2d(p.cutPos, noCut.data(), (size_t)L * 4, g.st);
-        if (markers) { p.markers = g.get<uint32_t>(nOut); rt_memset(p.markers, 0xFF, nOut * 4, g.st); }
-
-        const unsigned long long rowBlocks = ((unsigned long long)n + PM_THREADS - 1ull) / PM_THREADS, tiles = (unsigned long long)L * p.nTiles;
-        RT_LAUNCH(pm_colmax_kernel, gs_grid((unsigned long long)K * ((m + PM_TILE_ROWS - 1ull) / PM_TILE_ROWS)), PM_THREADS, g.st, p);
-        RT_LAUNCH(pm_normalise_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
-        RT_LAUNCH(pm_score_kernel, gs_grid(rowBlocks * ((L + PM_LBLOCK - 1u) / PM_LBLOCK)), PM_THREADS, g.st, p);
-        pm_rank_launch(p, small, g.st);
-        RT_LAUNCH(pm_rowmin_kernel, gs_grid(rowBlocks), PM_THREADS, g.st, p);
-        if (markers || markerCount) {
-            if (threshold == COGAPS_MARKERS_CUT) RT_LAUNCH(pm_cutpos_kernel, gs_grid(rowBlocks * L), PM_THREADS, g.st, p);
-            RT_LAUNCH(pm_marker_count_kernel, gs_grid(tiles), PM_THREADS, g.st, p);
-            RT_LAUNCH(pm_marker_scan_kernel, gs_grid((L + 63u) / 64u), 64, g.st, p);
-            if (markers) RT_LAUNCH(pm_marker_write_kernel, gs_grid(tiles), PM_THREADS, g.st, p);
-        }
-        if (ranks) rt_d2h(ranks, p.ranks, nOut * 4, g.st);
-        if (scores) rt_d2h(scores, p.scores, nOut * 8, g.st);
-        if (markers) rt_d2h(markers, p.markers, nOut * 4, g.st);
-        if (markerCount) rt_d2h(markerCount, p.markerCount, (size_t)L * 4, g.st);
-        rt_sync(g.st);
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Result statistics: the enrichment of gene sets in every pattern (gsea_kernel.h)
-// ------------------------------------------------------------------------------------------------
-int cogaps_pattern_gsea(const float *stat, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
-                        uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members,
-                        uint32_t numPerm, uint32_t seed, int device,
-                        double *es, uint32_t *peak, uint32_t *nGe, uint64_t *permSum, uint32_t *rankOut)
-{
-    static_assert(COGAPS_GSEA_MAX_SET == GSEA_MAX_SET, "the header's cap is the kernel's");
-    try {
-        const std::string me = "cogaps_pattern_gsea: ";
-        if (!stat || !memberOffsets || !members || !es || !peak || !nGe || !permSum) return fail(me + "null argument");
-        if (nRows == 0u || nCols == 0u) return fail(me + "the stat matrix is empty");
-        if (nSets == 0u) return fail(me + "nSets must be at least 1");
-        if (numPerm == 0u) return fail(me + "numPerm must be at least 1");
-        if (numPerm == 0xFFFFFFFFu) return fail(me + "numPerm must be below 2^32 - 1");
-        const uint32_t n = nRows, K = nCols;
-        // the values transposed (one column = one run of rows, as the sort wants them); -0 becomes +0, which is the same number
-        const size_t ldn = ((size_t)n + 15u) & ~(size_t)15u, ldk = ((size_t)K + 15u) & ~(size_t)15u;
-        std::vector<float> vt(ldn * K, 0.f);
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t k = 0; k < K; ++k) {
-                const float v = stat[(size_t)i * rowStride + (size_t)k * colStride];
-                if (!(v >= 0.f)) return fail(me + "stat holds a NaN or a negative value (row " + std::to_string(i) + ", column " + std::to_string(k) + "): factor matrices are non-negative");
-                vt[(size_t)k * ldn + i] = v + 0.f;
-            }
-        for (uint32_t t = 0; t < nSets; ++t) {
-            const std::string set = me + "set " + std::to_string(t);
-            if (memberOffsets[t + 1u] < memberOffsets[t]) return fail(set + ": memberOffsets decrease");
-            const uint64_t m = memberOffsets[t + 1u] - memberOffsets[t];
-            if (m == 0u) return fail(set + ": a set without members is not tested");
-            if (m > (uint64_t)GSEA_MAX_SET) return fail(set + ": " + std::to_string(m) + " members are more than GSEA_MAX_SET = " + std::to_string(GSEA_MAX_SET));
-            for (uint64_t i = memberOffsets[t]; i < memberOffsets[t + 1u]; ++i) {
-                if (members[i] >= nRows) return fail(set + ": member " + std::to_string(members[i]) + " is not a row of stat (nRows = " + std::to_string(nRows) + ")");
-                if (i > memberOffsets[t] && members[i] <= members[i - 1u]) return fail(set + ": members are not ascending");
-            }
-            if (m >= (uint64_t)nRows) return fail(set + ": " + std::to_string(m) + " members are not fewer than nRows = " + std::to_string(nRows));
-        }
-
-        GsScratch g(device);
-        rt_alloc_scope allocOn(g.st);
-        // ranks: the markers' stable sort on the descending keys, then (rank, value) of a row's columns side by side
-        float *dvt = g.get<float>(vt.size());
-        rt_h2d(dvt, vt.data(), vt.size() * 4, g.st);
-        PmArgs p;
-        memset(&p, 0, sizeof(p));
-        p.ldn = ldn; p.n = n; p.K = K; p.L = K;
-        const bool small = pm_sort_plan(p);
-        const size_t nCol = ldn * K;
-        p.keys[0] = g.get<unsigned long long>(nCol); p.order[0] = g.get<uint32_t>(nCol); p.rankT = g.get<uint32_t>(nCol);
-        if (!small) {
-            p.keys[1] = g.get<unsigned long long>(nCol); p.order[1] = g.get<uint32_t>(nCol);
-            p.hist = g.get<uint32_t>((size_t)K * PM_THREADS * p.nTiles); p.digitBase = g.get<uint32_t>((size_t)K * PM_THREADS);
-        }
-        const unsigned long long rowBlocks = ((unsigned long long)n + PM_THREADS - 1ull) / PM_THREADS;
-        RT_LAUNCH(gsea_key_kernel, gs_grid(rowBlocks * K), PM_THREADS, g.st, (const float *)dvt, p);
-        pm_rank_launch(p, small, g.st);
-        unsigned long long *pk = g.get<unsigned long long>((size_t)n * ldk);
-        RT_LAUNCH(gsea_pack_kernel, gs_grid(((unsigned long long)n * K + PM_THREADS - 1ull) / PM_THREADS), PM_THREADS, g.st,
-                  (const float *)dvt, (const uint32_t *)p.rankT, ldn, n, K, pk, ldk);
-        if (rankOut) {
-            std::vector<uint32_t> r(nCol);
-            rt_d2h(r.data(), p.rankT, nCol * 4, g.st); rt_sync(g.st);
-            for (uint32_t k = 0; k < K; ++k)
-                for (uint32_t i = 0; i < n; ++i) rankOut[(size_t)k * n + i] = r[(size_t)k * ldn + i] - 1u;
-        }
-
-        // scores: the sets in chunks whose outputs and members stay within a fixed amount of device memory
-        uint64_t chunkSets = pm_test_override("COGAPS_TEST_GSEA_CHUNK_SETS", ((uint64_t)1 << 22) / K);
-        if (chunkSets < 1u) chunkSets = 1u;
-        if (chunkSets > nSets) chunkSets = nSets;
-        const size_t nOut = (size_t)chunkSets * K, maxMem = (size_t)chunkSets * GSEA_MAX_SET < (size_t)(memberOffsets[nSets] - memberOffsets[0]) ? (size_t)chunkSets * GSEA_MAX_SET : (size_t)(memberOffsets[nSets] - memberOffsets[0]);
-        GseaArgs a;
-        memset(&a, 0, sizeof(a));
-        a.pk = pk; a.ldk = ldk; a.nRows = n; a.K = K; a.seed = seed;
-        unsigned long long *dOff = g.get<unsigned long long>(chunkSets + 1u);
-        uint32_t *dMem = g.get<uint32_t>(maxMem);
-        a.memberOffsets = dOff; a.members = dMem;
-        a.es = g.get<double>(nOut); a.peak = g.get<uint32_t>(nOut); a.nGe = g.get<uint32_t>(nOut); a.permSum = g.get<unsigned long long>(nOut);
-        std::vector<unsigned long long> off(chunkSets + 1u);
-        const unsigned long long kBlocks = (K + GSEA_BLOCK - 1u) / GSEA_BLOCK;
-        for (uint64_t t0 = 0; t0 < nSets; t0 += chunkSets) {
-            const uint32_t here = (uint32_t)(nSets - t0 < chunkSets ? nSets - t0 : chunkSets);
-            const uint64_t first = memberOffsets[t0], nMem = memberOffsets[t0 + here] - first;
-            for (uint32_t t = 0; t <= here; ++t) off[t] = memberOffsets[t0 + t] - first;
-            const size_t nHere = (size_t)here * K;
-            rt_h2d(dOff, off.data(), ((size_t)here + 1u) * 8, g.st);
-            rt_h2d(dMem, members + first, (size_t)nMem * 4, g.st);
-            rt_memset(a.nGe, 0, nHere * 4, g.st); rt_memset(a.permSum, 0, nHere * 8, g.st);
-            a.nSets = here; a.setBase = (uint32_t)t0;
-            a.slot0 = 0u; a.nSlots = 1u;                                         // the sets themselves ...
-            RT_LAUNCH(gsea_score_kernel, gs_grid((unsigned long long)here * kBlocks), GSEA_THREADS, g.st, a);
-            a.slot0 = 1u; a.nSlots = numPerm;                                    // ... then their permutations, which compare with them
-            RT_LAUNCH(gsea_score_kernel, gs_grid((unsigned long long)here * ((numPerm + GSEA_PERMS - 1ull) / GSEA_PERMS) * kBlocks), GSEA_THREADS, g.st, a);
-            rt_d2h(es + (size_t)t0 * K, a.es, nHere * 8, g.st); rt_d2h(peak + (size_t)t0 * K, a.peak, nHere * 4, g.st);
-            rt_d2h(nGe + (size_t)t0 * K, a.nGe, nHere * 4, g.st); rt_d2h(permSum + (size_t)t0 * K, a.permSum, nHere * 8, g.st);
-            rt_sync(g.st);                                                       // (off is rewritten for the next chunk)
-        }
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Result statistics: residuals and the chi-square of every gene and sample (residual_kernel.h)
-// ------------------------------------------------------------------------------------------------
-} // extern "C"
-
-static std::string rs_dims(const char *what, uint64_t has, const char *of, uint64_t wants)
-{
-    return std::string("cogaps_residuals: the data has ") + std::to_string(has) + " " + what + ", " + of + " has " + std::to_string(wants) + " rows";
-}
-
-extern "C" {
-
-int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t aColStride,
-                     const float *p, uint32_t nSamples, size_t pRowStride, size_t pColStride, uint32_t nPatterns,
-                     const cogaps_residual_data *data, const uint32_t *rows, uint32_t nRowsOut, int device,
-                     double *geneChiSq, double *sampleChiSq, double *chiSq, double *matrixOut, uint64_t *peakDeviceBytes)
-{
-    try {
-        const uint32_t G = nGenes, N = nSamples, K = nPatterns;
-        if (!a || !p) return fail("cogaps_residuals: null argument");
-        if (G == 0u || N == 0u || K == 0u) return fail("cogaps_residuals: a matrix is empty");
-        if (G > 0xFFFFFF00u) return fail("cogaps_residuals: " + std::to_string(G) + " genes are more than the blocks of 64 count in 32 bits");
-        if ((rows == nullptr) != (nRowsOut == 0u) || (nRowsOut != 0u && !matrixOut)) return fail("cogaps_residuals: rows, their number and matrixOut must be given together");
-        for (uint32_t x = 0; x < nRowsOut; ++x)
-            if (rows[x] >= G) return fail("cogaps_residuals: output row " + std::to_string(x) + " asks for gene " + std::to_string(rows[x]) + ", the result has " + std::to_string(G));
-        const int kind = data ? data->kind : COGAPS_RESIDUAL_DATA_NONE;
-        if (kind == COGAPS_RESIDUAL_DATA_NONE && nRowsOut == 0u) return fail("cogaps_residuals: neither data nor rows: nothing to compute");
-        const cogaps_device_matrix *handle = nullptr;
-        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            uint32_t dr = 0, dc = 0;
-            if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
-                if (!data->dense) return fail("cogaps_residuals: null argument: dense");
-                dr = data->nrow; dc = data->ncol;
-            } else if (kind == COGAPS_RESIDUAL_DATA_SPARSE || kind == COGAPS_RESIDUAL_DATA_COO) {
-                const cogaps_sparse_matrix *sp = kind == COGAPS_RESIDUAL_DATA_SPARSE ? data->sparse : nullptr;
-                const cogaps_coo_matrix *coo = kind == COGAPS_RESIDUAL_DATA_COO ? data->coo : nullptr;
-                if (!sp && !coo) return fail("cogaps_residuals: null argument: the matrix");
-                if (const char *refusal = sparse_args_refusal(sp, coo)) return fail(refusal);
-                dr = sp ? sp->nrow : coo->nrow; dc = sp ? sp->ncol : coo->ncol;
-            } else if (kind == COGAPS_RESIDUAL_DATA_DEVICE_MATRIX) {
-                handle = data->deviceMatrix;
-                if (!handle) return fail("cogaps_residuals: null argument: deviceMatrix");
-                if (device != -1 && device != handle->device)
-                    return fail("cogaps_residuals: the matrix resides on device " + std::to_string(handle->device) + ", the call was given device " + std::to_string(device));
-                device = handle->device;
-                dr = handle->m.nrow; dc = handle->m.ncol;
-            } else return fail("cogaps_residuals: unknown kind of data " + std::to_string(kind));
-            if (kind != COGAPS_RESIDUAL_DATA_DENSE && data->uncertainty)
-                return fail("cogaps_residuals: a sparse matrix takes the default uncertainty only (no uncertainty matrix)");
-            const uint32_t dG = data->transposeData ? dc : dr, dN = data->transposeData ? dr : dc;
-            if (dG != G) return fail(rs_dims("genes", dG, "featureLoadings", G));
-            if (dN != N) return fail(rs_dims("samples", dN, "sampleFactors", N));
-        }
-        const uint32_t nSteps = (uint32_t)(((uint64_t)N + 63u) / 64u), nBlocks = (G + (uint32_t)RS_BLOCK - 1u) / (uint32_t)RS_BLOCK;
-        const size_t ldp = (size_t)nSteps * 64u;
-        // A widened row by row (rows of zeros up to whole blocks), P widened and transposed (zeros past the last sample); the output rows that want each gene
-        std::vector<double> a64((size_t)nBlocks * RS_BLOCK * K, 0.0), pt64((size_t)K * ldp, 0.0);
-        for (size_t i = 0; i < G; ++i)
-            for (size_t k = 0; k < K; ++k) a64[i * K + k] = (double)a[i * aRowStride + k * aColStride];
-        for (size_t j = 0; j < N; ++j)
-            for (size_t k = 0; k < K; ++k) pt64[k * ldp + j] = (double)p[j * pRowStride + k * pColStride];
-        std::vector<uint32_t> outStart, outList(nRowsOut);
-        if (nRowsOut) {
-            outStart.assign((size_t)G + 1u, 0u);
-            for (uint32_t x = 0; x < nRowsOut; ++x) ++outStart[(size_t)rows[x] + 1u];
-            for (size_t i = 0; i < G; ++i) outStart[i + 1u] += outStart[i];
-            std::vector<uint32_t> cursor(outStart.begin(), outStart.end() - 1);
-            for (uint32_t x = 0; x < nRowsOut; ++x) outList[cursor[rows[x]]++] = x;
-        }
-
-        rt_alloc_meter meter;                                                // (outlives everything the call allocates)
-        rt_meter_scope metered(&meter);
-        GsScratch g(device);
-        rt_alloc_scope allocOn(g.st);
-        SpbTemps tmp;
-        RsArgs r;
-        memset(&r, 0, sizeof(r));
-        r.G = G; r.N = N; r.K = K; r.nSteps = nSteps; r.ldp = ldp; r.source = RS_DATA_NONE;
-        double *da = g.get<double>(a64.size()), *dp = g.get<double>(pt64.size());
-        rt_h2d(da, a64.data(), a64.size() * 8, g.st); rt_h2d(dp, pt64.data(), pt64.size() * 8, g.st);
-        r.a64 = da; r.pt64 = dp;
-        if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
-            r.source = RS_DATA_DENSE;
-            r.rowStride = data->transposeData ? data->colStride : data->rowStride;
-            r.colStride = data->transposeData ? data->rowStride : data->colStride;
-            r.data = data->dense; r.unc = data->uncertainty;
-            if (!data->onDevice) {      // the caller's arrays as they lie, from the first element to the last the strides reach
-                const size_t span = (size_t)(G - 1u) * r.rowStride + (size_t)(N - 1u) * r.colStride + 1u;
-                float *dd = g.get<float>(span); rt_h2d(dd, data->dense, span * 4, g.st); r.data = dd;
-                if (data->uncertainty) { float *du = g.get<float>(span); rt_h2d(du, data->uncertainty, span * 4, g.st); r.unc = du; }
-            }
-        } else if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            // the gene side of the sparse model's packed form, by the one builder; nothing of size genes x samples exists
-            SpbMatrix staged; const SpbMatrix *src = &staged;
-            const unsigned cu = rt_compute_units();
-            if (kind == COGAPS_RESIDUAL_DATA_SPARSE) {
-                const cogaps_sparse_matrix &m = *data->sparse;
-                spb_compressed(staged, m, g.st, [&](auto *from, size_t n) { return tmp.stage(from, n, m.onDevice != 0, g.st); });
-            } else if (kind == COGAPS_RESIDUAL_DATA_COO) {
-                const cogaps_coo_matrix &m = *data->coo;
-                spb_triplets(staged, m, tmp.alloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), cu, g.st,
-                             [&](auto *from, size_t n) { return tmp.stage(from, n, m.onDevice != 0, g.st); });
-            } else src = &handle->m;
-            SpbSide side;
-            side.M = G; side.Wn = N / 64u + 1u; side.vals = nullptr;
-            side.swap = (data->transposeData == 0) == src->majorIsRow ? 0u : 1u;      // genes are the data's rows unless transposeData
-            side.flags = g.get<unsigned long long>((size_t)G * side.Wn); side.prefix = g.get<uint32_t>((size_t)G * side.Wn); side.ptr = g.get<uint32_t>((size_t)G + 1u);
-            SpbMap identity; identity.start = identity.list = nullptr; identity.onMajor = 0u;
-            spb_build_sides(*src, identity, false, &side, 1, cu, g.st, [&](int, size_t n) { return g.get<float>(n); });
-            r.source = RS_DATA_PACKED; r.side = side;
-        }
-        double *dSample = nullptr, *dChi = nullptr;
-        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            r.geneChiSq = g.get<double>(G); r.partial = g.get<double>((size_t)nBlocks * ldp);
-            dSample = g.get<double>(N); dChi = g.get<double>(1);
-        }
-        if (nRowsOut) {
-            uint32_t *dStart = g.get<uint32_t>(outStart.size()), *dList = g.get<uint32_t>(nRowsOut);
-            rt_h2d(dStart, outStart.data(), outStart.size() * 4, g.st); rt_h2d(dList, outList.data(), (size_t)nRowsOut * 4, g.st);
-            r.outStart = dStart; r.outList = dList; r.matrixOut = g.get<double>((size_t)nRowsOut * N);
-        }
-        RT_LAUNCH(rs_main_kernel, gs_grid(nBlocks), RS_THREADS, g.st, r);
-        if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            RT_LAUNCH(rs_fold_kernel, (uint32_t)(((uint64_t)N + RS_THREADS - 1u) / RS_THREADS) + 1u, RS_THREADS, g.st, r, dSample, dChi);
-            if (geneChiSq) rt_d2h(geneChiSq, r.geneChiSq, (size_t)G * 8, g.st);
-            if (sampleChiSq) rt_d2h(sampleChiSq, dSample, (size_t)N * 8, g.st);
-            if (chiSq) rt_d2h(chiSq, dChi, 8, g.st);
-        }
-        if (nRowsOut) rt_d2h(matrixOut, r.matrixOut, (size_t)nRowsOut * N * 8, g.st);
-        rt_sync(g.st);
-        if (peakDeviceBytes) *peakDeviceBytes = meter.peak.load();
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
 
 void cogaps_default_params(cogaps_params *p)
 {
@@ -3199,27 +2745,28 @@ int cogaps_session_run_to_end(cogaps_session *s, const char *statePath, uint32_t
     return cogaps_session_finish(s, out);
 }
 
-int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)
+// The one-shot entries' run of the session they have just created: both phases, the result, and the session's end whatever came of
+// them.  s null: the creation has said why (cogaps_last_error).  The iterations are the session's copy of the caller's parameters.
+static int run_once(cogaps_session *s, cogaps_result *out)
 {
-    cogaps_session *s = cogaps_session_create(data, nrow, ncol, params, unc, 0);
     if (!s) return 1;
-    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
+    int rc = cogaps_session_run_iterations(s, 1, 0, s->p.nIterations, nullptr);
+    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, s->p.nIterations, nullptr);
     if (!rc) rc = cogaps_session_finish(s, out);
     cogaps_session_destroy(s);
     return rc;
 }
 
+int cogaps_run(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)
+{
+    if (!out) return fail("null argument");
+    return run_once(cogaps_session_create(data, nrow, ncol, params, unc, 0), out);
+}
+
 int cogaps_run_device(const float *data, uint32_t nrow, uint32_t ncol, const cogaps_params *params, const float *unc, cogaps_result *out)
 {
     if (!out) return fail("null argument");
-    cogaps_session *s = cogaps_session_create(data, nrow, ncol, params, unc, 1);
-    if (!s) return 1;
-    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_finish(s, out);
-    cogaps_session_destroy(s);
-    return rc;
+    return run_once(cogaps_session_create(data, nrow, ncol, params, unc, 1), out);
 }
 
 int cogaps_session_debug_dense_data(cogaps_session *s, char which, float *D, float *Sraw, float *S2, float *lambda, float *maxGibbsMass, float *sparsity, int *hasS2)
@@ -3263,37 +2810,19 @@ int cogaps_session_debug_sparse_data(cogaps_session *s, char which, uint32_t *Wn
 int cogaps_run_sparse(const cogaps_sparse_matrix *m, const cogaps_params *params, cogaps_result *out)
 {
     if (!out) return fail("null argument");
-    cogaps_session *s = cogaps_session_create_sparse(m, params);
-    if (!s) return 1;
-    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_finish(s, out);
-    cogaps_session_destroy(s);
-    return rc;
+    return run_once(cogaps_session_create_sparse(m, params), out);
 }
 
 int cogaps_run_coo(const cogaps_coo_matrix *m, const cogaps_params *params, cogaps_result *out)
 {
     if (!out) return fail("null argument");
-    cogaps_session *s = cogaps_session_create_coo(m, params);
-    if (!s) return 1;
-    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_finish(s, out);
-    cogaps_session_destroy(s);
-    return rc;
+    return run_once(cogaps_session_create_coo(m, params), out);
 }
 
 int cogaps_run_device_matrix(const cogaps_device_matrix *m, const cogaps_params *params, cogaps_result *out)
 {
     if (!out) return fail("null argument");
-    cogaps_session *s = cogaps_session_create_from_device_matrix(m, params);
-    if (!s) return 1;
-    int rc = cogaps_session_run_iterations(s, 1, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_run_iterations(s, 2, 0, params->nIterations, nullptr);
-    if (!rc) rc = cogaps_session_finish(s, out);
-    cogaps_session_destroy(s);
-    return rc;
+    return run_once(cogaps_session_create_from_device_matrix(m, params), out);
 }
 
 // ---- the file entry point (gaps::run(const std::string&...), GapsRunner.h:24-29; cogaps_from_file_cpp, Cogaps.cpp:217-227) ----

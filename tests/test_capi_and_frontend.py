@@ -321,3 +321,29 @@ def test_bench_refuses_to_report_fewer_gpus_than_asked_for():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--no-cpu"], cwd=ROOT, env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"),
                          capture_output=True, text=True, timeout=600)
     assert out.returncode != 0 and "WORLD_SIZE=2" in out.stderr and not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_every_one_shot_run_refuses_a_null_result(emul_lib):
+    """the five cogaps_run* entries with out = NULL and every other argument in order: "null argument", before a session is created.
+    (Not to be run on a build from before the five shared one helper: its cogaps_run handed the null pointer to
+    cogaps_session_finish, which wrote through it.)"""
+    import scipy.sparse as sp
+    from cogaps_amd import _capi
+    lib = emul_lib(256)
+    d = np.ascontiguousarray(np.arange(1, 21, dtype=np.float32).reshape(5, 4))
+    p = _capi.make_params(lib, nPatterns=2, nIterations=2, sparseOptimization=True)
+    csr = _capi.SparseMatrix.from_scipy(sp.csr_matrix(d)).c_struct()
+    r, c = np.nonzero(d)
+    coo = _capi.CooMatrix(d.shape, r.astype(np.uint32), c.astype(np.uint32), d[r, c]).c_struct()
+    with _capi.DeviceMatrix(_capi.SparseMatrix.from_scipy(sp.csr_matrix(d)), lib=lib) as dm:
+        calls = {
+            "cogaps_run": lambda: lib.cogaps_run(_capi._fp(d), 5, 4, ctypes.byref(p), None, None),
+            "cogaps_run_device": lambda: lib.cogaps_run_device(d.ctypes.data, 5, 4, ctypes.byref(p), None, None),
+            "cogaps_run_sparse": lambda: lib.cogaps_run_sparse(ctypes.byref(csr), ctypes.byref(p), None),
+            "cogaps_run_coo": lambda: lib.cogaps_run_coo(ctypes.byref(coo), ctypes.byref(p), None),
+            "cogaps_run_device_matrix": lambda: lib.cogaps_run_device_matrix(dm.h, ctypes.byref(p), None),
+        }
+        for name, call in calls.items():
+            assert lib.cogaps_debug_math(5, 0, None, None, 0, 0) != 0 and b"bad function" in lib.cogaps_last_error()      # (another message in between)
+            assert call() != 0, name
+            assert b"null argument" in lib.cogaps_last_error(), (name, lib.cogaps_last_error())

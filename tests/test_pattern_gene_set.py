@@ -251,3 +251,12 @@ def test_c_entry_refusals(lib):
         assert rc != 0 and msg in err, (kw, err)
         assert lib.cogaps_last_error_code() == _capi.ERR_GENERIC
         valid()
+
+
+def test_the_refusal_names_the_first_offending_element_in_row_major_order(lib):
+    """a NaN at (row 3, column 1) and a negative value at (row 1, column 2): the rows are looked through in order, each by its columns"""
+    stat = np.ascontiguousarray(pc.stat_random()[:20, :3])
+    stat[3, 1], stat[1, 2] = np.nan, -0.5
+    for s in (stat, np.asfortranarray(stat)):
+        with pytest.raises(_capi.CogapsError, match=r"stat holds a NaN or a negative value \(row 1, column 2\)"):
+            _capi.pattern_gsea(s, [[1, 4], [0, 7, 19]], 4, seed=5, lib=lib)

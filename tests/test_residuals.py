@@ -212,6 +212,23 @@ def test_a_sparse_call_holds_less_than_a_quarter_of_a_densification(lib):
         rc.same_bits(out[key], dense[key], key)
 
 
+# peakDeviceBytes of three calls at 70 genes x 130 samples x 3 patterns, rows = [69, 0, 64, 64]: dense host data with an uncertainty
+# matrix, the CSR form of rc.sparse_matrix(), the reconstruction alone.  Taken from the build before the statistics' host code was
+# rewritten around one owner of a call's temporaries (the meter counts requested sizes, so they are exact on the emulator and the device)
+PEAK_BYTES = {"dense": 89620, "sparse": 29812, "reconstruction": 12140}
+
+
+def peak_bytes(lib):
+    A, P = rc.factors(70, 130, 3)
+    D = rc.sparse_matrix()
+    kw = {"dense": dict(data=D, unc=rc.uncertainty_for(D)), "sparse": dict(data=sp.csr_matrix(D)), "reconstruction": {}}
+    return {case: _capi.residuals(A, P, rows=[69, 0, 64, 64], lib=lib, **kw[case])["peakDeviceBytes"] for case in kw}
+
+
+def test_the_allocations_of_a_call_are_pinned(lib):
+    assert peak_bytes(lib) == PEAK_BYTES
+
+
 # ---- 7. refusals ----
 def test_refusals_of_the_entry(lib, sparse_case):
     A, P, D, _ = sparse_case

@@ -7,7 +7,7 @@ import pytest
 import scipy.sparse as sp
 
 import residual_cases as rc
-from test_residuals import EDGES, check_memory, result_of
+from test_residuals import EDGES, PEAK_BYTES, check_memory, peak_bytes, result_of
 from cogaps_amd import CoGAPS, _capi
 
 pytestmark = pytest.mark.gpu
@@ -149,3 +149,7 @@ def test_a_sparse_call_holds_less_than_a_quarter_of_a_densification(hip_lib):
     out, dense = check_memory(hip_lib)
     for key in ("geneChiSq", "sampleChiSq", "chiSq"):
         rc.same_bits(out[key], dense[key], key)
+
+
+def test_the_allocations_of_a_call_are_pinned(hip_lib):
+    assert peak_bytes(hip_lib) == PEAK_BYTES
