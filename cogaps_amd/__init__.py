@@ -1,6 +1,7 @@
 """cogaps_amd -- the CoGAPS asynchronous Gibbs sampler hot path on MI355X (HIP, gfx950).
 
 Public surface mirrors the reference's: CoGAPS(), GWCoGAPS(), scCoGAPS(), CogapsParams, CogapsResult, calcZ(), calcCoGAPSStat() (the gene-set permutation statistic of a result, on the GPU), patternMarkers() (every gene or sample ranked against every pattern, and the marker lists, on the GPU), getPatternGeneSet() (the gene sets of every pattern: enrichment with its permutation null on the GPU, or overrepresentation among the markers),
+findConsensusMatrix() / patternMatch() (the consensus of the patterns of a distributed run's first pass -- correlation distance, complete linkage, weighted mean patterns -- on the GPU),
 reconstructGene(), residuals() (plotResiduals' matrix and the chi-square of every gene and sample, on the GPU; sparse data stays sparse), binaryA(),
 DeviceMatrix (a sparse matrix uploaded to the GPU once, the source of any number of runs and subsets), DeviceDense (a dense matrix that
 already resides on the GPU, by address; a torch tensor on the GPU is taken as one by every entry point), buildReport(), checkpointsEnabled(), compiledWithOpenMPSupport().  CoGAPS(..., stateFile=, stateInterval=, resume=) saves a run's chain to the
@@ -9,6 +10,7 @@ csrc/libcogaps_hip.so (include/cogaps_hip.h); importing works without a GPU, run
 from .params import CogapsParams
 from .result import CogapsResult, calcZ, calcCoGAPSStat, patternMarkers, getPatternGeneSet, reconstructGene, residuals, binaryA
 from .api import CoGAPS, GWCoGAPS, scCoGAPS
+from .distributed import findConsensusMatrix, patternMatch
 from ._capi import DeviceMatrix, DeviceDense
 
 
@@ -27,4 +29,5 @@ def compiledWithOpenMPSupport():
 
 
 __all__ = ["CoGAPS", "GWCoGAPS", "scCoGAPS", "CogapsParams", "CogapsResult", "DeviceMatrix", "DeviceDense", "buildReport", "checkpointsEnabled",
-           "compiledWithOpenMPSupport", "calcZ", "calcCoGAPSStat", "patternMarkers", "getPatternGeneSet", "reconstructGene", "residuals", "binaryA"]
+           "compiledWithOpenMPSupport", "calcZ", "calcCoGAPSStat", "patternMarkers", "getPatternGeneSet", "reconstructGene", "residuals", "binaryA",
+           "findConsensusMatrix", "patternMatch"]

@@ -106,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -237,6 +237,8 @@ def bind(L):
     L.cogaps_pattern_gsea.argtypes = [fp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, dp, u32p, u32p, u64p, u32p]
     L.cogaps_residuals.argtypes = [fp, C.c_uint32, C.c_size_t, C.c_size_t, fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(CogapsResidualDataC),
                                    u32p, C.c_uint32, C.c_int, dp, dp, dp, dp, u64p]
+    L.cogaps_pattern_match.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                       u32p, u32p, dp, fp, dp, u32p]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -1168,6 +1170,53 @@ def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=
         raise _error(L)
     return {"matrix": out, "geneChiSq": gene if have else None, "sampleChiSq": sample if have else None,
             "chiSq": float(chi.value) if have else None, "peakDeviceBytes": int(peak.value)}
+
+
+PATTERN_MATCH_MAX_COLS = 4096         # COGAPS_PATTERN_MATCH_MAX_COLS
+
+
+def pattern_match(patterns, cut, minNS, maxNS, device=-1, lib=None, debug=False):
+    """cogaps_pattern_match: the consensus of the gathered patterns (L x n, one pattern per column).  patterns: a numpy
+    array (float32, any strides: a column-major array goes in as it is) or a torch tensor -- on the GPU it goes by address, like a
+    DeviceDense, after its stream is synchronised, and `device` follows it.
+    -> {"nClusters": int, "cluster": uint32 [n] (1-based, in the order of clusteredPatterns; 0: dropped), "corr": float64 [n] (the rounded
+    correlation with the cluster's mean pattern; NaN: dropped), "consensus": float32 [L][nClusters]; with debug=True "dist": float64
+    [n][n] and "firstLabels": uint32 [n], the labels of the first corcut before its minNS filter}"""
+    L = lib if lib is not None else load()
+    keep, on_device = None, 0
+    if on_gpu(patterns):
+        import torch
+        if patterns.dim() != 2:
+            raise ValueError("patterns must be a matrix")
+        dev = patterns.device.index if patterns.device.index is not None else torch.cuda.current_device()
+        if int(device) not in (-1, dev):
+            raise ValueError("the pattern tensor resides on device %d, the call was given device=%d" % (dev, int(device)))
+        keep = patterns.detach()
+        if keep.dtype != torch.float32 or any(st < 0 for st in keep.stride()):
+            keep = keep.to(dtype=torch.float32).contiguous()
+        torch.cuda.current_stream(keep.device).synchronize()
+        addr, shape, strides, device, on_device = keep.data_ptr(), tuple(keep.shape), tuple(keep.stride()), dev, 1
+    else:
+        if is_tensor(patterns):
+            patterns = patterns.detach().cpu().numpy()
+        keep = _strided(patterns, np.float32, "patterns must be a matrix")
+        addr, shape, strides = keep.ctypes.data, keep.shape, tuple(st // 4 for st in keep.strides)
+    rows, n = int(shape[0]), int(shape[1])
+    count = C.c_uint32(0)
+    cluster, corr = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.float64)
+    consensus = np.empty(max(rows * n, 1), dtype=np.float32)
+    dist = np.zeros((n, n), dtype=np.float64) if debug else None
+    first = np.zeros(max(n, 1), dtype=np.uint32) if debug else None
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    if L.cogaps_pattern_match(addr, rows, n, strides[0], strides[1], on_device, int(cut), int(minNS), int(maxNS), int(device),
+                              C.byref(count), cluster.ctypes.data_as(u32p), corr.ctypes.data_as(dp), _fp(consensus),
+                              dist.ctypes.data_as(dp) if debug else None, first.ctypes.data_as(u32p) if debug else None):
+        raise _error(L)
+    k = int(count.value)
+    out = {"nClusters": k, "cluster": cluster[:n], "corr": corr[:n], "consensus": consensus[:rows * k].reshape(rows, k).copy()}
+    if debug:
+        out["dist"], out["firstLabels"] = dist, first[:n]
+    return out
 
 
 def device_memory(device=-1, lib=None):

@@ -64,7 +64,7 @@ def check_inputs(data, uncertainty, params, snapshotPhase="sampling", nSnapshots
 def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputFrequency=1000, uncertainty=None,
            checkpointOutFile="gaps_checkpoint.out", checkpointInterval=0, checkpointInFile=None, transposeData=False,
            BPPARAM=None, workerID=1, asynchronousUpdates=True, nSnapshots=0, snapshotPhase="sampling", device=-1,
-           stateFile=None, stateInterval=0, resume=False, sampler=None, **extra):
+           stateFile=None, stateInterval=0, resume=False, sampler=None, consensus="host", **extra):
     if params is None:
         params = CogapsParams(**({} if nPatterns is None else {"nPatterns": nPatterns}))
     else:
@@ -76,6 +76,8 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
     if sampler is not None:                                      # "async" | "sequential" (CogapsParams.sampler; include/cogaps_hip.h)
         params.setParam("sampler", sampler)
     params.validate()
+    if consensus not in ("host", "device"):                      # where a distributed run matches its patterns (distributed.py)
+        raise ValueError("consensus must be 'host' or 'device', not %r" % (consensus,))
     path = data if isinstance(data, str) else None
     subset = params.subsetIndices is not None and params.subsetDim > 0     # a distributed worker's call: the run takes these rows / columns only
     subset_by_rows = (params.subsetDim == 1) != bool(transposeData)         # genes are the data's rows unless transposeData
@@ -141,7 +143,7 @@ def CoGAPS(data, params=None, nPatterns=None, nThreads=1, messages=True, outputF
         # flight per GPU, run as batches of lock-stepped chains (an int, or an object with a `workers` attribute; default 16 = two batches of eight)
         in_flight = 16 if BPPARAM is None else int(getattr(BPPARAM, "workers", BPPARAM))
         raw = distributedCogaps(data, params, unc, messages=messages, outputFrequency=outputFrequency, transposeData=transposeData, device=device,
-                                shardsInFlight=in_flight, nSnapshots=nSnapshots, snapshotPhase=snapshotPhase)
+                                shardsInFlight=in_flight, nSnapshots=nSnapshots, snapshotPhase=snapshotPhase, consensus=consensus)
     else:
         subset_kw = dict(subsetIndices=params.subsetIndices, subsetDim=params.subsetDim)
         if subset and isinstance(data, _capi.CooMatrix):

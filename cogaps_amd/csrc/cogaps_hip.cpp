@@ -24,6 +24,7 @@
 #include "markers_kernel.h"
 #include "gsea_kernel.h"
 #include "residual_kernel.h"
+#include "consensus_kernel.h"
 
 #include <math.h>
 #include <cmath>

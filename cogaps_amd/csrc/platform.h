@@ -21,6 +21,7 @@ inline double cg_shfl_xor_f64(double v, int mask)
     double r; memcpy(&r, w, 8); return r;
 }
 inline double cg_fma_f64(double a, double b, double c) { return __builtin_fma(a, b, c); }      // a * b + c rounded once
+inline uint32_t cg_shfl_xor_u32(uint32_t v, int mask) { float f; memcpy(&f, &v, 4); const float g = cgemu::wave_exchange_f32(f, mask); uint32_t r; memcpy(&r, &g, 4); return r; }
 #else
 #include <hip/hip_runtime.h>
 
@@ -165,6 +166,7 @@ CG_DEVICE bool cg_poll_expired(uint32_t spins) { return spins > (1u << 22); }
 CG_DEVICE float cg_shfl_xor_f32(float v, int mask) { return __shfl_xor(v, mask, 64); }
 CG_DEVICE float cg_shfl_f32(float v, int lane) { return __shfl(v, lane, 64); }
 CG_DEVICE double cg_shfl_xor_f64(double v, int mask) { return __shfl_xor(v, mask, 64); }
+CG_DEVICE uint32_t cg_shfl_xor_u32(uint32_t v, int mask) { return (uint32_t)__shfl_xor((int)v, mask, 64); }
 // a * b + c rounded once (the build contracts nothing by itself: -ffp-contract=off)
 CG_DEVICE double cg_fma_f64(double a, double b, double c) { return __builtin_fma(a, b, c); }
 // the value lane `lane` holds (lane: the same in every lane of the wave) -- a lane read instead of an LDS-crossbar permute

@@ -1,11 +1,11 @@
-// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.11): host code only, a chapter of cogaps_hip.cpp, which includes
+// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.12): host code only, a chapter of cogaps_hip.cpp, which includes
 // it once, after everything it takes from there:
 //   fail, fail_exc                    the one home of the library's error message
 //   SpbTemps, SpbMatrix, SpbSide, SpbMap, sparse_args_refusal, spb_compressed, spb_triplets, spb_build_sides
 //                                     the sparse builder's helpers (cogaps_residuals reads the gene side of its packed form)
 //   cogaps_device_matrix              the handle cogaps_residuals takes as data
-// and after the kernel headers geneset_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h.  The entries here:
-// cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals.
+// and after the kernel headers geneset_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h.  The entries here:
+// cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match.
 #pragma once
 
 // One call's device and stream, its device memory, and the stream announced for its allocations' fills.  However the call ends they go
@@ -477,6 +477,154 @@ int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t 
         if (nRowsOut) rt_d2h(matrixOut, r.matrixOut, (size_t)nRowsOut * N * 8, g.st);
         rt_sync(g.st);
         if (peakDeviceBytes) *peakDeviceBytes = meter.peak.load();
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Consensus patterns: the step between the passes of a distributed run (consensus_kernel.h)
+// ------------------------------------------------------------------------------------------------
+} // extern "C"
+
+static_assert(COGAPS_PATTERN_MATCH_MAX_COLS == CS_MAX_COLS, "the header's limit is the clustering kernel's");
+
+// What one clustering works with: the distances, the matrix it destroys, the list of its columns and of its merges on the device
+struct CsCutree {
+    GsScratch &g;
+    const double *dist; size_t ld;
+    double *w; uint32_t *dCols, *dMerges;
+    // cutree(agnes(complete), k) of the sub-block of dist of `cols` (null: all m columns): the label of every one, 1-based, numbered
+    // by first appearance.  k >= m: singletons, nothing is launched.
+    std::vector<uint32_t> labels(const std::vector<uint32_t> *cols, uint32_t m, uint32_t k)
+    {
+        std::vector<uint32_t> root(m), label(m, 0u), ofRoot(m, 0u);
+        for (uint32_t i = 0; i < m; ++i) root[i] = i;
+        if (k < m) {
+            if (cols) rt_h2d(dCols, cols->data(), (size_t)m * 4, g.st);
+            RT_LAUNCH(cs_gather_kernel, gs_grid(((unsigned long long)m * m + CS_THREADS - 1ull) / CS_THREADS), CS_THREADS, g.st,
+                      dist, ld, cols ? (const uint32_t *)dCols : (const uint32_t *)nullptr, m, w, (size_t)m);
+            RT_LAUNCH(cs_link_kernel, 1, CS_LINK_THREADS, g.st, w, (size_t)m, m, k, dMerges);
+            std::vector<uint32_t> merges(2u * (size_t)(m - k));
+            rt_d2h(merges.data(), dMerges, merges.size() * 4, g.st); rt_sync(g.st);
+            for (size_t s = 0; s < merges.size(); s += 2) {
+                const uint32_t lo = merges[s], hi = merges[s + 1u];
+                if (lo >= hi || hi >= m || root[hi] != hi) throw std::runtime_error("cogaps_pattern_match: the clustering left no pair to merge");
+                root[hi] = lo;
+            }
+            for (uint32_t i = 0; i < m; ++i) root[i] = root[root[i]];      // (a cluster keeps its lowest index: root[i] <= i, resolved before i)
+        }
+        uint32_t next = 0;
+        for (uint32_t i = 0; i < m; ++i) {
+            if (!ofRoot[root[i]]) ofRoot[root[i]] = ++next;
+            label[i] = ofRoot[root[i]];
+        }
+        return label;
+    }
+    // corcut: the clusters of `cols` (null: all m columns) with minNS members or more, in the order of their first members, as columns of X
+    std::vector<std::vector<uint32_t>> cut(const std::vector<uint32_t> *cols, uint32_t m, uint32_t k, uint32_t minNS, std::vector<uint32_t> *labelsOut = nullptr)
+    {
+        const std::vector<uint32_t> label = labels(cols, m, k);
+        uint32_t most = 0;
+        for (uint32_t l : label) most = l > most ? l : most;
+        std::vector<std::vector<uint32_t>> all(most), kept;
+        for (uint32_t i = 0; i < m; ++i) all[label[i] - 1u].push_back(cols ? (*cols)[i] : i);
+        for (auto &c : all) if (c.size() >= (size_t)minNS) kept.push_back(std::move(c));
+        if (labelsOut) *labelsOut = label;
+        return kept;
+    }
+};
+
+extern "C" {
+
+int cogaps_pattern_match(const float *patterns, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride, int onDevice,
+                         uint32_t cut, uint32_t minNS, uint32_t maxNS, int device,
+                         uint32_t *nClusters, uint32_t *cluster, double *corr, float *consensus, double *dist, uint32_t *firstLabels)
+{
+    try {
+        const std::string me = "cogaps_pattern_match: ";
+        if (!patterns || !nClusters || !cluster || !consensus) return fail(me + "null argument");
+        if (nRows == 0u || nCols == 0u) return fail(me + "the pattern matrix is empty");
+        if (nCols < 2u) return fail(me + "nCols must be at least 2: one pattern has nothing to be matched with");
+        if (cut == 0u) return fail(me + "cut must be at least 1");
+        if (minNS == 0u) return fail(me + "minNS must be at least 1");
+        if (maxNS < minNS) return fail(me + "maxNS = " + std::to_string(maxNS) + " is below minNS = " + std::to_string(minNS));
+        if (nCols > CS_MAX_COLS) return fail(me + std::to_string(nCols) + " patterns are more than COGAPS_PATTERN_MATCH_MAX_COLS = " + std::to_string(CS_MAX_COLS));
+        const uint32_t L = nRows, n = nCols;
+
+        GsScratch g(device);
+        CsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.L = L; a.n = n; a.nChunks = (uint32_t)(((uint64_t)L + CS_KC - 1u) / CS_KC); a.ldx = ((size_t)n + CS_TILE - 1u) / CS_TILE * CS_TILE;
+        a.rowStride = rowStride; a.colStride = colStride;
+        // the caller's array as it lies, from the first element to the last the strides reach -- or where it lies on the device
+        a.x = g.mem.stage(patterns, (size_t)(L - 1u) * rowStride + (size_t)(n - 1u) * colStride + 1u, onDevice != 0, g.st);
+        a.xr = g.get<float>((size_t)L * a.ldx); a.partial = g.get<double>((size_t)a.nChunks * a.ldx); a.mean = g.get<double>(a.ldx);
+        a.c = g.get<double>((size_t)n * a.ldx); a.dist = g.get<double>((size_t)n * a.ldx); a.flags = g.get<uint32_t>(4);
+        const unsigned long long colBlocks = ((unsigned long long)n + CS_THREADS - 1ull) / CS_THREADS, tiles = a.ldx / CS_TILE;
+        uint32_t flags[4] = {0u, 0u, 0u, 0u};
+        RT_LAUNCH(cs_stage_kernel, gs_grid(tiles * (((unsigned long long)L + CS_TILE - 1ull) / CS_TILE)), CS_THREADS, g.st, a);
+        RT_LAUNCH(cs_colsum_kernel<float>, gs_grid(colBlocks * a.nChunks), CS_THREADS, g.st, (const float *)a.xr, a.ldx, L, n, a.nChunks, a.partial, a.ldx);
+        RT_LAUNCH(cs_mean_kernel, gs_grid(colBlocks), CS_THREADS, g.st, (const double *)a.partial, a.ldx, L, n, a.nChunks, a.mean);
+        rt_d2h(flags, a.flags, sizeof(flags), g.st); rt_sync(g.st);
+        if (flags[CS_FLAG_INPUT]) return fail(me + "the patterns hold a NaN or a negative value: factor matrices are non-negative");
+        RT_LAUNCH(cs_cross_kernel, gs_grid(tiles * (tiles + 1ull) / 2ull), CS_THREADS, g.st, a);
+        RT_LAUNCH(cs_dist_kernel, gs_grid(((unsigned long long)n * n + CS_THREADS - 1ull) / CS_THREADS), CS_THREADS, g.st, a);
+        rt_d2h(flags, a.flags, sizeof(flags), g.st); rt_sync(g.st);
+        if (flags[CS_FLAG_DIST]) return fail(me + "NA values in correlation of patterns");
+        if (dist) {
+            std::vector<double> padded((size_t)n * a.ldx);
+            rt_d2h(padded.data(), a.dist, padded.size() * 8, g.st); rt_sync(g.st);
+            for (size_t i = 0; i < n; ++i) memcpy(dist + i * n, padded.data() + i * a.ldx, (size_t)n * 8);
+        }
+
+        // patternMatch: corcut of everything, then the first cluster above maxNS is split in two until none is left (a handful of integers: host)
+        CsCutree tree{g, a.dist, a.ldx, g.get<double>((size_t)n * n), g.get<uint32_t>(n), g.get<uint32_t>(2u * (size_t)n)};
+        std::vector<uint32_t> first;
+        std::vector<std::vector<uint32_t>> clusters = tree.cut(nullptr, n, cut, minNS, &first);
+        if (firstLabels) memcpy(firstLabels, first.data(), (size_t)n * 4);
+        for (;;) {
+            size_t big = 0;
+            while (big < clusters.size() && clusters[big].size() <= (size_t)maxNS) ++big;
+            if (big == clusters.size()) break;
+            std::vector<std::vector<uint32_t>> parts = tree.cut(&clusters[big], (uint32_t)clusters[big].size(), 2u, minNS);
+            if (parts.empty()) { clusters.erase(clusters.begin() + (ptrdiff_t)big); continue; }
+            clusters[big] = std::move(parts[0]);
+            if (parts.size() > 1u) clusters.push_back(std::move(parts[1]));
+        }
+        if (clusters.empty()) return fail(me + "no cluster of patterns reaches minNS members");
+
+        // the clusters' statistics: their members one after the other
+        const uint32_t nC = (uint32_t)clusters.size();
+        std::vector<uint32_t> start(nC + 1u, 0u), slotCol, slotCluster;
+        for (uint32_t c = 0; c < nC; ++c) {
+            for (uint32_t col : clusters[c]) { slotCol.push_back(col); slotCluster.push_back(c); }
+            start[c + 1u] = (uint32_t)slotCol.size();
+        }
+        CsClusterArgs s;
+        memset(&s, 0, sizeof(s));
+        s.xr = a.xr; s.ldx = a.ldx; s.mean = a.mean; s.c = a.c; s.L = L; s.nChunks = a.nChunks; s.nC = nC; s.T = (uint32_t)slotCol.size();
+        s.start = g.up(start); s.slotCol = g.up(slotCol); s.slotCluster = g.up(slotCluster);
+        s.ldc = pad16(nC);
+        s.mp = g.get<double>((size_t)L * s.ldc); s.mpw = g.get<double>((size_t)L * s.ldc);
+        s.partial = g.get<double>((size_t)a.nChunks * s.ldc); s.mpMean = g.get<double>(s.ldc); s.maxPart = g.get<double>((size_t)a.nChunks * s.ldc);
+        s.cpart = g.get<double>((size_t)a.nChunks * (s.T + nC)); s.r = g.get<double>(s.T); s.w = g.get<double>(s.T);
+        s.consensus = g.get<float>((size_t)L * nC); s.flags = a.flags;
+        const unsigned long long cells = ((unsigned long long)L * nC + CS_THREADS - 1ull) / CS_THREADS, cBlocks = ((unsigned long long)nC + CS_THREADS - 1ull) / CS_THREADS;
+        RT_LAUNCH(cs_meanpat_kernel, gs_grid(cells), CS_THREADS, g.st, s);
+        RT_LAUNCH(cs_colsum_kernel<double>, gs_grid(cBlocks * a.nChunks), CS_THREADS, g.st, (const double *)s.mp, s.ldc, L, nC, a.nChunks, s.partial, s.ldc);
+        RT_LAUNCH(cs_mean_kernel, gs_grid(cBlocks), CS_THREADS, g.st, (const double *)s.partial, s.ldc, L, nC, a.nChunks, s.mpMean);
+        RT_LAUNCH(cs_cluster_cross_kernel, gs_grid((((unsigned long long)s.T + nC + CS_THREADS - 1ull) / CS_THREADS) * a.nChunks), CS_THREADS, g.st, s);
+        RT_LAUNCH(cs_corr_kernel, gs_grid(((unsigned long long)s.T + CS_THREADS - 1ull) / CS_THREADS), CS_THREADS, g.st, s);
+        RT_LAUNCH(cs_wmean_kernel, gs_grid(cells), CS_THREADS, g.st, s);
+        RT_LAUNCH(cs_colmax_kernel, gs_grid(cBlocks * a.nChunks), CS_THREADS, g.st, s);
+        RT_LAUNCH(cs_consensus_kernel, gs_grid(cells), CS_THREADS, g.st, s);
+        std::vector<double> r(s.T);
+        rt_d2h(r.data(), s.r, (size_t)s.T * 8, g.st); rt_d2h(flags, a.flags, sizeof(flags), g.st); rt_sync(g.st);
+        if (flags[CS_FLAG_CORR]) return fail(me + "NA values in correlation of patterns");
+        rt_d2h(consensus, s.consensus, (size_t)L * nC * 4, g.st); rt_sync(g.st);
+        for (uint32_t j = 0; j < n; ++j) { cluster[j] = 0u; if (corr) corr[j] = (double)NAN; }
+        for (uint32_t t = 0; t < s.T; ++t) { cluster[slotCol[t]] = slotCluster[t] + 1u; if (corr) corr[slotCol[t]] = r[t]; }
+        *nClusters = nC;
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

@@ -6,7 +6,11 @@ subset per GPU.
   all-gather of the shared factor  :71-74  (sampleFactors for genome-wide, featureLoadings for single-cell)
                                    -> torch.distributed.all_gather (RCCL over xGMI on GPUs, gloo in CPU tests)
   findConsensusMatrix              :129-217 (cor -> 1-cor -> complete linkage -> cutree -> split -> cubic-weighted
-                                   mean -> max-normalise), computed redundantly on every rank
+                                   mean -> max-normalise), computed redundantly on every rank: on the host in float64 numpy
+                                   (find_consensus_matrix, consensus="host", the default) or on the GPU by the library's
+                                   definition (cogaps_pattern_match; consensus="device": with an NCCL group the
+                                   gathered factor never leaves the device).  findConsensusMatrix / patternMatch, the reference's
+                                   exported functions, are the GPU path for a caller's own pipeline
   pass 2: fixed matrix             :86-97
   stitchTogether                   :226-278
 
@@ -212,6 +216,28 @@ def find_consensus_matrix(unmatched, params):
     return pattern_match(np.concatenate(unmatched, axis=1), params)
 
 
+def patternMatch(allPatterns, gapsParams, device=-1, lib=None):
+    """The reference's patternMatch (R/DistributedCogaps.R:145-177) on the GPU: cogaps_pattern_match, whose every output is defined bit
+    for bit (fp64 in fixed orders -- pattern_match above is the float64 numpy form, whose sums follow the BLAS).
+    allPatterns: one pattern per column, a numpy array or a torch tensor (on the GPU it is read where it lies).  -> {"clusteredPatterns":
+    per cluster the matrix of its columns, "consensus": float32 [rows][clusters], "CorrToMeanPattern": per cluster the rounded
+    correlation of every member with the cluster's mean pattern}.  A constant column, which the host form turns into a NaN, is an error."""
+    out = _capi.pattern_match(allPatterns, gapsParams.cut, gapsParams.minNS, gapsParams.maxNS, device=device, lib=lib)
+    host = allPatterns.detach().cpu().numpy() if _capi.is_tensor(allPatterns) else np.asarray(allPatterns)
+    members = [np.nonzero(out["cluster"] == c + 1)[0] for c in range(out["nClusters"])]
+    return {"clusteredPatterns": [host[:, m] for m in members], "consensus": out["consensus"],
+            "CorrToMeanPattern": [out["corr"][m] for m in members]}
+
+
+def findConsensusMatrix(unmatchedPatterns, gapsParams, device=-1, lib=None):
+    """The reference's findConsensusMatrix (R/DistributedCogaps.R:129-135) on the GPU: patternMatch of the matrices side by side"""
+    if all(_capi.on_gpu(m) for m in unmatchedPatterns):
+        import torch
+        return patternMatch(torch.cat(list(unmatchedPatterns), dim=1), gapsParams, device=device, lib=lib)
+    host = [m.detach().cpu().numpy() if _capi.is_tensor(m) else np.asarray(m) for m in unmatchedPatterns]
+    return patternMatch(np.concatenate(host, axis=1), gapsParams, device=device, lib=lib)
+
+
 # ------------------------------------------------------------------------------------------------
 def _dist():
     try:
@@ -223,8 +249,9 @@ def _dist():
     return None
 
 
-def _all_gather_arrays(local, shapes, dist, device):
-    """all-gather a list of equally shaped fp32 matrices per owned subset; returns them in subset order"""
+def _all_gather_arrays(local, shapes, dist, device, stacked=False):
+    """all-gather a list of equally shaped fp32 matrices per owned subset; returns them in subset order -- with stacked=True beside
+    the tensor of all of them side by side, in subset order, on `device` (what the device consensus reads where it lies)"""
     import torch
     world, rank = dist.get_world_size(), dist.get_rank()
     n_sets = len(shapes)
@@ -238,6 +265,8 @@ def _all_gather_arrays(local, shapes, dist, device):
     for r in range(world):
         for slot, i in enumerate(range(r, n_sets, world)):
             res[i] = out[r][slot].cpu().numpy()
+    if stacked:
+        return res, torch.cat([out[i % world][i // world] for i in range(n_sets)], dim=1)
     return res
 
 
@@ -427,7 +456,12 @@ class _Source:
 
 
 def distributedCogaps(data, params, uncertainty=None, messages=False, outputFrequency=1000, transposeData=False,
-                      device=-1, run_fn=None, comm_device=None, shardsInFlight=16, nSnapshots=0, snapshotPhase="sampling", shape=None):
+                      device=-1, run_fn=None, comm_device=None, shardsInFlight=16, nSnapshots=0, snapshotPhase="sampling", shape=None,
+                      consensus="host"):
+    """consensus: "host" -- find_consensus_matrix, float64 numpy -- or "device": the library's cogaps_pattern_match, on the
+    gathered tensor itself where the group gathers on the GPU"""
+    if consensus not in ("host", "device"):
+        raise ValueError("consensus must be 'host' or 'device', not %r" % (consensus,))
     _ipc_mode_for_rccl()
     run_fn = run_fn or _capi.run
     shardsInFlight = max(1, int(shardsInFlight))
@@ -499,10 +533,17 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         local = {i: initial[i][key] for i in mine}
         if dist is not None:
             shape = next(iter(local.values())).shape
-            unmatched = _all_gather_arrays(local, [shape] * len(sets), dist, comm_device)
+            unmatched = _all_gather_arrays(local, [shape] * len(sets), dist, comm_device, stacked=consensus == "device")
+            if consensus == "device":
+                unmatched, gathered = unmatched
         else:
             unmatched = [local[i] for i in range(len(sets))]
-        matched = find_consensus_matrix(unmatched, params)
+        if consensus == "device":
+            # the gathered tensor where it lies (an NCCL group), else the concatenation uploaded once
+            on_device = dist is not None and _capi.on_gpu(gathered)
+            matched = patternMatch(gathered if on_device else np.concatenate(unmatched, axis=1), params, device=-1 if on_device else device)
+        else:
+            matched = find_consensus_matrix(unmatched, params)
         if dist is not None:
             # the consensus is computed redundantly on every rank from the gathered patterns: the second pass is only meaningful
             # if all ranks hold the same bits -- checked, not assumed
@@ -561,5 +602,5 @@ def distributedCogaps(data, params, uncertainty=None, messages=False, outputFreq
         out["firstPass"] = initial
         out["unmatchedPatterns"] = unmatched
         out["clusteredPatterns"] = matched["clusteredPatterns"]
-        out["CorrToMeanPattern"] = [corr_to_mean_pattern(c) for c in matched["clusteredPatterns"]]
+        out["CorrToMeanPattern"] = matched["CorrToMeanPattern"] if "CorrToMeanPattern" in matched else [corr_to_mean_pattern(c) for c in matched["clusteredPatterns"]]
     return out

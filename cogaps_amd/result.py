@@ -120,6 +120,10 @@ class CogapsResult:
     def getClusteredPatterns(self):
         return self.metadata["diagnostics"].get("clusteredPatterns")
 
+    def getCorrelationToMeanPattern(self):
+        """per cluster the rounded correlation of every member with the cluster's mean pattern (a distributed run's; else None)"""
+        return self.metadata["diagnostics"].get("CorrToMeanPattern")
+
     def calcZ(self, whichMatrix="featureLoadings"):
         """R/methods-CogapsResult.R:220-231: mean / standard deviation of the chosen matrix in float64; a zero deviation becomes 1e-6"""
         if whichMatrix not in _WHICH:

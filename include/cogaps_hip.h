@@ -615,6 +615,41 @@ int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t 
                      const cogaps_residual_data *data, const uint32_t *rows, uint32_t nRowsOut, int device,
                      double *geneChiSq, double *sampleChiSq, double *chiSq, double *matrixOut, uint64_t *peakDeviceBytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * Consensus patterns: the step between the two passes of a distributed run -- the reference's findConsensusMatrix / patternMatch
+ * (R/DistributedCogaps.R:129-217).
+ *
+ * patterns: the gathered patterns, one per column: nRows x nCols floats, element (k, j) at patterns[k * rowStride + j * colStride]
+ * (rowStride = nCols, colStride = 1 for a row-major matrix; rowStride = 1, colStride = nRows for R's column-major one).  onDevice = 0:
+ * host memory, uploaded once per call; onDevice = 1: a device pointer of `device`, read where it lies (complete before the call).
+ * All arithmetic is fp64 on the exactly widened floats, every product rounded before it is added, and every sum over the rows follows
+ * one rule: chunks of 4096 consecutive rows, a chunk's terms added in ascending row order from +0.0, the chunk sums in ascending chunk
+ * order from +0.0.  With mean[j] = (sum of column j) / nRows and y[k][j] = x[k][j] - mean[j]:
+ *   c[i][j]    = sum over k of y[k][i] * y[k][j]               dist[i][j] = 1 - c[i][j] / (sqrt(c[i][i]) * sqrt(c[j][j]))
+ *   corcut(columns, k, minNS): complete linkage of the columns' sub-block of dist down to k clusters -- the smallest distance is
+ *                merged, ties go to the pair whose lower index is smallest, then whose higher index is smallest; the merged cluster
+ *                keeps the lower index and the maximum of the two distances to every other; clusters are numbered by first
+ *                appearance, k >= the number of columns gives singletons -- of which those with minNS columns or more are kept
+ *   patternMatch: corcut(all, cut, minNS); while a cluster has more than maxNS columns the first such is split by corcut(cluster, 2,
+ *                minNS): its first part replaces it, a second part is appended, a cluster that leaves no part is dropped
+ *   per cluster with the columns m_1 < ... < m_q:  meanPat[k] = (x[k][m_1] + ... + x[k][m_q]) / q;  cor_j = the correlation of column
+ *                m_j with meanPat by the formulas above;  r_j = rint(1000 * cor_j) / 1000;  w_j = (r_j * r_j) * r_j;
+ *                mp[k] = (x[k][m_1] * w_1 + ... + x[k][m_q] * w_q) / (w_1 + ... + w_q), both sums ascending from +0.0;
+ *                consensus[k] = (float)(mp[k] / max over k of mp[k])
+ * Outputs: nClusters [1]; cluster [nCols]: the 1-based cluster of every column in the order of the reference's clusteredPatterns, 0 for
+ * a dropped one; corr [nCols] (may be NULL): r_j of every column, NaN for a dropped one; consensus: room for nRows x nCols floats, of
+ * which the first nRows x nClusters are written, row-major [nRows][nClusters]; dist [nCols][nCols] and firstLabels [nCols] (the labels
+ * of the first corcut before its minNS filter), both for tests, may be NULL.  No output depends on the device, on the grid or on
+ * scheduling; each can be recomputed bit for bit.  device: -1 for the calling thread's current one (it is restored before the call
+ * returns).  Refused, with a message: patterns, nClusters, cluster or consensus NULL, an empty matrix, nCols < 2, cut == 0, minNS == 0,
+ * maxNS < minNS, nCols > COGAPS_PATTERN_MATCH_MAX_COLS (what the clustering workgroup keeps in LDS), a NaN or negative value in
+ * patterns, a NaN in dist or among the r_j ("NA values in correlation of patterns": a constant column), no cluster with minNS columns.
+ * ---------------------------------------------------------------------------------------------- */
+#define COGAPS_PATTERN_MATCH_MAX_COLS 4096
+int cogaps_pattern_match(const float *patterns, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride, int onDevice,
+                         uint32_t cut, uint32_t minNS, uint32_t maxNS, int device,
+                         uint32_t *nClusters, uint32_t *cluster, double *corr, float *consensus, double *dist, uint32_t *firstLabels);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
