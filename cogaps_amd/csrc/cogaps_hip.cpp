@@ -860,447 +860,7 @@ static void build_samplers_dense_device_sparse(cogaps_session *s, const float *d
     build_samplers_sparse_input(s, m);
 }
 
-static void read_gs(cogaps_session *s, HostSampler &h)
-{
-    rt_d2h(s->hGs, h.d.gs, sizeof(GenScalars), s->stream);
-    rt_sync(s->stream);
-}
-
-// the next n outputs of the session's seeder into dst, from the look-ahead buffer as far as it reaches
-static void seed_take(cogaps_session *s, uint64_t *dst, size_t n)
-{
-    const size_t avail = s->seedFifo.size() - s->seedHead, k = std::min(avail, n);
-    if (k) { memcpy(dst, s->seedFifo.data() + s->seedHead, k * 8); s->seedHead += k; }
-    for (size_t i = k; i < n; ++i) dst[i] = s->seeder.next();
-    if (s->seedHead == s->seedFifo.size()) { s->seedFifo.clear(); s->seedHead = 0; }
-}
-// look ahead while the GPU works through a chunk of launches: the seeds of the next update, the other sampler's (about one per atom it
-// holds; Poisson spread + margin)
-static void seed_top_up(cogaps_session *s, const HostSampler &next)
-{
-    const uint32_t na = std::max(next.nAtoms, 10u);
-    const size_t target = (size_t)na + (size_t)(6.0 * sqrt((double)na)) + 64u;
-    size_t avail = s->seedFifo.size() - s->seedHead;
-    if (avail >= target) return;
-    if (s->seedHead) { s->seedFifo.erase(s->seedFifo.begin(), s->seedFifo.begin() + (ptrdiff_t)s->seedHead); s->seedHead = 0; }
-    s->seedFifo.reserve(target);
-    for (; avail < target; ++avail) s->seedFifo.push_back(s->seeder.next());
-}
-
-static void grow_atoms(cogaps_session *s, HostSampler &h, uint32_t need)
-{
-    SamplerDev &d = h.d;
-    if (need <= d.atomCap) return;
-    rt_alloc_scope allocOn(s->stream); rt_owner_scope owner(&s->deviceBytes);
-    uint32_t cap = d.atomCap;
-    while (cap < need) cap = (uint32_t)std::min<uint64_t>((uint64_t)cap * 2, 0x7FFFFFF0ull);
-    auto regrow = [&](auto *&ptr, size_t elt) {
-        void *n = rt_malloc((size_t)cap * elt);
-        rt_d2d(n, ptr, (size_t)d.atomCap * elt, s->stream); rt_sync(s->stream);
-        rt_free(ptr); ptr = (decltype(ptr))n;
-    };
-    regrow(d.atoms, sizeof(AtomRec)); regrow(d.vec, 4); regrow(d.freeHandles, 4);
-    regrow(d.atomStamp, 8); regrow(d.inlineStamp, 8); regrow(d.atomDest, 8);
-    { void *n = rt_malloc(((size_t)cap + 1) * 8); rt_d2d(n, d.gapStamp, ((size_t)d.atomCap + 1) * 8, s->stream); rt_sync(s->stream); rt_free(d.gapStamp); d.gapStamp = (unsigned long long *)n; }
-    d.atomCap = cap;
-    rt_free((void *)d.deathProb); d.deathProb = nullptr;
-    build_death_prob_table(s, d);
-}
-
-// A one-chain session times every 8th generator / evaluation launch (and every sync launch) of its plain launches
-static int timing_slot(cogaps_session *s, HostSampler &h, int kind, uint64_t ordinal)
-{
-    if (!s->timing || (kind != EV_SYNC && (ordinal % 8) != 0)) return -1;
-    return s->ev.take(kind, &h, h.updLaunches);
-}
-// `realBatches` = batches the current update has generated so far: pair number k processed a batch iff k < realBatches
-static void timing_resolve(cogaps_session *s, uint64_t realBatches)
-{
-    s->ev.drain([&](const EvSample &e, float ms) {
-        HostSampler *h = e.owner;
-        const bool real = e.ord < realBatches;
-        if (e.kind == EV_GEN) { if (real) { h->genMs += ms; h->genTimed++; } else { h->genNoopMs += ms; h->genNoopTimed++; } }
-        else if (e.kind == EV_EVAL) { if (real) { h->evalMs += ms; h->evalTimed++; } else { h->evalNoopMs += ms; h->evalNoopTimed++; } }
-        else if (e.kind == EV_SYNC) { s->syncMs += ms; s->syncTimed++; }     // sync (AP transpose / lookup tables): every launch is timed
-        else { if (real) h->evalMs += ms; else h->evalNoopMs += ms; }
-    });
-}
-// The generator reads the sampler's record from device memory (gen_populate.h: a by-value SamplerDev made the compiler open the kernel
-// with seven serial scalar-cache misses).  The copy is refreshed, on the session's stream, whenever the host's record changed.
-static void sync_record(cogaps_session *s, HostSampler &h)
-{
-    if (!h.dRecord) h.dRecord = dalloc<SamplerDev>(1);
-    if (h.recordValid && memcmp(&h.recordHeld, &h.d, sizeof(SamplerDev)) == 0) return;
-    h.recordHeld = h.d;
-    rt_h2d(h.dRecord, &h.recordHeld, sizeof(SamplerDev), s->stream);
-    rt_sync(s->stream);
-    h.recordValid = true;
-}
-// The one-chain split evaluation (data vectors of more than 4096 elements, dense model, product arithmetic) is ONE launch that decides
-// (eval_kernel<EVAL_DECIDE>); the A*P updates it owes are carried out by the further workgroups of the NEXT generator launch
-// (gen_apply_kernel) -- see eval_kernel.h.  The batched multi-chain launches keep the two-launch form (alpha, apply).
-static bool split_one_launch(const HostSampler &h)
-{
-    static const bool twoLaunches = dev_env("COGAPS_SPLIT_TWO_LAUNCHES") != nullptr;      // dev builds: A/B against the two-launch form (alpha kernel, apply kernel)
-    return !twoLaunches && !h.d.seq && !h.d.sparse && h.d.redW > 1024u;
-}
-static uint32_t apply_grid()
-{
-#if defined(COGAPS_EMUL)
-    static const uint32_t g = 5u;        // (test-only emulator: a workgroup is a set of fibers, few of them keep the tests quick; 5 does not divide the items evenly)
-#else
-    static const uint32_t g = dev_env("COGAPS_APPLY_GRID") ? (uint32_t)atoi(dev_env("COGAPS_APPLY_GRID")) : 127u;      // dev builds: A/B of the update workgroups' number
-#endif
-    return g < 1u ? 1u : g;
-}
-// Updates in flight in this process (sessions stepped from several host threads: shards in flight, bench --chains-mode threads).  A chained
-// launch wants every workgroup of its launch resident at once -- one per compute unit: its kernel's LDS -- so two chains' chained launches
-// take turns on the chip and the hand-over inside each waits for the other's workgroups to leave (correct, and slower than two launches
-// per batch each).  The chained form is therefore taken only by an update that runs alone ON ITS GPU: one count per device ordinal (sessions
-// on different GPUs of one process do not switch each other's chained launch off), taken by the one-chain update and by the batched update
-// alike; the count is looked at when an update begins.
-static const int MAX_DEVICES = 64;
-static std::atomic<int> &g_updatesRunning(int device) { static std::atomic<int> n[MAX_DEVICES]; return n[device >= 0 && device < MAX_DEVICES ? device : 0]; }
-struct UpdateInFlight { int dev; explicit UpdateInFlight(int device) : dev(device) { g_updatesRunning(dev).fetch_add(1); } ~UpdateInFlight() { g_updatesRunning(dev).fetch_sub(1); } };
-// The chained launch serves the one-chain fused evaluation (dense model, product arithmetic) whose workgroups are at least as large as
-// the generator's and small enough for the generator's register budget (chain_kernel.h); everything else keeps two launches per batch.
-static bool chain_eligible(const cogaps_session *s, const HostSampler &h);
-// launch geometry of the split evaluation (data vectors of more than 4096 elements): `slices` workgroups of `bs` threads per proposal
-// (512 threads fill the machine a little better than 1024; at most 16 slices fit the partials record)
-static void split_geometry(const HostSampler &h, uint32_t &bs, uint32_t &slices)
-{
-    bs = std::max<uint32_t>(512u, h.d.redW / 16u);
-    slices = std::min<uint32_t>(h.d.redW / bs, ((h.d.Npad >> 2) + bs - 1u) / bs);
-}
-static void launch_chain(cogaps_session *s, HostSampler &h)
-{
-    const int slot = timing_slot(s, h, EV_EVAL, h.evalLaunches);
-    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
-    const uint32_t parity = h.chainParity; h.chainParity ^= 1u;
-    if (h.d.sparse) {
-        // sparse model (sparse_kernels.h, chain_sparse_kernel): the launch has 512 threads per workgroup whatever the model's width
-        // (255 evaluation workgroups + the generator = the chip's 256 compute units; a workgroup evaluates two proposals side by side where the
-        // model's vectors take one round of flag words -- sparse_kernels.h, sp_grp -- so queues of up to 510 fit one pass; the dense launch keeps
-        // 240 workgroups, profiles/r04_ab_chained_launch_not_kept.txt)
-#if defined(COGAPS_EMUL)
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID) + 1u;      // (test-only emulator: few workgroups, so that both groups of an evaluation workgroup get proposals)
-#else
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, s->computeUnits >= 256u ? 255u : CHAIN_EVAL_GRID) + 1u;
-#endif
-        const bool wide = h.d.Wn > cogaps_sparse_width(h.d.N);
-        by_window<true>(h.genWin, [&](auto W) {
-            constexpr int WIN = decltype(W)::value;
-            if (wide) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_sparse_kernel<WIN, true>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-            else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_sparse_kernel<WIN, false>), grid, CHAIN_MAX_THREADS, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);
-        });
-    } else {
-        // the fused evaluation, or the split one (data vectors of more than 4096 elements): then the evaluation workgroups are a multiple of
-        // the slices per proposal (chain_kernel.h)
-        const bool split = h.d.redW > 1024u;
-        uint32_t bs = h.d.redW, slices = 1u;
-        if (split) split_geometry(h, bs, slices);
-        const uint32_t groups = split ? std::max<uint32_t>(1u, std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID / slices)) : std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID);
-        const uint32_t grid = groups * slices + 1u;
-        // (one kernel per window dispatch: the kernels are instantiated, and laid out in the code object, in the order they appear here)
-        if (split) by_window(h.genWin, [&](auto W) {
-            constexpr int WIN = decltype(W)::value;
-            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_kernel<WIN, true>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
-        });
-        else by_window(h.genWin, [&](auto W) {
-            constexpr int WIN = decltype(W)::value;
-            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, (chain_kernel<WIN, false>), grid, bs, h.d.lcgMul, h.d.lcgInc, h.d.gs, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, slices, rec);
-        });
-#if defined(COGAPS_EMUL)
-        if (split) RT_LAUNCH(chain_updates_kernel, 5, bs, s->stream, h.d.queue, h.chainGrans, h.d.chainSlots, h.d.queueCap, parity, rec);      // (test-only emulator: the updates behind the launch)
-#endif
-    }
-    h.evalLaunches++;      // (one launch per batch: counted with the evaluation launches, as its time is)
-}
-static void launch_gen(cogaps_session *s, HostSampler &h)
-{
-    const int slot = timing_slot(s, h, EV_GEN, h.genLaunches);
-    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
-    if (split_one_launch(h)) by_window(h.genWin, [&](auto W) {      // (the one-launch split evaluation's A*P updates: further workgroups of this launch)
-        constexpr int WIN = decltype(W)::value;
-        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, gen_apply_kernel<WIN>, 1u + apply_grid(), WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
-    });
-    else by_window(h.genWin, [&](auto W) {
-        constexpr int WIN = decltype(W)::value;
-        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, gen_kernel<WIN>, 1, WIN + 64, h.d.lcgMul, h.d.lcgInc, h.d.gs, (const unsigned long long *)h.d.eraseList, (const uint32_t *)h.d.queueUnits, h.d.eraseCap, h.d.queueCap, rec);
-    });
-    h.genLaunches++;
-}
-static void launch_eval(cogaps_session *s, HostSampler &h)
-{
-    const int slot = timing_slot(s, h, EV_EVAL, h.evalLaunches);
-    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;      // (kept current by sync_record, as for the generator)
-    if (h.d.seq) {
-        // verification mode: one workgroup per proposal whatever the vector length, sums in the reference's order
-        if (h.d.sparse) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_seq_kernel, std::min<uint32_t>(h.d.queueCap, SEQ_SPARSE_GRID), cogaps_sparse_width(h.d.N), h.d);
-        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_SEQ>, std::min<uint32_t>(h.d.queueCap, 512u), EVAL_SEQ_BS, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
-    } else if (h.d.sparse) {
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, 1024u);
-        const uint32_t W = cogaps_sparse_width(h.d.N);
-        if (h.d.Wn > W) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_kernel_wide, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);      // several rounds of flag words per vector
-        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_sparse_kernel, grid, W, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, rec);
-    } else if (h.d.redW <= 1024u) {
-        // one workgroup of W threads per proposal
-        static const uint32_t fusedGrid = dev_env("COGAPS_FUSED_GRID") ? (uint32_t)atoi(dev_env("COGAPS_FUSED_GRID")) : 512u;      // dev builds: A/B of the launch size
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, fusedGrid);
-        LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_FUSED>, grid, h.d.redW, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, 1u, rec);
-    } else {
-        // long data vectors: `slices` workgroups of `bs` threads per proposal, alpha kernel then apply kernel
-        // (512 threads fill the machine a little better than 1024; at most 16 slices fit the partials record)
-        uint32_t bs, slices; split_geometry(h, bs, slices);
-        const uint32_t perWave = std::max<uint32_t>(1u, (512u * (1024u / bs)) / slices);   // two resident 1024-thread workgroups per compute unit
-        const uint32_t grid = std::min<uint32_t>(h.d.queueCap, perWave) * slices;
-        if (split_one_launch(h)) {
-            // one launch: the slices' totals reach the proposal's last slice workgroup inside it (eval_kernel.h, EVAL_DECIDE); the A*P updates
-            // follow beside the next generator launch (launch_gen)
-            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_DECIDE>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
-        } else {
-            const int slot2 = slot >= 0 ? s->ev.take(EV_EVAL2, &h, h.updLaunches) : -1;
-            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, eval_kernel<EVAL_ALPHA>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
-            LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot2, eval_kernel<EVAL_APPLY>, grid, bs, (const PropRec *)h.d.queue, (const GenScalars *)h.d.gs, h.d.queueCap, slices, rec);
-        }
-    }
-    h.evalLaunches++;
-}
-
-static bool chain_eligible(const cogaps_session *s, const HostSampler &h)
-{
-    // (a device with fewer compute units than the launch has workgroups -- a partitioned GPU -- would run them in turns, the generator
-    // workgroup last: correct, and slower than two launches)
-    if (s->noChain || h.d.seq || h.chainOff) return false;
-    if (g_updatesRunning(s->p.device).load() > 1 && !s->forceChain) return false;      // (another update -- a session's or a batch's -- is in flight on this session's GPU: see g_updatesRunning)
-    if (h.d.sparse)      // sparse model (round 5): a launch of 512-thread workgroups, the evaluation keeps the model's width inside it
-        return CHAIN_MAX_THREADS >= h.genWin + 64u && (s->forceChain || s->computeUnits >= std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID) + 1u);
-    uint32_t block = h.d.redW;
-    if (h.d.redW > 1024u) {      // split evaluation (round 5): workgroups of 512 threads, at most as many slices per proposal as the launch has evaluation workgroups
-        uint32_t slices; split_geometry(h, block, slices);
-        if (!split_one_launch(h) || slices > 16u || s->noChainSplit) return false;
-    }
-    // (the split form's update items wait for deciding workgroups of HIGHER index -- eval_chain_updates --: every workgroup must be resident,
-    // so COGAPS_FORCE_CHAIN does not take it on a device with fewer compute units than the launch has workgroups; the fused form, whose
-    // evaluation workgroups never wait, runs in turns there)
-    const bool forced = s->forceChain && h.d.redW <= 1024u;
-    return block <= (uint32_t)CHAIN_MAX_THREADS && block >= h.genWin + 64u
-           && (forced || s->computeUnits >= std::min<uint32_t>(h.d.queueCap, CHAIN_EVAL_GRID) + 1u);
-}
-// one batch step: the chained launch, or a generator launch and an evaluation launch
-static void launch_pair(cogaps_session *s, HostSampler &h)
-{
-    if (h.chain) launch_chain(s, h); else { launch_gen(s, h); launch_eval(s, h); }
-}
-// the generator window for the coming update (stepsPerBatch = 0: none measured yet) or the next one; the captured launches carry the window
-static void retune_window(cogaps_session *s, HostSampler &h, float stepsPerBatch)
-{
-    const bool wideOk = h.chain && h.d.sparse != 0u;      // (the wide window: the chained sparse launch only; tests take it from the first update on)
-    const uint32_t win = wideOk && s->testWideWindow ? (uint32_t)GEN_WIN_WIDE : gen_window_for(h.genWin, stepsPerBatch, wideOk);
-    if (win != h.genWin) { h.genWin = win; h.graphs.drop(); }
-}
-
-// Launch clock of the chained launches (gaps_state.h): the ring holds {entry of the first workgroup, end of the generator workgroup} of
-// every chained launch, slot = tag of the batch it evaluated.  Read back with the progress word of a chunk (at most 4096 launches, the ring
-// holds 8192): the launches that evaluated batches (clockSeen, upTo] are complete -- the batch generated last is evaluated by the next
-// launch, unless the update is over.
-static void clock_collect(cogaps_session *s, HostSampler &h, uint64_t epoch, bool flushed)
-{
-    const uint64_t upTo = flushed ? epoch : (epoch ? epoch - 1u : 0u);
-    if (!s->timing || !h.d.launchClock) { h.clockSeen = upTo; return; }
-    if (upTo <= h.clockSeen) return;
-    h.clockHost.resize(2u * GAPS_CLOCK_RING);
-    rt_d2h(h.clockHost.data(), h.d.launchClock, sizeof(unsigned long long) * 2u * GAPS_CLOCK_RING, s->stream); rt_sync(s->stream);
-    if (h.clockHist.empty()) h.clockHist.assign(2048, 0);
-    if (h.periodHist.empty()) h.periodHist.assign(2048, 0);
-    const uint64_t from = upTo - h.clockSeen > GAPS_CLOCK_RING ? upTo - GAPS_CLOCK_RING : h.clockSeen;
-    for (uint64_t e = from + 1u; e <= upTo; ++e) {
-        const unsigned long long b = h.clockHost[2u * (uint32_t)(e % GAPS_CLOCK_RING)], en = h.clockHost[2u * (uint32_t)(e % GAPS_CLOCK_RING) + 1u];
-        if (!b || en <= b || en - b > 100000000ull) continue;      // (an entry whose halves belong to different launches: a stale slot)
-        const double us = 0.01 * (double)(en - b);
-        h.clockSumUs += us; h.clockN++;
-        h.clockHist[std::min<size_t>(h.clockHist.size() - 1u, (size_t)(us * 10.0))]++;
-        // the period to the next launch (the batch behind this one is evaluated by the very next launch on the stream; a chunk's last launch is
-        // followed by the host's progress read-back: periods beyond 100 us are such seams and left out)
-        if (e + 1u <= upTo) {
-            const unsigned long long nb = h.clockHost[2u * (uint32_t)((e + 1u) % GAPS_CLOCK_RING)];
-            if (nb > b && nb - b < 10000ull) {
-                const double pu = 0.01 * (double)(nb - b);
-                h.periodSumUs += pu; h.periodN++;
-                h.periodHist[std::min<size_t>(h.periodHist.size() - 1u, (size_t)(pu * 10.0))]++;
-            }
-        }
-    }
-    h.clockSeen = upTo;
-}
-
-// A chained launch's generator gave up waiting for a decision (GAPS_ERR_SPIN; chain_kernel.h, chain_recover_kernel): the stream is idle
-// (the error word was read behind a synchronisation), the evaluation workgroups of the failed launch have all ended.  The batch is
-// completed on the device, the scalars are put back, and the sampler goes on with two launches per batch -- for the rest of the session:
-// what kept a workgroup from being scheduled for two seconds (a foreign kernel holding compute units, a debugger) may well still be there.
-// The split evaluation's chained form (not the default) is not recovered: its deciding workgroups wait as well.
-static bool chain_recover(cogaps_session *s, HostSampler &h, uint32_t nSteps)
-{
-    if (!h.chain || h.d.seq || (!h.d.sparse && h.d.redW > 1024u)) return false;
-    // launch k of the update (k = 0, 1, ...) has parity start ^ (k & 1), evaluates batch k and generates batch k + 1: the launch that gave up
-    // had generated nothing, so it is launch number nBatches and the batch it was carrying out lies in the queue copy of its parity
-    const uint32_t parityFail = (h.chainParityStart + s->hGs->nBatches) & 1u;
-    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
-    RT_LAUNCH(chain_recover_kernel, 1, 256, s->stream, h.d.gs, (const PropRec *)(h.d.queue + (size_t)parityFail * h.d.queueCap), (const unsigned long long *)h.chainGrans, nSteps, rec);
-    read_gs(s, h);
-    if (s->hGs->error) return false;      // (a decision is still missing: the update cannot be completed)
-    h.chain = false; h.chainOff = true; h.chainRecoveries++;
-    retune_window(s, h, 0.f);      // (the wide window exists for the chained sparse launch only)
-    return true;
-}
-
-// Arms sampler h for an update of n proposals: room for the atoms it can add, exactly n seeder outputs in the seed buffer
-// (ProposalQueue.cpp:12-15; a failed attempt rolls the seeder back, Random.cpp:244-248) and its scalars `g` (as read back) reset for the
-// update; the caller uploads them.  Returns the predicted proposals per batch: the previous update of this sampler is the best predictor.
-static float begin_update(cogaps_session *s, HostSampler &h, GenScalars &g, uint32_t n, uint32_t traceCap)
-{
-    rt_owner_scope owner(&s->deviceBytes);      // (a batch steps its sessions from its own scope)
-    grow_atoms(s, h, g.nAtoms + n + 1024u);
-    if (h.seedCap < (size_t)n + 1) { rt_free(h.seeds); h.seedCap = (size_t)n * 5 / 4 + 1024; h.seeds = dalloc<uint64_t>(h.seedCap); }
-    if (h.hSeedCap < (size_t)n + 1) { rt_free_host(h.hSeeds); h.hSeedCap = (size_t)n * 5 / 4 + 1024; h.hSeeds = (uint64_t *)rt_malloc_host(h.hSeedCap * 8); }
-    seed_take(s, h.hSeeds, n);
-    rt_h2d(h.seeds, h.hSeeds, (size_t)n * 8, s->stream);
-    h.d.seeds = h.seeds;
-    g.annealTemp = h.anneal;
-    g.nSteps = n; g.nDone = 0; g.nBatches = 0; g.updateFlushed = 0; g.qlen = 0;
-    g.traceOn = traceCap ? 1u : 0u; g.traceCount = 0; g.traceCap = traceCap; g.traceBatchCount = 0;
-    h.updLaunches = 0;
-    return h.stepsPerBatch > 1.f ? h.stepsPerBatch : (g.avgQueue > 1.f ? g.avgQueue : 1.f);
-}
-// the outcome of an update of n proposals, as the statistics and the sampler's next update read it
-static void end_update(HostSampler &h, const GenScalars &g, uint32_t n)
-{
-    h.nAtoms = g.nAtoms; h.avgQueue = g.avgQueue; h.batches += g.nBatches;
-    if (g.nBatches >= 8u) h.stepsPerBatch = (float)n / (float)g.nBatches;
-}
-// Batch steps to enqueue before the next progress read-back, for C chains stepped together (g, nSteps, avgq: one per chain; done: the
-// chains whose update is over, or null): what the slowest unfinished chain still needs.  A step enqueued past the end of an update is a
-// wasted launch (two), a read-back one short pipeline bubble: the first chunk takes slightly fewer steps than the estimate says, the
-// later ones converge on the tail.
-static uint32_t chunk_size(uint32_t C, const GenScalars *g, const uint32_t *nSteps, const float *avgq, const char *done, bool first)
-{
-    uint32_t chunk = 0;
-    for (uint32_t c = 0; c < C; ++c)
-        if (!done || !done[c]) chunk = std::max(chunk, (uint32_t)((double)(nSteps[c] - g[c].nDone) / avgq[c] * (first ? 0.97 : 1.0)) + (first ? 0u : 2u));
-    return std::min(std::max(chunk, 6u), 4096u);
-}
-
-// AsynchronousGibbsSampler::update (AsynchronousGibbsSampler.h:88-122): batches of generate + evaluate
-// until nSteps proposals have been processed.  The number of batches is data dependent, so (generate,
-// evaluate) pairs are enqueued in chunks and the generator's progress word is read back per chunk;
-// pairs enqueued past the end are no-ops (the generator flushes the last erase cache and reports
-// qlen = 0).
-static int run_update_seq(cogaps_session *s, HostSampler &h, uint32_t nSteps);
-static int run_update(cogaps_session *s, HostSampler &h, uint32_t nSteps, uint32_t traceCap)
-{
-    SamplerDev &d = h.d;
-    if (s->poisoned) return fail("this session was ended by a device error in an earlier update; its chain cannot be continued");
-    if (s->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) {
-        if (traceCap) return fail("proposal traces belong to the asynchronous sampler's queue: a sequential session has none");
-        return run_update_seq(s, h, nSteps);
-    }
-    UpdateInFlight inFlight(s->p.device);
-    read_gs(s, h);
-    if (h.traceCap < traceCap) {
-        rt_free(d.trace); rt_free(d.traceBatchNproc); rt_free(d.traceBatchQlen);
-        d.trace = dalloc<PropRec>(traceCap); d.traceBatchNproc = dalloc<uint32_t>(traceCap); d.traceBatchQlen = dalloc<uint32_t>(traceCap);
-        h.traceCap = traceCap;
-    }
-    float avgq = begin_update(s, h, *s->hGs, nSteps, traceCap);
-    rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream);
-    const ChainSlot emptySlots[2] = {{0u, 0u}, {0u, 0u}};
-    rt_h2d(d.chainSlots, emptySlots, sizeof(emptySlots), s->stream);      // (chained launch: both parities start from an empty queue)
-    rt_sync(s->stream);
-    if (nSteps == 0) return 0;
-    sync_record(s, h);
-    h.chain = chain_eligible(s, h);
-    retune_window(s, h, 0.f);
-    h.chainParityStart = h.chainParity;
-    h.clockSeen = s->hGs->batchEpoch;      // (launch clock: the batches of this update carry the tags behind this one)
-    bool firstChunk = true, topped = false;
-    for (;;) {
-        uint32_t plain = chunk_size(1, s->hGs, &nSteps, &avgq, nullptr, firstChunk);
-        firstChunk = false;
-        if (rt_graphs_supported() && !s->noGraph && !traceCap && plain >= GRAPH_PAIRS) {
-            h.graphs.rekey(h.d);
-            // HIP events cannot ride on replayed launches.  While timing is on, one replay of every chunk -- its position moves
-            // through the chunk from update to update -- is issued as plain launches that carry events, so that the sample covers
-            // the whole population of batches and not only the tail of each chunk (the remainder below).
-            const uint32_t nRep = plain / GRAPH_PAIRS;
-            const uint64_t rot = s->timing ? h.plainRotor++ : 0;                       // (every fourth chunk: the plain launches leave longer gaps than a replay)
-            const uint32_t timedRep = (s->timing && (rot & 3u) == 0u) ? (uint32_t)(((rot >> 2) * 7u) % nRep) : 0xFFFFFFFFu;
-            for (uint32_t r = 0; plain >= GRAPH_PAIRS; plain -= GRAPH_PAIRS, ++r) {
-                if (r == timedRep) { for (uint32_t b = 0; b < GRAPH_PAIRS; ++b) { launch_pair(s, h); h.updLaunches++; } continue; }
-                const bool timing = s->timing; s->timing = false;      // (a capture's launches are neither timed nor counted)
-                const uint64_t g0 = h.genLaunches, e0 = h.evalLaunches;
-                h.graphs.replay(s->stream, h.chain, h.chainParity, [&] { launch_pair(s, h); });
-                s->timing = timing; h.genLaunches = g0 + (h.chain ? 0u : GRAPH_PAIRS); h.evalLaunches = e0 + GRAPH_PAIRS; h.updLaunches += GRAPH_PAIRS;
-            }
-        }
-        for (uint32_t b = 0; b < plain; ++b) { launch_pair(s, h); h.updLaunches++; }
-        if (!topped) { seed_top_up(s, &h == &s->A ? s->P : s->A); topped = true; }
-        read_gs(s, h);
-        timing_resolve(s, s->hGs->nBatches);
-        if (h.chain) clock_collect(s, h, s->hGs->batchEpoch, s->hGs->updateFlushed != 0);
-        if (s->hGs->error == GAPS_ERR_SPIN && chain_recover(s, h, nSteps)) continue;      // (the batch completed, the update goes on with two launches per batch)
-        if (s->hGs->error) { s->poisoned = true; return fail(std::string("device error code ") + std::to_string(s->hGs->error) + " in sampler " + h.name); }
-        if (s->hGs->updateFlushed) break;
-        if (s->hGs->nBatches > 0) avgq = std::max(1.f, (float)s->hGs->nDone / (float)s->hGs->nBatches);
-    }
-    end_update(h, *s->hGs, nSteps);
-    retune_window(s, h, h.stepsPerBatch);
-    return 0;
-}
-
-// ---- the sequential sampler (seq_kernel.h): SingleThreadedGibbsSampler::update ------------------------------------------------------
-// Arms sampler h for update(n): room for the atoms n births can add, progress and temperature in its scalars `g` (as read back; the
-// caller uploads them).  No seeder output is taken: the sampler's one generator lives in g.qrng since the session's creation.
-static void begin_update_seq(cogaps_session *s, HostSampler &h, GenScalars &g, uint32_t n)
-{
-    rt_owner_scope owner(&s->deviceBytes);
-    grow_atoms(s, h, g.nAtoms + n + 1024u);
-    g.annealTemp = h.anneal;
-    g.nSteps = n; g.nDone = 0; g.nBatches = 0; g.updateFlushed = n == 0 ? 1u : 0u; g.qlen = 0;
-    g.traceOn = 0; g.traceCount = 0; g.traceBatchCount = 0;
-    h.updLaunches = 0;
-}
-static uint32_t seq_launches(uint32_t nSteps) { return (nSteps + (uint32_t)SEQ_STEPS_PER_LAUNCH - 1u) / (uint32_t)SEQ_STEPS_PER_LAUNCH; }
-// workgroup size of a sampler's sequential launch: the reduction's width up to 1024 threads; the verification mode's term scratch holds 256
-static uint32_t seq_block(const SamplerDev &d) { return std::min<uint32_t>(d.redW, d.seq ? (uint32_t)EVAL_SEQ_BS : 1024u); }
-// One workgroup runs the whole update, SEQ_STEPS_PER_LAUNCH steps per launch; the number of launches is known beforehand, so they are
-// enqueued at once and the scalars are read back once.
-static int run_update_seq(cogaps_session *s, HostSampler &h, uint32_t nSteps)
-{
-    SamplerDev &d = h.d;
-    read_gs(s, h);
-    begin_update_seq(s, h, *s->hGs, nSteps);
-    rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream);
-    rt_sync(s->stream);
-    if (nSteps == 0) return 0;
-    sync_record(s, h);
-    h.chain = false;
-    const SamplerDev CG_CONSTANT *rec = (const SamplerDev CG_CONSTANT *)h.dRecord;
-    const uint32_t bs = seq_block(d);
-    for (uint32_t k = seq_launches(nSteps); k; --k) {
-        const int slot = timing_slot(s, h, EV_EVAL, 0);
-        if (d.seq) LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, seq_update_kernel<true>, 1, bs, rec);
-        else LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, seq_update_kernel<false>, 1, bs, rec);
-        h.evalLaunches++; h.updLaunches++;
-    }
-    read_gs(s, h);
-    timing_resolve(s, ~0ull);
-    if (s->hGs->error || !s->hGs->updateFlushed) {
-        s->poisoned = true;
-        return fail(std::string("device error code ") + std::to_string(s->hGs->error) + " in sampler " + h.name + " (sequential sampler)");
-    }
-    h.nAtoms = s->hGs->nAtoms;      // (avgQueue stays 0: SingleThreadedGibbsSampler::getAverageQueueLength)
-    return 0;
-}
+#include "sampler_update.h"
 
 static void do_sync(cogaps_session *s, HostSampler &dst, HostSampler &src)
 {
@@ -1316,6 +876,15 @@ static void do_sync(cogaps_session *s, HostSampler &dst, HostSampler &src)
     LAUNCH_MAYBE_TIMED(s->stream, s->ev, slot, transpose_kernel, tilesX * tilesY, 256, (const float *)src.d.AP, dst.d.AP, src.d.M, src.d.N, src.d.Npad, dst.d.Npad, tilesX);
 }
 
+// the M per-vector partial sums a chi-square launch left, added on the host: one float accumulator, ascending j
+static float sum_partials(cogaps_session *s, const float *partial, uint32_t M)
+{
+    std::vector<float> part(M);
+    rt_d2h(part.data(), partial, (size_t)M * 4, s->stream); rt_sync(s->stream);
+    float c = 0.f; for (uint32_t j = 0; j < M; ++j) c += part[j];
+    return c;
+}
+
 static float chisq_of(cogaps_session *s, HostSampler &h)
 {
     if (h.d.seq) {      // the reference's order: one accumulator over the whole matrix, on the device
@@ -1328,10 +897,7 @@ static float chisq_of(cogaps_session *s, HostSampler &h)
     if (h.d.sparse && h.d.K <= 64u) LAUNCH_V(chisq_sparse_tiled_kernel, h.d.redW, (h.d.M + (uint32_t)SP_CHI_ROWS - 1u) / (uint32_t)SP_CHI_ROWS, s->stream, h.d, h.partial);      // SP_CHI_ROWS vectors per workgroup share the other matrix's rows
     else if (h.d.sparse) LAUNCH_V(chisq_sparse_kernel, h.d.redW, h.d.M, s->stream, h.d, h.partial);
     else LAUNCH_V(chisq_rows_kernel_s, h.d.redW, h.d.M, s->stream, h.d, (const float *)h.Sraw, h.partial);
-    std::vector<float> part(h.d.M);
-    rt_d2h(part.data(), h.partial, (size_t)h.d.M * 4, s->stream); rt_sync(s->stream);
-    float c = 0.f;
-    for (uint32_t j = 0; j < h.d.M; ++j) c += part[j];
+    const float c = sum_partials(s, h.partial, h.d.M);
     return h.d.sparse ? c * h.d.beta : c;
 }
 
@@ -1847,321 +1413,7 @@ int cogaps_session_run_iterations(cogaps_session *s, int phase, uint32_t firstIt
     SESSION_END
 }
 
-// ================================================================================================================================
-// Batched multi-chain launches: C independent chains -- the subsets of a GWCoGAPS / scCoGAPS job that share one GPU (nSets > #GPUs),
-// or replicas -- stepped in lock-step by ONE stream.  One chain alone alternates between a one-workgroup generator launch and an
-// evaluation launch of a few hundred workgroups, both latency-bound; with C chains the generator grid is C workgroups and the
-// evaluation grid C times as many, so a step of the batch costs about what a step of one chain costs and the evaluation kernels
-// finally move enough rows per launch to approach the HBM roofline.  Every chain is the same chain it would be on its own, bit for
-// bit (tests/test_gpu_parity.py::test_batched_chains_equal_single_sessions): the kernels are the one-chain kernels' bodies, fed from
-// a device array of SamplerDev records instead of a by-value argument.
-// ================================================================================================================================
-struct cogaps_batch {
-    std::vector<cogaps_session *> ss;
-    rt_stream_t stream = rt_stream_t();
-    SamplerDev *dev[2] = {nullptr, nullptr};            // [0] the A samplers' records, [1] the P samplers'
-    std::vector<SamplerDev> host[2];                    // what the device arrays hold
-    GraphCache graphs[2];
-    // round 6: a side whose evaluation is the fused one steps as ONE chained launch for all chains (chain_kernel_multi) where every workgroup
-    // of it is resident at once
-    bool chain[2] = {false, false}; uint32_t chainParity[2] = {0, 0}; uint32_t chainWg[2] = {0, 0};
-    GenScalars *hGs = nullptr;                          // pinned, [C]
-    bool sparse = false; char fixed = 'N';
-    uint64_t launches[2] = {0, 0};
-    // HIP-event samples of the plain-launch remainder of each chunk
-    bool timing = false; EventPool ev;
-    double genMs[2] = {0, 0}, evalMs[2] = {0, 0}; uint64_t genTimed[2] = {0, 0}, evalTimed[2] = {0, 0};
-    uint64_t ord = 0;
-    uint32_t genWin[2] = {GEN_WIN, GEN_WIN};           // per side, from the chain with the longest batches
-};
-
-static HostSampler &bpick(cogaps_batch *b, uint32_t c, int w) { return w == 0 ? b->ss[c]->A : b->ss[c]->P; }
-
-// launch geometry shared by the chains of a batch (checked at creation: equal reduction widths and slice counts)
-struct MultiGeom { uint32_t block, slices, wgPerChain; bool fused; };
-static MultiGeom multi_geom(cogaps_batch *b, int w)
-{
-    const SamplerDev &d = bpick(b, 0, w).d;
-    const uint32_t C = (uint32_t)b->ss.size();
-    uint32_t minCap = 0xFFFFFFFFu; for (uint32_t c = 0; c < C; ++c) minCap = std::min(minCap, bpick(b, c, w).d.queueCap);
-    MultiGeom g;
-    if (b->sparse) { g.block = cogaps_sparse_width(d.N); g.slices = 1; g.fused = true; g.wgPerChain = std::min<uint32_t>(minCap, std::max<uint32_t>(64u, 1024u / C)); return g; }
-    if (d.redW <= 1024u) { g.block = d.redW; g.slices = 1; g.fused = true; g.wgPerChain = std::min<uint32_t>(minCap, std::max<uint32_t>(64u, 2048u / C)); return g; }
-    g.fused = false;
-    g.block = std::max<uint32_t>(512u, d.redW / 16u);
-    g.slices = std::min<uint32_t>(d.redW / g.block, ((d.Npad >> 2) + g.block - 1u) / g.block);
-    const uint32_t perWave = std::max<uint32_t>(1u, (512u * (1024u / g.block)) / g.slices);      // (launch_eval: two resident 1024-thread workgroups per compute unit)
-    g.wgPerChain = std::min<uint32_t>(minCap, std::max<uint32_t>(4u, (2u * perWave) / C + 1u)) * g.slices;
-    return g;
-}
-// The chained form for a batch (chain_kernel.h, chain_kernel_multi): the dense model's fused evaluation (workgroups as large as the generator's),
-// every workgroup of the launch resident at once -- compute units / chains per chain -- and no other update in flight on the GPU.  Taken
-// for up to FOUR chains (64 workgroups each on the MI355X): measured +9 % at two chains, +2 % at four, -7 % at eight, -20 % at sixteen
-// (profiles/r06_ab_chained_batch.txt) -- a chain's evaluation workgroups are alone on their compute units (the generator's LDS), where the
-// batched evaluation launch packs three per unit.  COGAPS_NO_CHAIN switches it off (A/B, equality tests).
-static uint32_t multi_chain_wg(cogaps_batch *b, int w, const MultiGeom &g)
-{
-    const cogaps_session *s0 = b->ss[0];
-    const uint32_t C = (uint32_t)b->ss.size();
-    if (s0->noChain || b->sparse || !g.fused || g.block > (uint32_t)CHAIN_MAX_THREADS || g.block < b->genWin[w] + 64u) return 0u;
-    if (g_updatesRunning(s0->p.device).load() > 1) return 0u;
-    for (cogaps_session *s : b->ss) if ((w == 0 ? s->A : s->P).d.seq) return 0u;
-    const uint32_t perChain = std::min<uint32_t>(s0->computeUnits / C, CHAIN_EVAL_GRID + 1u);
-    return perChain >= (CHAIN_EVAL_GRID >= 16u ? 64u : 3u) ? perChain : 0u;      // (the test-only emulator's launches have seven evaluation workgroups)
-}
-static void multi_launch_pair(cogaps_batch *b, int w, const MultiGeom &g, int slotGen, int slotEval, int slotEval2)
-{
-    const uint32_t C = (uint32_t)b->ss.size();
-    const SamplerDev CG_CONSTANT *arr = (const SamplerDev CG_CONSTANT *)b->dev[w];
-    if (b->chain[w]) {
-        const uint32_t parity = b->chainParity[w]; b->chainParity[w] ^= 1u;
-        by_window(b->genWin[w], [&](auto W) {
-            constexpr int WIN = decltype(W)::value;
-            LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, chain_kernel_multi<WIN>, C * b->chainWg[w], g.block, arr, parity, b->chainWg[w]);
-        });
-        b->launches[w]++;
-        return;
-    }
-    by_window(b->genWin[w], [&](auto W) {
-        constexpr int WIN = decltype(W)::value;
-        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotGen, gen_kernel_multi<WIN>, C, WIN + 64, arr);
-    });
-    if (b->sparse) LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_sparse_kernel_multi, C * g.wgPerChain, g.block, arr, g.wgPerChain);
-    else if (g.fused) LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_kernel_multi<EVAL_FUSED>, C * g.wgPerChain, g.block, arr, 1u, g.wgPerChain);
-    else {
-        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval, eval_kernel_multi<EVAL_ALPHA>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
-        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slotEval2, eval_kernel_multi<EVAL_APPLY>, C * g.wgPerChain, g.block, arr, g.slices, g.wgPerChain);
-    }
-    b->launches[w]++;
-}
-
-// AsynchronousGibbsSampler::update of sampler `w` (0 = A, 1 = P) of every chain, nSteps[c] proposals each
-static int run_update_multi_seq(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps);
-static int run_update_multi(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps)
-{
-    const uint32_t C = (uint32_t)b->ss.size();
-    if (b->ss[0]->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) return run_update_multi_seq(b, w, nSteps);
-    UpdateInFlight inFlight(b->ss[0]->p.device);      // (a one-chain session stepped beside the batch on the same GPU keeps two launches per batch meanwhile)
-    rt_alloc_scope allocOn(b->stream);
-    for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
-    rt_sync(b->stream);
-    std::vector<float> avgq(C); std::vector<char> done(C, 0);
-    for (uint32_t c = 0; c < C; ++c) {
-        HostSampler &h = bpick(b, c, w); GenScalars &g = b->hGs[c];
-        avgq[c] = begin_update(b->ss[c], h, g, nSteps[c], 0);
-        // update(0) -- a Poisson draw of 0 has probability e^-10 while a chain holds at most 10 atoms -- is a no-op in the reference
-        // (AsynchronousGibbsSampler.h:94: the loop body never runs): the chain is done before the first launch and the lock-stepped
-        // batch never waits for it (its generator workgroup sees nDone >= nSteps and leaves at once)
-        if (nSteps[c] == 0) { g.updateFlushed = 1; done[c] = 1; }
-        rt_h2d(h.d.gs, &g, sizeof(GenScalars), b->stream);
-    }
-    if (std::all_of(done.begin(), done.end(), [](char d) { return d != 0; })) { rt_sync(b->stream); return 0; }
-    // the records the kernels read: re-uploaded when a pointer in one of them changed (atom tables regrown, seed buffer moved);
-    // the captured graph stays valid -- its kernels' arguments are the array's address and the launch geometry
-    bool changed = false;
-    for (uint32_t c = 0; c < C; ++c) if (memcmp(&b->host[w][c], &bpick(b, c, w).d, sizeof(SamplerDev)) != 0) { b->host[w][c] = bpick(b, c, w).d; changed = true; }
-    if (changed) rt_h2d(b->dev[w], b->host[w].data(), (size_t)C * sizeof(SamplerDev), b->stream);
-    rt_sync(b->stream);
-    const MultiGeom geo = multi_geom(b, w);
-    b->chainWg[w] = multi_chain_wg(b, w, geo);
-    b->chain[w] = b->chainWg[w] != 0u;
-    for (uint32_t c = 0; c < C; ++c) bpick(b, c, w).chain = b->chain[w];      // (cogaps_session_chained reports what runs)
-    if (b->chain[w]) {      // both parities of every chain start from an empty queue
-        const ChainSlot emptySlots[2] = {{0u, 0u}, {0u, 0u}};
-        for (uint32_t c = 0; c < C; ++c) rt_h2d(bpick(b, c, w).d.chainSlots, emptySlots, sizeof(emptySlots), b->stream);
-        rt_sync(b->stream);
-    }
-    bool first = true, topped = false;
-    for (;;) {
-        uint32_t plain = chunk_size(C, b->hGs, nSteps.data(), avgq.data(), done.data(), first);
-        first = false;
-        if (rt_graphs_supported() && !b->ss[0]->noGraph)
-            for (; plain >= GRAPH_PAIRS; plain -= GRAPH_PAIRS) {
-                const uint64_t l0 = b->launches[w];      // (the captured launches are not counted)
-                b->graphs[w].replay(b->stream, b->chain[w], b->chainParity[w], [&] { multi_launch_pair(b, w, geo, -1, -1, -1); });
-                b->launches[w] = l0 + GRAPH_PAIRS; b->ord += GRAPH_PAIRS;
-            }
-        for (uint32_t k = 0; k < plain; ++k) {
-            int sg = -1, se = -1, se2 = -1;
-            if (b->timing && (b->ord % 4u) == 0u && b->ev.room(3)) {
-                if (b->chain[w]) se = b->ev.take(EV_EVAL);      // (one launch per step: timed as the evaluation launch, as the one-chain form's is)
-                else { sg = b->ev.take(EV_GEN); se = b->ev.take(EV_EVAL); if (!geo.fused) se2 = b->ev.take(EV_EVAL2); }
-            }
-            multi_launch_pair(b, w, geo, sg, se, se2);
-            b->ord++;
-        }
-        if (!topped) { for (uint32_t c = 0; c < C; ++c) seed_top_up(b->ss[c], bpick(b, c, 1 - w)); topped = true; }
-        for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
-        rt_sync(b->stream);
-        b->ev.drain([&](const EvSample &e, float ms) {          // (sampled launches near the end of a chunk: most chains still have work there)
-            if (e.kind == EV_GEN) { b->genMs[w] += ms; b->genTimed[w]++; } else { b->evalMs[w] += ms; if (e.kind == EV_EVAL) b->evalTimed[w]++; }
-        });
-        bool all = true;
-        for (uint32_t c = 0; c < C; ++c) {
-            const GenScalars &g = b->hGs[c];
-            if (g.error) { b->ss[c]->poisoned = true; return fail(std::string("device error code ") + std::to_string(g.error) + " in sampler " + (w ? 'P' : 'A') + " of chain " + std::to_string(c)); }
-            if (g.updateFlushed) done[c] = 1; else all = false;
-            if (g.nBatches > 0) avgq[c] = std::max(1.f, (float)g.nDone / (float)g.nBatches);
-        }
-        if (all) break;
-    }
-    float spb = 0.f;
-    for (uint32_t c = 0; c < C; ++c) { end_update(bpick(b, c, w), b->hGs[c], nSteps[c]); spb = std::max(spb, bpick(b, c, w).stepsPerBatch); }
-    const uint32_t win = gen_window_for(b->genWin[w], spb);
-    if (win != b->genWin[w]) { b->genWin[w] = win; b->graphs[w].drop(); }
-    return 0;
-}
-
-// The sequential sampler's update of sampler `w` of every chain: ONE launch of a workgroup per chain per SEQ_STEPS_PER_LAUNCH steps of the
-// longest update; a chain whose update is over leaves at once and nobody waits for anybody.
-static int run_update_multi_seq(cogaps_batch *b, int w, const std::vector<uint32_t> &nSteps)
-{
-    const uint32_t C = (uint32_t)b->ss.size();
-    rt_alloc_scope allocOn(b->stream);
-    for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
-    rt_sync(b->stream);
-    uint32_t longest = 0;
-    for (uint32_t c = 0; c < C; ++c) {
-        HostSampler &h = bpick(b, c, w);
-        begin_update_seq(b->ss[c], h, b->hGs[c], nSteps[c]);
-        rt_h2d(h.d.gs, &b->hGs[c], sizeof(GenScalars), b->stream);
-        longest = std::max(longest, nSteps[c]);
-    }
-    bool changed = false;
-    for (uint32_t c = 0; c < C; ++c) if (memcmp(&b->host[w][c], &bpick(b, c, w).d, sizeof(SamplerDev)) != 0) { b->host[w][c] = bpick(b, c, w).d; changed = true; }
-    if (changed) rt_h2d(b->dev[w], b->host[w].data(), (size_t)C * sizeof(SamplerDev), b->stream);
-    rt_sync(b->stream);
-    if (longest == 0) return 0;
-    const SamplerDev CG_CONSTANT *arr = (const SamplerDev CG_CONSTANT *)b->dev[w];
-    const uint32_t bs = seq_block(bpick(b, 0, w).d);      // (equal reduction widths: checked at the batch's creation)
-    for (uint32_t k = seq_launches(longest); k; --k) {
-        const int slot = (b->timing && b->ev.room(1)) ? b->ev.take(EV_EVAL) : -1;
-        LAUNCH_MAYBE_TIMED(b->stream, b->ev, slot, seq_update_kernel_multi, C, bs, arr);
-        b->launches[w]++; b->ord++;
-    }
-    for (uint32_t c = 0; c < C; ++c) rt_d2h(&b->hGs[c], bpick(b, c, w).d.gs, sizeof(GenScalars), b->stream);
-    rt_sync(b->stream);
-    b->ev.drain([&](const EvSample &, float ms) { b->evalMs[w] += ms; b->evalTimed[w]++; });
-    for (uint32_t c = 0; c < C; ++c) {
-        const GenScalars &g = b->hGs[c];
-        if (g.error || !g.updateFlushed) { b->ss[c]->poisoned = true; return fail(std::string("device error code ") + std::to_string(g.error) + " in sampler " + (w ? 'P' : 'A') + " of chain " + std::to_string(c) + " (sequential sampler)"); }
-        bpick(b, c, w).nAtoms = g.nAtoms; bpick(b, c, w).chain = false;
-    }
-    return 0;
-}
-
-cogaps_batch *cogaps_batch_create(cogaps_session **sessions, uint32_t n)
-{
-    cogaps_batch *b = nullptr;
-    try {
-        if (!sessions || n == 0) { fail("no sessions"); return nullptr; }
-        const cogaps_session *s0 = sessions[0];
-        for (uint32_t c = 0; c < n; ++c) {
-            const cogaps_session *s = sessions[c];
-            if (!s) { fail("null session"); return nullptr; }
-            if (!s->ownsStream) { fail("a session can be in one batch only"); return nullptr; }
-            if (s->A.d.seq || s0->A.d.seq) { fail("the verification mode runs one chain at a time"); return nullptr; }
-            if (s->p.sampler != s0->p.sampler) { fail("the sessions of a batch must share the sampler: sequential and asynchronous chains cannot be mixed"); return nullptr; }
-            // one launch geometry for all chains: the same model, reduction widths and slice counts (subsets of one job have them)
-            if (s->p.useSparseOptimization != s0->p.useSparseOptimization || s->p.whichMatrixFixed != s0->p.whichMatrixFixed || s->p.device != s0->p.device
-                || s->A.d.redW != s0->A.d.redW || s->P.d.redW != s0->P.d.redW || ((s->A.d.Npad >> 2) + 511u) / 512u != ((s0->A.d.Npad >> 2) + 511u) / 512u
-                || ((s->P.d.Npad >> 2) + 511u) / 512u != ((s0->P.d.Npad >> 2) + 511u) / 512u
-                || (s->p.useSparseOptimization && (cogaps_sparse_width(s->A.d.N) != cogaps_sparse_width(s0->A.d.N) || cogaps_sparse_width(s->P.d.N) != cogaps_sparse_width(s0->P.d.N))))      // (the dense kernels never see the sparse model's workgroup width: subsets of 4095 and 4096 rows share a batch)
-            { fail("the sessions of a batch must share the model, the fixed matrix, the device and the evaluation launch shape (equal reduction widths)"); return nullptr; }
-        }
-        rt_set_device(s0->p.device);
-        b = new cogaps_batch();
-        b->ss.assign(sessions, sessions + n);
-        b->sparse = s0->p.useSparseOptimization != 0; b->fixed = s0->p.whichMatrixFixed;
-        b->stream = rt_stream_create();
-        rt_alloc_scope allocOn(b->stream);
-        // everything that can fail is done BEFORE a session is touched: a failed creation leaves every session as it was
-        b->hGs = (GenScalars *)rt_malloc_host(sizeof(GenScalars) * n);
-        for (int w = 0; w < 2; ++w) { b->dev[w] = dalloc<SamplerDev>(n); b->host[w].resize(n); memset(b->host[w].data(), 0, sizeof(SamplerDev) * n); }
-        for (cogaps_session *s : b->ss) rt_sync(s->stream);
-        for (cogaps_session *s : b->ss) {      // from here on the sessions run on the batch's stream, one after the other (nothing below throws)
-            s->A.graphs.drop(); s->P.graphs.drop();
-            rt_stream_destroy(s->stream); s->stream = b->stream; s->ownsStream = false; s->A.chain = false; s->P.chain = false;      // (the batched launches keep two launches per step: cogaps_session_chained reports what runs)
-        }
-        return b;
-    } catch (const std::exception &e) {
-        fail_exc(e);
-        if (b) {
-            for (int w = 0; w < 2; ++w) rt_free(b->dev[w]);
-            rt_free_host(b->hGs);
-            if (b->stream) rt_stream_destroy(b->stream);
-            delete b;
-        }
-        return nullptr;
-    }
-}
-
-void cogaps_batch_destroy(cogaps_batch *b)
-{
-    if (!b) return;
-    try { rt_sync(b->stream); } catch (...) { }
-    for (cogaps_session *s : b->ss) { try { s->stream = rt_stream_create(); s->ownsStream = true; } catch (...) { } }      // the sessions outlive the batch
-    for (int w = 0; w < 2; ++w) { b->graphs[w].drop(); rt_free(b->dev[w]); }
-    rt_free_host(b->hGs);
-    rt_stream_destroy(b->stream);
-    delete b;
-}
-
-// runOnePhase for every chain of the batch: iterations [firstIter, firstIter + n) of `phase`; updates[c] += proposals of chain c
-int cogaps_batch_run_iterations(cogaps_batch *b, int phase, uint32_t firstIter, uint32_t n, uint64_t *updates)
-{
-    try {
-        rt_set_device(b->ss[0]->p.device);
-        rt_alloc_scope allocOn(b->stream);
-        const uint32_t C = (uint32_t)b->ss.size();
-        for (uint32_t c = 0; c < C; ++c)
-            if (b->ss[c]->poisoned) return fail("chain " + std::to_string(c) + " of this batch was ended by a device error in an earlier update; the batch cannot be continued");
-        const double t0 = now_s();
-        for (cogaps_session *s : b->ss)
-            if (s->p.printMessages && firstIter == 0 && n > 0) { printf(phase == 1 ? "-- Equilibration Phase --\n" : "-- Sampling Phase --\n"); fflush(stdout); }
-        std::vector<uint32_t> nA(C), nP(C);
-        const char f = b->fixed;
-        for (uint32_t it = firstIter; it < firstIter + n; ++it) {
-            for (uint32_t c = 0; c < C; ++c)
-                if (iteration_head(b->ss[c], phase, it, &nA[c], &nP[c])) return 1;
-            // updateSampler (GapsRunner.cpp:201-222), every chain at once
-            if (f != 'A') { if (run_update_multi(b, 0, nA)) return 1; if (f != 'P') for (cogaps_session *s : b->ss) do_sync(s, s->P, s->A); }
-            if (f != 'P') { if (run_update_multi(b, 1, nP)) return 1; if (f != 'A') for (cogaps_session *s : b->ss) do_sync(s, s->A, s->P); }
-            for (uint32_t c = 0; c < C; ++c) {
-                iterate_tail(b->ss[c], nA[c], nP[c], phase == 2);
-                if (updates) updates[c] += (uint64_t)nA[c] + nP[c];
-                if (iteration_tail(b->ss[c], phase, it)) return 1;
-            }
-            for (cogaps_session *s : b->ss) set_position(s, phase, it + 1u);
-        }
-        rt_sync(b->stream);
-        const double dt = now_s() - t0;
-        for (cogaps_session *s : b->ss) s->samplerSeconds += dt;
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-int cogaps_batch_set_timing(cogaps_batch *b, int on)
-{
-    try {
-        if (on) b->ev.create(1536);
-        if (on && !b->timing) for (int w = 0; w < 2; ++w) { b->genMs[w] = b->evalMs[w] = 0; b->genTimed[w] = b->evalTimed[w] = 0; }
-        b->timing = on != 0;
-        return 0;
-    } catch (const std::exception &e) { return fail_exc(e); }
-}
-
-// mean HIP-event time of the sampled batched launches since cogaps_batch_set_timing(1), per sampler side (0 = A, 1 = P); the
-// algorithmic bytes and proposal counts are the sessions' own (cogaps_session_perf_sampler)
-int cogaps_batch_perf(cogaps_batch *b, int side, double *genUs, double *evalUs, uint64_t *sampled, uint64_t *launches)
-{
-    if (side < 0 || side > 1) return fail("side must be 0 (A) or 1 (P)");
-    if (genUs) *genUs = b->genTimed[side] ? 1e3 * b->genMs[side] / (double)b->genTimed[side] : 0.0;
-    if (evalUs) *evalUs = b->evalTimed[side] ? 1e3 * b->evalMs[side] / (double)b->evalTimed[side] : 0.0;
-    if (sampled) *sampled = b->evalTimed[side];
-    if (launches) *launches = b->launches[side];
-    return 0;
-}
+#include "chain_batch.h"
 
 int cogaps_session_natoms(cogaps_session *s, char which, uint32_t *n) { *n = pick(s, which).nAtoms; return 0; }
 int cogaps_session_chisq(cogaps_session *s, char which, float *c) { SESSION_TRY *c = chisq_of(s, pick(s, which)); SESSION_END }
@@ -2197,15 +1449,22 @@ int cogaps_session_get_ap(cogaps_session *s, char which, float *out)
     for (uint32_t r = 0; r < h.d.M; ++r) memcpy(out + (size_t)r * h.d.N, m.data() + (size_t)r * h.d.Npad, (size_t)h.d.N * 4);
     SESSION_END
 }
+// a sampler's atomic domain as the device holds it: its scalars (in s->hGs), the handles of its atoms in vector order, every atom record;
+// returns the number of atoms
+static uint32_t fetch_domain(cogaps_session *s, HostSampler &h, std::vector<uint32_t> &vec, std::vector<AtomRec> &atoms)
+{
+    read_gs(s, h);
+    vec.resize(s->hGs->nAtoms); atoms.resize(h.d.atomCap);
+    if (!vec.empty()) rt_d2h(vec.data(), h.d.vec, vec.size() * 4, s->stream);
+    rt_d2h(atoms.data(), h.d.atoms, atoms.size() * sizeof(AtomRec), s->stream); rt_sync(s->stream);
+    return s->hGs->nAtoms;
+}
 int cogaps_session_get_atoms(cogaps_session *s, char which, uint64_t *pos, float *mass, uint32_t *left, uint32_t *right)
 {
     SESSION_TRY
     HostSampler &h = pick(s, which);
-    read_gs(s, h);
-    const uint32_t n = s->hGs->nAtoms;
-    std::vector<uint32_t> vec(n); std::vector<AtomRec> atoms(h.d.atomCap);
-    if (n) rt_d2h(vec.data(), h.d.vec, (size_t)n * 4, s->stream);
-    rt_d2h(atoms.data(), h.d.atoms, (size_t)h.d.atomCap * sizeof(AtomRec), s->stream); rt_sync(s->stream);
+    std::vector<uint32_t> vec; std::vector<AtomRec> atoms;
+    const uint32_t n = fetch_domain(s, h, vec, atoms);
     for (uint32_t i = 0; i < n; ++i) {
         const AtomRec &a = atoms[vec[i]];
         if (pos) pos[i] = a.pos;
@@ -2222,11 +1481,8 @@ int cogaps_session_debug_check_domain(cogaps_session *s, char which, uint32_t *v
 {
     SESSION_TRY
     HostSampler &h = pick(s, which);
-    read_gs(s, h);
-    const uint32_t n = s->hGs->nAtoms;
-    std::vector<uint32_t> vec(n); std::vector<AtomRec> atoms(h.d.atomCap);
-    if (n) rt_d2h(vec.data(), h.d.vec, (size_t)n * 4, s->stream);
-    rt_d2h(atoms.data(), h.d.atoms, (size_t)h.d.atomCap * sizeof(AtomRec), s->stream); rt_sync(s->stream);
+    std::vector<uint32_t> vec; std::vector<AtomRec> atoms;
+    const uint32_t n = fetch_domain(s, h, vec, atoms);
     uint32_t bad = 0, fronts = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t hd = vec[i];
@@ -2278,10 +1534,7 @@ int cogaps_session_finish(cogaps_session *s, cogaps_result *out)
         } else {
         if (s->P.d.sparse) LAUNCH_V(mean_chisq_rows_packed_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);      // (no dense D / Sraw: sparse_build.h)
         else LAUNCH_V(mean_chisq_rows_kernel, s->P.d.redW, s->P.d.M, s->stream, s->P.d, (const float *)s->P.Sraw, (const float *)s->Asum, (const float *)s->Psum, s->A.d.Mpad, n2, s->P.partial);
-        std::vector<float> part(s->P.d.M);
-        rt_d2h(part.data(), s->P.partial, (size_t)s->P.d.M * 4, s->stream); rt_sync(s->stream);
-        float c = 0.f; for (uint32_t j = 0; j < s->P.d.M; ++j) c += part[j];
-        out->meanChiSq = c;
+        out->meanChiSq = sum_partials(s, s->P.partial, s->P.d.M);
         }
     }
     if (s->p.takePumpSamples) {                                                       // GapsRunner.cpp:487-492, GapsStatistics.cpp:113-131

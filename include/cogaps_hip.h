@@ -428,9 +428,12 @@ int cogaps_session_perf_sampler(cogaps_session *s, char which, cogaps_perf *out)
  * decisions the evaluation workgroups have left by then (chain_recover_kernel), and the sampler goes on -- same chain, same bits -- with
  * two launches per batch for the rest of the session.  cogaps_session_chain_recoveries counts such events (0 in every run so far).  Only if
  * a decision is still missing then (the split evaluation's chained form, COGAPS_CHAIN_SPLIT: its deciding workgroups wait as well) does the
- * update end with an error (GAPS_ERR_SPIN) and the session refuse further steps.  This recovery serves one-chain sessions only: in a batch
- * (cogaps_batch_*, whose chained launch is chain_kernel_multi) a wait that runs out ends the update with the error GAPS_ERR_SPIN, and the
- * batch refuses further steps. */
+ * update end with an error (GAPS_ERR_SPIN) and the session refuse further steps.  All of this -- the completed batch, "same chain, same
+ * bits" -- holds for ONE-CHAIN sessions only.  A batch (cogaps_batch_*, whose chained launch is chain_kernel_multi) has no recovery: there
+ * the same event ENDS the chain it happens in.  cogaps_batch_run_iterations fails with "device error code 4 in sampler X of chain C"
+ * (4 = GAPS_ERR_SPIN), that chain's session is poisoned -- it refuses further updates, on its own too, and holds no result -- and the batch
+ * refuses every later call.  The other chains' sessions are not poisoned and take calls of their own once the batch is destroyed, but
+ * the failing call left them wherever their own update stood: they are no longer the chains an undisturbed run gives. */
 int cogaps_session_chained(cogaps_session *s, char which, int *chained);
 int cogaps_session_chain_recoveries(cogaps_session *s, char which, uint32_t *n);
 /* Attempts per round of the sampler's generator launches as of its last update (the library's instantiations: 128, 256, and 448 for the sparse

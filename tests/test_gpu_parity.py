@@ -1275,3 +1275,35 @@ def test_configs4_eight_sparse_shards_on_one_gpu(hip_lib):
         assert one["totalUpdates"] == r["firstPass"][i]["totalUpdates"] and one["meanChiSq"] == r["firstPass"][i]["meanChiSq"]
         two = _capi.run(shard, nPatterns=k2, workerID=i + 1, whichMatrixFixed="A", fixedPatterns=cons, **kw)
         assert np.array_equal(two["Pmean"], r["Pmean"][i * per:(i + 1) * per]), "second pass, shard %d" % i
+
+
+def test_host_launch_counters_on_the_gpu(hip_lib):
+    """The update drivers' host launch counters (csrc/sampler_update.h, csrc/chain_batch.h) on the hardware, timing off, for the dense,
+    sparse and three-chain cases of tests/test_update_drivers.py: launches per sampler -- replayed from a captured graph or not, a launch
+    counts once -- and the batches they processed.  They follow from the chains and the chunk arithmetic alone and repeat run to run
+    (profiles/update_drivers_refactor_checks.txt); on the MI355X the dense A sampler (300-element vectors: workgroups smaller than the
+    generator's) keeps two launches per batch, one chain or three."""
+    from cogaps_amd import _capi
+
+    def counters(S):
+        return {w: (int(S.perf(w)["genLaunches"]), int(S.perf(w)["evalLaunches"]), int(S.perf(w)["batches"]), S.chained(w)) for w in "AP"}
+    S = _capi.Session(pu.synthetic(1200, 300, seed=7), lib=hip_lib, nPatterns=3, seed=123, nIterations=40)
+    S.run_iterations(1, 0, 20)
+    dense = counters(S)
+    S.close()
+    S = _capi.Session(pu.synthetic_counts(600, 200, zeros=0.9, seed=5), lib=hip_lib, nPatterns=4, seed=11, nIterations=40, sparseOptimization=True)
+    S.run_iterations(1, 0, 30)
+    sparse = counters(S)
+    S.close()
+    ss = [_capi.Session(pu.synthetic(1200, 300, seed=7 + c), lib=hip_lib, nPatterns=3, nIterations=40, seed=100 + c) for c in range(3)]
+    B = _capi.Batch(ss)
+    B.run_iterations(1, 0, 20)
+    launches = [int(B.perf(w)["launches"]) for w in "AP"]
+    batches = [[int(S.perf(w)["batches"]) for w in "AP"] for S in ss]
+    chained = [[S.chained(w) for w in "AP"] for S in ss]
+    B.close()
+    for S in ss: S.close()
+    print(dense, sparse, launches, batches, chained)
+    assert dense == {"A": (222, 222, 163, False), "P": (0, 248, 146, True)}
+    assert sparse == {"A": (0, 348, 259, True), "P": (0, 318, 212, True)}
+    assert launches == [278, 259] and batches == [[181, 141], [182, 146], [172, 140]] and chained == [[False, True]] * 3
