@@ -106,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_gene_set_membership", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -233,6 +233,7 @@ def bind(L):
     u64p, dp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
     L.cogaps_gene_set_stat.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     L.cogaps_debug_permutation_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u32p]
+    L.cogaps_gene_set_membership.argtypes = [dp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, dp, dp, C.c_int, dp, u32p, dp]
     L.cogaps_pattern_markers.argtypes = [dp, C.c_uint64, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint64, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_int, C.c_int, u32p, dp, u32p, u32p]
     L.cogaps_pattern_gsea.argtypes = [fp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_int, dp, u32p, u32p, u64p, u32p]
     L.cogaps_residuals.argtypes = [fp, C.c_uint32, C.c_size_t, C.c_size_t, fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(CogapsResidualDataC),
@@ -1033,6 +1034,34 @@ def gene_set_stat(z, members, sizes, numPerm, seed=0, device=-1, lib=None):
                               int(numPerm), int(seed) & 0xFFFFFFFF, int(device), cnt.ctypes.data_as(u32p), act.ctypes.data_as(dp)):
         raise _error(L)
     return cnt, act
+
+
+def gene_set_membership(z, members, wMember, wNull=None, device=-1, stat=True, counts=True, allStat=False, lib=None):
+    """cogaps_gene_set_membership: the statistic of every member of every set under the set's pattern weights, and the rows outside the
+    set that exceed it.  z, members: as for gene_set_stat; wMember, wNull: float64 [nSets][K] (wNull None: = wMember).
+    -> {"memberStat": float64 and "greaterCount": uint32, the sets one after the other (members' order); "offsets": where each set
+    begins in them; "allStat": float64 [nSets][n]} -- each None unless asked for (stat, counts, allStat)"""
+    L = lib if lib is not None else load()
+    z = _strided(z, np.float64, "z must be a matrix")
+    off, mem = _pack_sets(members)
+    nSets, (n, K) = off.size - 1, z.shape
+    w = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (wMember, wNull)]
+    if any(x is not None and x.shape != (nSets, K) for x in w):
+        raise ValueError("one weight per set and column")
+    nMem = max(int(off[-1]), 1)
+    out = {"memberStat": np.zeros(nMem) if stat else None, "greaterCount": np.zeros(nMem, dtype=np.uint32) if counts else None,
+           "allStat": np.zeros((nSets, n)) if allStat else None}
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    ptr = lambda x, t: None if x is None else x.ctypes.data_as(t)
+    if L.cogaps_gene_set_membership(z.ctypes.data_as(dp), n, K, z.strides[0] // 8, z.strides[1] // 8, nSets,
+                                    off.ctypes.data_as(C.POINTER(C.c_uint64)), mem.ctypes.data_as(u32p), ptr(w[0], dp), ptr(w[1], dp), int(device),
+                                    ptr(out["memberStat"], dp), ptr(out["greaterCount"], u32p), ptr(out["allStat"], dp)):
+        raise _error(L)
+    for k in ("memberStat", "greaterCount"):
+        if out[k] is not None:
+            out[k] = out[k][:int(off[-1])]
+    out["offsets"] = off.astype(np.int64)
+    return out
 
 
 def permutation_draw(nRows, size, seed, set_index, perm, device=-1, lib=None):

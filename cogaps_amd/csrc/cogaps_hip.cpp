@@ -21,6 +21,7 @@
 #include "state_digest.h"
 #include "state_file.h"
 #include "geneset_kernel.h"
+#include "genemember_kernel.h"
 #include "markers_kernel.h"
 #include "gsea_kernel.h"
 #include "residual_kernel.h"

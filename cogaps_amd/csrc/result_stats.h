@@ -1,11 +1,11 @@
-// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.12): host code only, a chapter of cogaps_hip.cpp, which includes
+// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.13): host code only, a chapter of cogaps_hip.cpp, which includes
 // it once, after everything it takes from there:
 //   fail, fail_exc                    the one home of the library's error message
 //   SpbTemps, SpbMatrix, SpbSide, SpbMap, sparse_args_refusal, spb_compressed, spb_triplets, spb_build_sides
 //                                     the sparse builder's helpers (cogaps_residuals reads the gene side of its packed form)
 //   cogaps_device_matrix              the handle cogaps_residuals takes as data
-// and after the kernel headers geneset_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h.  The entries here:
-// cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match.
+// and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h.
+// The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match.
 #pragma once
 
 // One call's device and stream, its device memory, and the stream announced for its allocations' fills.  However the call ends they go
@@ -156,6 +156,55 @@ int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, 
         uint32_t *d = g.get<uint32_t>(size);
         RT_LAUNCH(gs_draw_kernel, 1, 64, g.st, nRows, size, seed, set, perm, d);
         rt_d2h(out, d, (size_t)size * 4, g.st); rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The genes of a set that behave like the set (genemember_kernel.h)
+// ------------------------------------------------------------------------------------------------
+int cogaps_gene_set_membership(const double *z, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                               uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members,
+                               const double *wMember, const double *wNull, int device,
+                               double *memberStat, uint32_t *greaterCount, double *allStat)
+{
+    try {
+        const std::string me = "cogaps_gene_set_membership: ";
+        if (!z || !memberOffsets || !members || !wMember) return fail(me + "null argument");
+        if (!memberStat && !greaterCount && !allStat) return fail(me + "null argument: one of memberStat, greaterCount and allStat must be given");
+        if (nRows == 0u || nCols == 0u) return fail(me + "the Z matrix is empty");
+        if (nSets == 0u) return fail(me + "nSets must be at least 1");
+        const std::string refusal = set_list_refusal(me, "Z", nRows, nSets, memberOffsets, members, nullptr, 0u);
+        if (!refusal.empty()) return fail(refusal);
+        // Z transposed: one column = one run of rows, read lane = row
+        const size_t ldn = pad16(nRows);
+        std::vector<double> zt(ldn * nCols, 0.0);
+        stage_matrix(zt, ldn, true, z, nRows, nCols, rowStride, colStride);
+        std::vector<unsigned long long> off(nSets + 1u);
+        const size_t nMem = (size_t)(memberOffsets[nSets] - memberOffsets[0]), nW = (size_t)nSets * nCols, nAll = (size_t)nSets * nRows;
+
+        GsScratch g(device);
+        GmArgs a;
+        memset(&a, 0, sizeof(a));
+        a.zt = g.up(zt); a.ldn = ldn; a.nRows = nRows; a.K = nCols; a.nSets = nSets;
+        unsigned long long *dOff = g.get<unsigned long long>(off.size());
+        uint32_t *dMem = g.get<uint32_t>(nMem);
+        upload_sets(memberOffsets, members, 0, nSets, off, dOff, dMem, g.st);
+        a.memberOffsets = dOff; a.members = dMem;
+        a.wMember = a.wNull = g.mem.stage(wMember, nW, false, g.st);
+        if (wNull) a.wNull = g.mem.stage(wNull, nW, false, g.st);
+        a.memberStat = g.get<double>(nMem);                                  // (zero-filled, as the counts are)
+        if (greaterCount) a.greaterCount = g.get<uint32_t>(nMem);
+        if (allStat) a.allStat = g.get<double>(nAll);                        // the one thing of size nSets x nRows, and only on request
+        if (memberStat || greaterCount) RT_LAUNCH(gm_member_kernel, gs_grid(((unsigned long long)nSets + GM_WAVES - 1ull) / GM_WAVES), GM_THREADS, g.st, a);
+        if (greaterCount || allStat)
+            RT_LAUNCH(gm_count_kernel, gs_grid((unsigned long long)nSets * (((unsigned long long)nRows + GM_THREADS - 1ull) / GM_THREADS)), GM_THREADS, g.st, a);
+        double *const statOut = memberStat ? memberStat + memberOffsets[0] : nullptr;
+        uint32_t *const countOut = greaterCount ? greaterCount + memberOffsets[0] : nullptr;
+        if (statOut && nMem) rt_d2h(statOut, a.memberStat, nMem * 8, g.st);
+        if (countOut && nMem) rt_d2h(countOut, a.greaterCount, nMem * 4, g.st);
+        if (allStat) rt_d2h(allStat, a.allStat, nAll * 8, g.st);
+        rt_sync(g.st);
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

@@ -12,8 +12,14 @@ beside it -- and binaryA: how well the result fits its data, on the GPU for dens
 0.1) in double; genes select rows in the order given where R's NULL means all), and getPatternGeneSet -- which gene sets go with which
 pattern: the pre-ranked enrichment analysis of every set in every pattern with its permutation null on the GPU (cogaps_pattern_gsea;
 DESIGN.md 4.11: ties rank in row order, the permutations are the keyed draw, the p-value is the simple one, a set that is not tested
-is a NaN row where fgsea drops it), or the hypergeometric test of every set against patternMarkers' lists.  calcGeneGSStat,
-computeGeneGSProb, plotPatternGeneSet and the plots themselves are out of scope."""
+is a NaN row where fgsea drops it), or the hypergeometric test of every set against patternMarkers' lists, and calcGeneGSStat and
+computeGeneGSProb -- which genes of a set behave like the set: every gene's pattern-weighted statistic and the share of the genes
+outside the set that exceed each member's, for any number of sets, on the GPU (cogaps_gene_set_membership; DESIGN.md 4.13: the weights
+come from calcCoGAPSStat's counts, floored at 1 / numPerm where R's become infinite; one permutation test serves a set's members and
+its null; fp64 in fixed orders), and toCSV / fromCSV, the eleven files of the reference's export.  plotPatternGeneSet and the plots
+themselves are out of scope."""
+import os
+import re
 import warnings
 
 import numpy as np
@@ -155,6 +161,95 @@ class CogapsResult:
         up[:, [m.size == 0 for m in members]] = np.nan
         down = 1.0 - up
         return {"twoSidedPValue": np.maximum(np.minimum(down, up), 1.0 / numPerm), "GSUpreg": up, "GSDownreg": down, "GSActEst": 1.0 - 2.0 * up, "sets": labels}
+
+    def _gene_set_weights(self, sets, numPerm, Pw, seed, lib):
+        """what calcGeneGSStat and computeGeneGSProb start from -> (Z, set names, member rows per set, GSUpreg
+        [nSets][K] floored at 1 / numPerm, g = -log(GSUpreg), w = g * Pw -- g itself without a weighting)"""
+        from . import _capi
+        if isinstance(numPerm, bool) or not isinstance(numPerm, (int, np.integer)) or numPerm < 1 or numPerm > 0xFFFFFFFF:
+            raise ValueError("numPerm must be a whole number of at least 1")
+        z = self.calcZ("featureLoadings")
+        labels, members, sizes = _resolve_sets(sets, self.geneNames, z.shape[0], "featureLoadings")
+        if Pw is not None:
+            Pw = np.asarray(Pw, dtype=np.float64).reshape(-1)
+            if np.isnan(Pw).all():
+                Pw = None                                                        # R: all(is.na(Pw)) means no weighting
+            elif Pw.size != z.shape[1]:
+                raise ValueError("Invalid weighting")
+        if seed is None:
+            seed = self.metadata.get("seed") or 0
+        count, _ = _capi.gene_set_stat(z, members, sizes, int(numPerm), seed=int(seed), lib=lib)
+        up = np.maximum(count, 1) / float(numPerm)
+        g = -np.log(up)
+        return z, labels, members, up, g, g if Pw is None else g * Pw[None, :]
+
+    def _row_labels(self, rows):
+        return [self.geneNames[i] for i in rows] if self.geneNames is not None else [int(i) + 1 for i in rows]
+
+    def calcGeneGSStat(self, sets=None, numPerm=500, Pw=None, nullGenes=False, seed=None, GStoGenes=None, lib=None):
+        """R/methods-CogapsResult.R:535-569 on the GPU, for any number of sets: the statistic T of the genes of every set (nullGenes:
+        of the genes outside it) -- the gene's Z over the patterns, weighted by how active the set is in each pattern (-log GSUpreg of
+        calcCoGAPSStat with numPerm permutations, GSUpreg floored at 1 / numPerm, times Pw if given: one weight per pattern), over the
+        weights' sum and over the gene's plain sum of Z; 0 where either sum is below 1e-6.  sets, seed: as for calcCoGAPSStat;
+        GStoGenes: the reference's name of `sets`.  -> {"sets": the set names, "genes": per set the rows' names (1-based indices if the
+        result carries none) in ascending row order, "stat": per set their float64 T}.  DESIGN.md 4.13 has every deviation from R."""
+        from . import _capi
+        z, labels, members, _, _, w = self._gene_set_weights(GStoGenes if GStoGenes is not None else sets, numPerm, Pw, seed, lib)
+        out = _capi.gene_set_membership(z, members, w, stat=not nullGenes, counts=False, allStat=bool(nullGenes), lib=lib)
+        if nullGenes:
+            rows = [np.setdiff1d(np.arange(z.shape[0], dtype=np.int64), m) for m in members]
+            stat = [out["allStat"][t, r] for t, r in enumerate(rows)]
+        else:
+            rows = members
+            stat = [out["memberStat"][out["offsets"][t]:out["offsets"][t + 1]].copy() for t in range(len(members))]
+        return {"sets": labels, "genes": [self._row_labels(r) for r in rows], "stat": stat}
+
+    def computeGeneGSProb(self, sets=None, numPerm=500, Pw=None, PwNull=False, seed=None, GStoGenes=None, lib=None):
+        """R/methods-CogapsResult.R:571-594 on the GPU, for any number of sets: for every gene of a set the share of the genes outside
+        the set whose statistic (calcGeneGSStat) is strictly greater than the gene's -- small for a gene that behaves like its set.
+        The members' statistic is weighted by Pw; the null's as well if PwNull, else not (R's second call drops Pw).
+        -> {"sets": the set names, "genes", "prob", "stat", "greaterCount": per set one entry per member in ascending row order (names
+        or 1-based indices; float64; the members' T; int64), "nullSize": int64 [nSets], the rows outside each set, "GSUpreg": float64
+        [nSets][K], the floored shares the weights were made from}.  prob is NaN for a member whose statistic is NaN, for a set whose
+        weights sum to less than 1e-6 (the members' or the null's) and for a set that is every row.  A set none of whose members is
+        a row gives empty arrays.  DESIGN.md 4.13 has every deviation from R."""
+        from . import _capi
+        z, labels, members, up, g, w = self._gene_set_weights(GStoGenes if GStoGenes is not None else sets, numPerm, Pw, seed, lib)
+        wNull = None if PwNull or w is g else g
+        out = _capi.gene_set_membership(z, members, w, wNull=wNull, lib=lib)
+        inactive = np.zeros(len(members), dtype=bool)
+        for v in (w,) if wNull is None else (w, wNull):
+            W = np.zeros(len(members))
+            for k in range(v.shape[1]):                                          # ascending k from +0, as the kernel adds
+                W = W + v[:, k]
+            inactive |= W < 1e-6
+        nullSize = np.array([z.shape[0] - m.size for m in members], dtype=np.int64)
+        stat, cnt, prob = [], [], []
+        for t in range(len(members)):
+            lo, hi = out["offsets"][t], out["offsets"][t + 1]
+            stat.append(out["memberStat"][lo:hi].copy()); cnt.append(out["greaterCount"][lo:hi].astype(np.int64))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                p = cnt[t] / np.float64(nullSize[t])
+            p[np.isnan(stat[t])] = np.nan
+            if inactive[t] or nullSize[t] == 0:
+                p[:] = np.nan
+            prob.append(p)
+        return {"sets": labels, "genes": [self._row_labels(m) for m in members], "prob": prob, "stat": stat, "greaterCount": cnt,
+                "nullSize": nullSize, "GSUpreg": up}
+
+    def toCSV(self, save_location):
+        """R/methods-CogapsResult.R:624-642: the result as eleven csv files in the directory save_location, under R's names -- the four
+        matrices (a header of pattern names, a row per gene or sample), geneNames, sampleNames, meanChiSq, chisqHistory, version,
+        atomsA, atomsP (a header "x", a value per line).  Numbers are written with the digits that read back to the same value; NA
+        stands for a NaN and for what the result does not carry."""
+        diag = self.metadata["diagnostics"]
+        for name in ("featureLoadings", "sampleFactors", "loadingStdDev", "factorStdDev"):
+            m = np.asarray(getattr(self, name))
+            _csv_write(save_location, name, [",".join('"Pattern_%d"' % (k + 1) for k in range(m.shape[1]))] + [",".join(_csv_value(v) for v in row) for row in m])
+        for name, v in (("geneNames", self.geneNames), ("sampleNames", self.sampleNames), ("meanChiSq", self.metadata.get("meanChiSq")),
+                        ("chisqHistory", diag.get("chisq")), ("version", self.metadata.get("version")), ("atomsA", diag.get("atomsA")), ("atomsP", diag.get("atomsP"))):
+            v = [None] if v is None else [v] if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__") else list(v)
+            _csv_write(save_location, name, ['"x"'] + [_csv_value(x) for x in v])
 
     def patternMarkers(self, threshold="all", lp=None, axis=1, lib=None):
         """R/methods-CogapsResult.R:397-494 on the GPU: the rows of featureLoadings (axis=1: genes) or sampleFactors (axis=2: samples),
@@ -373,6 +468,83 @@ class CogapsResult:
     def binaryA(self, threshold):
         """R/methods-CogapsResult.R:246-263 without the heatmap: 1 where calcZ() of featureLoadings exceeds threshold, 0 elsewhere"""
         return (self.calcZ() > threshold).astype(np.int8)
+
+
+def _csv_value(v):
+    if v is None:
+        return "NA"
+    if isinstance(v, (str, bytes)):
+        return '"%s"' % (v.decode() if isinstance(v, bytes) else v).replace('"', '""')
+    if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+        return str(int(v))
+    v = float(v)                                                                 # (from float32: exact)
+    return "NA" if v != v else "Inf" if v == float("inf") else "-Inf" if v == float("-inf") else repr(v)
+
+
+def _csv_write(save_location, name, lines):
+    with open(os.path.join(save_location, name + ".csv"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+_CSV_FIELD = re.compile(r'"((?:[^"]|"")*)"|([^,]*)')
+
+
+def _csv_read(save_location, name):
+    """-> the fields of every line after the header: a str for a quoted field, None for NA, else an int or a float"""
+    with open(os.path.join(save_location, name + ".csv")) as f:
+        lines = f.read().splitlines()[1:]
+    rows = []
+    for line in lines:
+        fields, pos = [], 0
+        while True:
+            m = _CSV_FIELD.match(line, pos)
+            if m.group(1) is not None:
+                fields.append(m.group(1).replace('""', '"'))
+            else:
+                x = m.group(2)
+                fields.append(None if x == "NA" else int(x) if x.lstrip("+-").isdigit() else float(x.replace("Inf", "inf")))
+            pos = m.end() + 1                                                    # (past the comma)
+            if pos > len(line):
+                break
+        rows.append(fields)
+    return rows
+
+
+def toCSV(result, save_location):
+    return result.toCSV(save_location)
+
+
+def fromCSV(save_location):
+    """R/methods-CogapsResult.R:644-682: the result toCSV wrote.  The four matrices come back as float32, the library's type of them
+    (toCSV's digits are exact for it), the chi-square history as float64, the atom counts as int64."""
+    def matrix(name):
+        rows = _csv_read(save_location, name)
+        return np.array([[np.nan if v is None else v for v in r] for r in rows], dtype=np.float64).astype(np.float32).reshape(len(rows), -1)
+
+    def column(name, dtype=None):
+        v = [r[0] for r in _csv_read(save_location, name)]
+        if v == [None]:
+            return None
+        return v if dtype is None else np.array([np.nan if x is None else x for x in v], dtype=dtype)
+    raw = {"Amean": matrix("featureLoadings"), "Asd": matrix("loadingStdDev"), "Pmean": matrix("sampleFactors"), "Psd": matrix("factorStdDev")}
+    mean = column("meanChiSq", np.float64)
+    raw["meanChiSq"] = None if mean is None else float(mean[0])
+    for key, name, dtype in (("chisq", "chisqHistory", np.float64), ("atomsA", "atomsA", np.int64), ("atomsP", "atomsP", np.int64)):
+        v = column(name, dtype)
+        if v is not None:
+            raw[key] = v
+    res = CogapsResult(raw, geneNames=column("geneNames"), sampleNames=column("sampleNames"))
+    version = column("version")
+    res.metadata["version"] = None if version is None else version[0]
+    return res
+
+
+def calcGeneGSStat(result, sets=None, numPerm=500, Pw=None, nullGenes=False, **kw):
+    return result.calcGeneGSStat(sets, numPerm=numPerm, Pw=Pw, nullGenes=nullGenes, **kw)
+
+
+def computeGeneGSProb(result, sets=None, numPerm=500, Pw=None, PwNull=False, **kw):
+    return result.computeGeneGSProb(sets, numPerm=numPerm, Pw=Pw, PwNull=PwNull, **kw)
 
 
 def reconstructGene(result, genes=None, **kw):

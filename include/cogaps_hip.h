@@ -507,6 +507,31 @@ int cogaps_gene_set_stat(const double *z, uint32_t nRows, uint32_t nCols, size_t
 int cogaps_debug_permutation_draw(uint32_t nRows, uint32_t size, uint32_t seed, uint32_t set, uint32_t perm, int device, uint32_t *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Result statistics: which genes of a set behave like the set -- the arithmetic of the reference's calcGeneGSStat and
+ * computeGeneGSProb (R/methods-CogapsResult.R:535-594).
+ *
+ * z: the Z-score matrix, addressed through its strides as cogaps_gene_set_stat addresses it (R's column-major matrix passes as it is);
+ * it is uploaded (and repacked) per call.  Set t has the member rows members[memberOffsets[t] .. memberOffsets[t + 1]), 0-based and
+ * ascending, and the pattern weights wMember[t][k] and wNull[t][k], k < nCols, row-major doubles (wNull NULL: wNull = wMember).  The
+ * weights are the caller's: the front end makes them from cogaps_gene_set_stat's counts with the host's logarithm.  Under the weights
+ * w of a set, the statistic of row i is, every sum in fp64 over ascending k from +0, the product rounded before it is added,
+ *   W = sum w[k],  R = sum z[i][k],  S = sum z[i][k] * w[k],  T = (S / W) / R,  but T = 0 where W < 1e-6 or R < 1e-6
+ * (a negative sum is below 1e-6, a NaN sum never is).  Outputs, each of which may be NULL but not all three:
+ *   memberStat[x]   = T under wMember of row members[x]                                  (laid out like members)
+ *   greaterCount[x] = the number of rows i outside set t with T under wNull of row i > memberStat[x], the comparison strict and
+ *                     false for a NaN on either side                                      (laid out like members)
+ *   allStat[t][i]   = T under wNull of every row, members included                        ([nSets][nRows])
+ * Nothing of size nSets x nRows is allocated, on the host or on the device, unless allStat is given.  No output depends on the device,
+ * on the grid, on scheduling or on how many sets a call holds.  device: -1 for the calling thread's current one (it is restored
+ * before the call returns).  Refused, with a message: z, memberOffsets, members or wMember NULL, all three outputs NULL, nSets == 0,
+ * an empty matrix, a member that is no row or not above its predecessor, memberOffsets that decrease.
+ * ---------------------------------------------------------------------------------------------- */
+int cogaps_gene_set_membership(const double *z, uint32_t nRows, uint32_t nCols, size_t rowStride, size_t colStride,
+                               uint32_t nSets, const uint64_t *memberOffsets, const uint32_t *members,
+                               const double *wMember, const double *wNull, int device,
+                               double *memberStat, uint32_t *greaterCount, double *allStat);
+
+/* ------------------------------------------------------------------------------------------------
  * Result statistics: the pattern markers of the reference's patternMarkers (R/methods-CogapsResult.R:397-494).
  *
  * a: the matrix whose rows are ranked (featureLoadings for the reference's axis = 1, sampleFactors for axis = 2), nRows x nCols doubles
