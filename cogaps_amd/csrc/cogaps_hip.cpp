@@ -325,7 +325,7 @@ struct cogaps_session {
     // where the run stands (cogaps_session_position): the phase and its next iteration, advanced by cogaps_session_run_iterations and
     // cogaps_batch_run_iterations; phase 3 = both phases complete
     int posPhase = 1; uint32_t posNext = 0;
-    // state-file fingerprint (the state-file section below): a hash of fixedPatterns, taken at creation (the caller's array is not kept), and
+    // state-file fingerprint (session_state.h): a hash of fixedPatterns, taken at creation (the caller's array is not kept), and
     // the data digest, computed on the device at the first save or load
     uint64_t fixedHash = 0, dataDigest = 0; bool digestValid = false;
 };
@@ -334,532 +334,8 @@ static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
 
 template <class T> static T *dalloc(size_t n) { return (T *)rt_malloc(n * sizeof(T)); }
 
-// SamplerDev::deathProb for the atom arrays' current capacity (the sampler's creation, grow_atoms)
-static void build_death_prob_table(cogaps_session *s, SamplerDev &d)
-{
-    const uint32_t n = d.atomCap + GAPS_DEATH_PROB_PAD;
-    float *tab = dalloc<float>(n);
-    RT_LAUNCH(death_prob_table_kernel, (n + 255u) / 256u, 256, s->stream, tab, n, d.domainLenD, d.alphaD, d.numBins);
-    rt_sync(s->stream);
-    d.deathProb = tab;
-}
-
-static void free_sampler(HostSampler &h)
-{
-    SamplerDev &d = h.d;
-    rt_free(d.seqScratch); rt_free((void *)d.deathProb); rt_free(d.launchClock);
-    rt_free((void *)d.D); rt_free((void *)d.S2); rt_free(d.AP); rt_free(d.mat); rt_free(d.colPos);
-    rt_free(d.atoms); rt_free(d.vec); rt_free(d.freeHandles); rt_free(d.binHead);
-    rt_free(d.bits0); rt_free(d.bits1); rt_free(d.bits2); rt_free(d.eraseList); rt_free(d.queue); rt_free(d.queueUnits); rt_free(d.chainSlots); rt_free(h.chainGrans); rt_free(d.partials); rt_free(d.grans); rt_free(d.dec);
-    rt_free(d.rowStamp); rt_free(d.atomStamp); rt_free(d.gapStamp); rt_free(d.inlineStamp); rt_free(d.atomDest);
-    rt_free(d.gs); rt_free(d.trace); rt_free(d.traceBatchNproc); rt_free(d.traceBatchQlen);
-    rt_free(h.Sraw); rt_free(h.seeds); rt_free_host(h.hSeeds); rt_free(h.partial); rt_free(h.dRecord);
-    rt_free((void *)d.dflags); rt_free((void *)d.dprefix); rt_free((void *)d.dptr); rt_free((void *)d.dvals); rt_free(d.rows); rt_free(d.mflags); rt_free(d.Z1); rt_free(d.Z2);
-}
-
-static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha);
-// dimensions of a sampler over nS data vectors of nG elements
-static void sampler_dims(cogaps_session *s, HostSampler &h, char name, uint32_t nG, uint32_t nS)
-{
-    const cogaps_params &p = s->p;
-    SamplerDev &d = h.d; memset(&d, 0, sizeof(d)); h.name = name;
-    d.N = nG; d.M = nS; d.K = p.nPatterns;
-    d.seq = p.reductionMode == COGAPS_REDUCE_SEQ ? 1u : 0u; d.mathMode = (uint32_t)p.mathMode;
-    d.Npad = (d.N + 3u) & ~3u; d.Mpad = (d.M + 3u) & ~3u;
-    d.redW = cogaps_reduction_width(d.N);
-    if (p.useSparseOptimization) {
-        if (d.K > SP_KMAX) throw std::runtime_error("useSparseOptimization supports at most 512 patterns");
-        d.Wn = d.N / 64u + 1u;
-    }
-}
-// the DenseNormalModel constructor's constants (DenseNormalModel.h:66-88) from the data's ordered sum and its count of entries > 0
-static void sampler_model(HostSampler &h, float alpha, float maxGibbsMass, float sum, unsigned nnz)
-{
-    SamplerDev &d = h.d;
-    const float meanD = sum / (float)nnz;
-    h.dataSparsity = 1.f - (float)(uint32_t)nnz / (float)(d.M * d.N);       // gaps::sparsity, MatrixMath.cpp:6-21 (unsigned count, float product of the dimensions)
-    d.alpha = alpha;
-    d.lambda = alpha * sqrtf((float)(uint64_t)d.K / meanD);
-    d.maxGibbsMass = maxGibbsMass / d.lambda;
-    d.unitBytes = 4u * d.N;
-}
-// the sparse model beside its packed data (dflags, dprefix, dptr, dvals: sparse_build.h, whatever form the input had -- the only data a
-// sparse-model session holds: d.D, d.S2 and h.Sraw stay null): the HybridMatrix copies and the lookup tables
-static void sampler_sparse_model(HostSampler &h)
-{
-    SamplerDev &d = h.d;
-    d.sparse = 1; d.beta = 100.f; d.unitBytes = 1u;
-    d.Mw = d.M / 64u + 1u; d.Kpad = (d.K + 3u) & ~3u; d.spW = cogaps_sparse_width(d.N);
-    d.rows = dalloc<float>((size_t)d.M * d.Kpad);
-    d.mflags = dalloc<unsigned long long>((size_t)d.K * d.Mw);
-    d.Z1 = dalloc<float>(d.K); d.Z2 = dalloc<float>((size_t)d.K * d.K);
-    if (d.seq) {
-        if (d.Wn > (uint32_t)SP_SEQ_WORDS) throw std::runtime_error("reductionMode SEQ with the sparse model supports data vectors of up to 262080 elements");
-        d.seqScratch = dalloc<float>((size_t)SEQ_SPARSE_GRID * 3u * d.Npad);
-    }
-}
-
-// The dense model's sampler: Matrix(mat, genesInCols, subsetGenes, indices) (data_structures/Matrix.cpp:30-69) laid out as
-// [vector j][element i] + the DenseNormalModel constructor (DenseNormalModel.h:66-88)
-static void build_sampler(cogaps_session *s, HostSampler &h, char name, const float *data, uint32_t nrow, uint32_t ncol, const float *unc,
-                          bool genesInCols, bool subsetGenes, float alpha, float maxGibbsMass)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetData = p.subsetData && !s->subset.empty();
-    const uint32_t *indices = s->subset.data(); const uint32_t nIdx = (uint32_t)s->subset.size();
-    const uint32_t nG = (subsetData && subsetGenes) ? nIdx : (genesInCols ? ncol : nrow);
-    const uint32_t nS = (subsetData && !subsetGenes) ? nIdx : (genesInCols ? nrow : ncol);
-    SamplerDev &d = h.d;
-    sampler_dims(s, h, name, nG, nS);
-    const size_t tot = (size_t)d.M * d.Npad;
-    // With the default uncertainty the evaluation kernel recomputes S*S = max(0.1 D, 0.1)^2 from the D value it loads anyway
-    // (bit-identical: the same three fp32 operations as the fill below): no S2 array, one row less per proposal from HBM.
-    // (COGAPS_READ_S: diagnostics, keeps the array and the loads.)
-    const bool defaultS = unc == nullptr && !dev_env("COGAPS_READ_S");
-    float *dD = dalloc<float>(tot), *dS2 = defaultS ? nullptr : dalloc<float>(tot); h.Sraw = dalloc<float>(tot);
-    // The vectors are staged through the host in blocks of at most 16 M elements (pad: D = 0, S = S2 = 1) -- never three dense
-    // host copies of the matrix (BASELINE configs[4]'s shard is 2.5 GB per copy).  The sums run over the vectors in order, as
-    // gaps::nonZeroMean does (MatrixMath.cpp:39-55).
-    const uint32_t rowsPerBlock = (uint32_t)std::max<size_t>(1, std::min<size_t>(d.M, ((size_t)1 << 24) / std::max<uint32_t>(1u, d.Npad)));
-    std::vector<float> D((size_t)rowsPerBlock * d.Npad), S2(dS2 ? D.size() : 0), SR(D.size());
-    float sum = 0.f; unsigned nnz = 0;
-    for (uint32_t j0 = 0; j0 < nS; j0 += rowsPerBlock) {
-        const uint32_t j1 = std::min(nS, j0 + rowsPerBlock);
-        std::fill(D.begin(), D.end(), 0.f); std::fill(SR.begin(), SR.end(), 1.f); if (dS2) std::fill(S2.begin(), S2.end(), 1.f);
-        for (uint32_t j = j0; j < j1; ++j) {
-            for (uint32_t i = 0; i < nG; ++i) {
-                const uint32_t dataRow = (subsetData && (subsetGenes != genesInCols)) ? indices[genesInCols ? j : i] - 1 : (genesInCols ? j : i);
-                const uint32_t dataCol = (subsetData && (subsetGenes == genesInCols)) ? indices[genesInCols ? i : j] - 1 : (genesInCols ? i : j);
-                const float v = data[(size_t)dataRow * ncol + dataCol];
-                const size_t o = (size_t)(j - j0) * d.Npad + i;
-                D[o] = v;
-                const float sd = unc ? unc[(size_t)dataRow * ncol + dataCol] : gm_max(v * 0.1f, 0.1f);   // gaps::pmax, MatrixMath.cpp:74-84
-                SR[o] = sd; if (dS2) S2[o] = sd * sd;
-                sum += v; if (v > 0.f) ++nnz;                                    // gaps::nonZeroMean, MatrixMath.cpp:39-55
-            }
-        }
-        const size_t off = (size_t)j0 * d.Npad, cnt = (size_t)(j1 - j0) * d.Npad;
-        rt_h2d(dD + off, D.data(), cnt * 4, s->stream); if (dS2) rt_h2d(dS2 + off, S2.data(), cnt * 4, s->stream); rt_h2d(h.Sraw + off, SR.data(), cnt * 4, s->stream);
-        rt_sync(s->stream);                                                     // the staging buffers are reused by the next block
-    }
-    sampler_model(h, alpha, maxGibbsMass, sum, nnz);
-    d.D = dD; d.S2 = dS2; d.defaultS = defaultS ? 1u : 0u;
-    d.AP = dalloc<float>(tot);
-    sampler_domain(s, h, alpha);
-}
-
-// the sampler's own state behind its data: the matrix, the atomic domain, the proposal queue (the seed of the queue's generator is
-// the session seeder's next output: A's sampler first, then P's)
-static void sampler_domain(cogaps_session *s, HostSampler &h, float alpha)
-{
-    SamplerDev &d = h.d;
-    d.mat = dalloc<float>((size_t)d.K * d.Mpad);
-    d.colPos = dalloc<uint32_t>(d.K);
-    d.luts.erf = s->dErf; d.luts.erfinv = s->dErfinv; d.luts.qgamma = s->dQgamma;
-    // atomic domain
-    const uint64_t nBins = (uint64_t)d.M * d.K;
-    d.atomCap = (uint32_t)std::min<uint64_t>(nBins + 65536ull, 0x7FFFFFF0ull);
-    if (const char *e = getenv("COGAPS_INITIAL_ATOM_CAP")) d.atomCap = (uint32_t)std::max(64l, atol(e));      // tests: exercises grow_atoms
-    d.atoms = dalloc<AtomRec>(d.atomCap); d.vec = dalloc<uint32_t>(d.atomCap); d.freeHandles = dalloc<uint32_t>(d.atomCap);
-    d.binHead = dalloc<uint32_t>(nBins); rt_memset(d.binHead, 0xFF, nBins * 4, s->stream);
-    d.nWords0 = (uint32_t)((nBins + 63) / 64); d.nWords1 = (d.nWords0 + 63) / 64; d.nWords2 = (d.nWords1 + 63) / 64;
-    d.bits0 = dalloc<unsigned long long>(d.nWords0); d.bits1 = dalloc<unsigned long long>(d.nWords1); d.bits2 = dalloc<unsigned long long>(d.nWords2);
-    d.queueCap = d.M + 8; d.eraseCap = d.queueCap;
-    d.eraseList = dalloc<unsigned long long>(d.eraseCap); d.queue = dalloc<PropRec>((size_t)2 * d.queueCap); d.chainSlots = dalloc<ChainSlot>(2); d.launchClock = dalloc<unsigned long long>(2u * GAPS_CLOCK_RING); h.chainGrans = dalloc<unsigned long long>((size_t)d.queueCap * CHAIN_GRAN_STRIDE); d.queueUnits = dalloc<uint32_t>(d.queueCap); d.partials = dalloc<float>((size_t)d.queueCap * 64); d.grans = dalloc<unsigned long long>((size_t)d.queueCap * 64); d.dec = dalloc<DecRec>(d.queueCap);
-    d.rowStamp = dalloc<unsigned long long>(d.M);
-    d.atomStamp = dalloc<unsigned long long>(d.atomCap); d.gapStamp = dalloc<unsigned long long>((size_t)d.atomCap + 1);
-    d.inlineStamp = dalloc<unsigned long long>(d.atomCap); d.atomDest = dalloc<uint64_t>(d.atomCap);
-    d.lcgMul = s->dLcgMul; d.lcgInc = s->dLcgInc;
-    d.binLength = 0xFFFFFFFFFFFFFFFFull / nBins;               // ProposalQueue.cpp:27
-    d.domainLenU = d.binLength * nBins;                         // ConcurrentAtomicDomain.cpp:16-18
-    d.domainLenD = (double)d.domainLenU;                        // ProposalQueue.cpp:30
-    d.numBins = (double)nBins; d.alphaD = (double)alpha;
-    d.invBinLen = 1.0 / (double)d.binLength;
-    d.invK = 1.0 / (double)d.K;
-    if (nBins >= 0xFFFFFFF0ull) throw std::runtime_error("rows x nPatterns must stay below 2^32");
-    d.rboundNone = gm_u64_from_double_x86(d.domainLenD);
-    d.iPartL = 0xFFFFFFFFFFFFFFFFull / d.domainLenU; d.limitL = d.domainLenU * d.iPartL;   // uniform64(1, L)
-    build_death_prob_table(s, d);
-    d.gs = dalloc<GenScalars>(1);
-    GenScalars g; memset(&g, 0, sizeof(g));
-    g.front = CG_NONE;
-    g.qrng = pcg_from_seed(s->seeder.next());                   // ProposalQueue::mRng(randState), ProposalQueue.cpp:24
-    rt_h2d(d.gs, &g, sizeof(g), s->stream); rt_sync(s->stream);
-    h.partial = dalloc<float>(d.M);
-}
-
-// side[w].ptr holds the kept entries per vector: their exclusive scan, the packed values' allocation (allocVals(w, count): the side's
-// owner makes it), the prefix counts; returns the number of kept entries
-template <class AllocVals>
-static uint32_t spb_scan_and_allocate(rt_stream_t stream, SpbSide *side, int nSides, AllocVals &&allocVals)
-{
-    uint32_t kept[2] = {0, 0};
-    for (int w = 0; w < nSides; ++w) { RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, side[w].ptr, side[w].M); rt_d2h(&kept[w], side[w].ptr + side[w].M, 4, stream); }
-    rt_sync(stream);
-    if (nSides == 2 && kept[0] != kept[1]) throw std::runtime_error("internal: the two samplers count different numbers of entries");
-    for (int w = 0; w < nSides; ++w) {
-        side[w].vals = allocVals(w, (size_t)kept[w] + 1);
-        RT_LAUNCH(spb_prefix_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, side[w]);
-    }
-    return kept[0];
-}
-// the packed values are in place: each sampler's ordered sum (sums: two floats of device scratch), then the model and the atomic domain
-static void spb_models(cogaps_session *s, SpbSide *side, HostSampler **hs, uint32_t kept, float *sums)
-{
-    const cogaps_params &p = s->p;
-    // gaps::nonZeroMean (MatrixMath.cpp:39-55): each sampler's sum in the order of its own vectors
-    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);      // (its time is reported: cogaps_session_sparse_build_ms)
-    RT_LAUNCH(spb_ordered_sum_kernel, 2, 256, s->stream, (const float *)side[0].vals, (const float *)side[1].vals, kept, sums);
-    rt_event_stop(ev, s->stream);
-    float sum[2] = {0.f, 0.f}; rt_d2h(sum, sums, 8, s->stream); rt_sync(s->stream);
-    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
-    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
-    for (int w = 0; w < 2; ++w) {      // (the seeder's outputs: A's queue, then P's -- sampler_domain)
-        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum[w], kept);
-        sampler_sparse_model(*hs[w]);
-        sampler_domain(s, *hs[w], alpha[w]);
-    }
-}
-// The two samplers' dimensions and their flag / prefix / pointer arrays (the session's from here on: free_sampler releases them if anything
-// later throws).  Sampler A: vectors = genes, elements = samples; P the other way round (GapsRunner.cpp:402-406).  Genes are the data's
-// rows unless transposeData; the sampler whose vector axis is the input's minor axis takes its entries transposed (SpbSide::swap)
-static void spb_sides(cogaps_session *s, uint32_t nrow, uint32_t ncol, bool majorIsRow, SpbSide *side, HostSampler **hs)
-{
-    const cogaps_params &p = s->p;
-    const uint32_t nGenes = p.transposeData ? ncol : nrow, nSamples = p.transposeData ? nrow : ncol;
-    sampler_dims(s, s->A, 'A', nSamples, nGenes); sampler_dims(s, s->P, 'P', nGenes, nSamples);
-    const bool genesAreRows = !p.transposeData;
-    for (int w = 0; w < 2; ++w) {
-        SamplerDev &d = hs[w]->d; SpbSide &sd = side[w];
-        const bool vectorsAreRows = (w == 0) == genesAreRows;
-        sd.M = d.M; sd.Wn = d.Wn; sd.swap = vectorsAreRows == majorIsRow ? 0u : 1u; sd.vals = nullptr;
-        sd.flags = dalloc<unsigned long long>((size_t)d.M * d.Wn); sd.prefix = dalloc<uint32_t>((size_t)d.M * d.Wn); sd.ptr = dalloc<uint32_t>((size_t)d.M + 1);
-        d.dflags = sd.flags; d.dprefix = sd.prefix; d.dptr = sd.ptr;
-    }
-}
-
-// Device temporaries of a call -- a build's, a result statistic's (result_stats.h): not a session's (allocated under a null owner scope),
-// released when their owner goes, however the call ends
-struct SpbTemps {
-    std::vector<void *> p;
-    ~SpbTemps() { for (void *q : p) rt_free(q); }
-    template <class T> T *alloc(size_t count)
-    {
-        p.push_back(nullptr);      // (the slot first: nothing is ever allocated that has no place here)
-        rt_owner_scope notTheSessions(nullptr); p.back() = dalloc<T>(count); return (T *)p.back();
-    }
-    // one of the caller's arrays where the kernels read it: uploaded, or used where it is
-    template <class T> const T *stage(const T *src, size_t count, bool onDevice, rt_stream_t stream)
-    {
-        if (onDevice) return src;
-        T *q = alloc<T>(count + 1);
-        if (count) rt_h2d(q, src, count * sizeof(T), stream);
-        return q;
-    }
-    uint32_t *err() { return alloc<uint32_t>(4); }      // the error word, the two ordered sums
-};
-
-// A sparse-model matrix in device memory as the one builder reads it: a plain description that owns nothing.  The arrays are a
-// caller's, staged for one session (build_samplers_sparse_input / _coo_input), or a cogaps_device_matrix's; either way they have been
-// through spb_compressed or spb_triplets -- checked, triplets resolved into keep[] -- before anything is built from them.
-struct SpbMatrix {
-    uint32_t nrow = 0, ncol = 0; uint64_t nnz = 0;
-    bool coo = false, majorIsRow = true;
-    const uint64_t *indptr = nullptr; const uint32_t *indices = nullptr;      // compressed: [nMajor + 1], [nnz]
-    const uint32_t *rows = nullptr, *cols = nullptr;                          // triplets: [nnz]
-    const unsigned long long *keep = nullptr;                                 // triplets: bit k = entry k is the latest of its position and > 0
-    const float *values = nullptr;
-    uint32_t nMajor() const { return majorIsRow ? nrow : ncol; }
-    uint32_t nMinor() const { return majorIsRow ? ncol : nrow; }
-};
-static uint32_t entry_grid(uint64_t n, unsigned computeUnits, uint32_t bs)
-{
-    // grid-stride over the entries: enough workgroups to fill the device, never more than the entries need (at least one)
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + bs - 1) / bs, (uint64_t)computeUnits * 8u));
-}
-static void spb_check_entries(uint64_t n)
-{
-    if (n >= 0xFFFFFFFFull) throw std::runtime_error("compressed-sparse matrix: 2^32 - 1 stored entries or more (the packed values are indexed by 32 bits)");
-}
-// What a caller's sparse matrix is refused for before anything else is looked at (null: nothing)
-static const char *sparse_args_refusal(const cogaps_sparse_matrix *sp, const cogaps_coo_matrix *coo)
-{
-    if (sp) return sp->indptr ? nullptr : "null argument: indptr";
-    if (!coo) return nullptr;
-    if (coo->nnz >= 0xFFFFFFFFull) return "triplet matrix: 2^32 - 1 entries or more (entries and packed values are indexed by 32 bits)";
-    if (coo->nnz && (!coo->rows || !coo->cols || !coo->values)) return "null argument: rows / cols / values";
-    return nullptr;
-}
-
-// The caller's compressed matrix, checked (sparse_build.h, spb_validate_kernel), as d.  place(array, count) puts one of the caller's
-// arrays where the kernels read it and says where that is: staged for the call, or copied into a handle's own memory.
-template <class Place> static void spb_compressed(SpbMatrix &d, const cogaps_sparse_matrix &m, rt_stream_t stream, Place &&place)
-{
-    d.nrow = m.nrow; d.ncol = m.ncol; d.coo = false; d.majorIsRow = m.majorIsRow != 0;
-    const uint32_t nMajor = d.nMajor();
-    if (m.onDevice) { rt_d2h(&d.nnz, m.indptr + nMajor, 8, stream); rt_sync(stream); } else d.nnz = m.indptr[nMajor];
-    spb_check_entries(d.nnz);
-    if (d.nnz && (!m.indices || !m.values)) throw std::runtime_error("null argument: indices / values");
-    d.indptr = place(m.indptr, (size_t)nMajor + 1); d.indices = place(m.indices, (size_t)d.nnz); d.values = place(m.values, (size_t)d.nnz);
-    SpbTemps tmp; uint32_t *err = tmp.err();
-    SpbIn in; in.nMajor = nMajor; in.nMinor = d.nMinor(); in.nnz = d.nnz; in.indptr = d.indptr; in.indices = d.indices; in.values = d.values;
-    RT_LAUNCH(spb_validate_kernel, (nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, in, err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
-    if (code == SPB_ERR_INDPTR) throw std::runtime_error("compressed-sparse matrix: indptr must start at 0, never decrease and end at the number of stored entries");
-    if (code == SPB_ERR_RANGE) throw std::runtime_error("compressed-sparse matrix: an index is outside the minor dimension");
-    if (code != 0) throw std::runtime_error("compressed-sparse matrix: the indices of a row / column must be strictly ascending (sorted, no duplicates)");
-}
-
-// The caller's triplets, checked and resolved (sparse_build.h, passes 1 to 4 of its second half), as d: keep -- nnz / 64 + 1 words, the
-// caller's to own -- gets one bit per entry.  The present flags with their prefix counts and pointers and the winner indices are
-// temporaries of this call: O(nnz + nrow x ncol / 64 bits).
-template <class Place> static void spb_triplets(SpbMatrix &d, const cogaps_coo_matrix &m, unsigned long long *keep, unsigned computeUnits, rt_stream_t stream, Place &&place)
-{
-    d.keep = keep;
-    d.nrow = m.nrow; d.ncol = m.ncol; d.coo = true; d.majorIsRow = true; d.nnz = m.nnz;
-    d.rows = place(m.rows, (size_t)d.nnz); d.cols = place(m.cols, (size_t)d.nnz); d.values = place(m.values, (size_t)d.nnz);
-    SpbTemps tmp; uint32_t *err = tmp.err();
-    CooIn in; in.nrow = d.nrow; in.ncol = d.ncol; in.nnz = d.nnz; in.rows = d.rows; in.cols = d.cols; in.values = d.values;
-    SpbSide pres; pres.M = d.nrow; pres.Wn = d.ncol / 64u + 1u; pres.swap = 0u; pres.vals = nullptr;
-    pres.flags = tmp.alloc<unsigned long long>((size_t)pres.M * pres.Wn); pres.prefix = tmp.alloc<uint32_t>((size_t)pres.M * pres.Wn);
-    pres.ptr = tmp.alloc<uint32_t>((size_t)pres.M + 1);
-    const uint32_t grid = entry_grid(d.nnz, computeUnits, COO_BS), vecGrid = (pres.M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
-    RT_LAUNCH(coo_present_kernel, grid, COO_BS, stream, in, pres, err);
-    uint32_t code = 0; rt_d2h(&code, err, 4, stream); rt_sync(stream);
-    if (code != 0) throw std::runtime_error("triplet matrix: a row or column index is outside the stated dimensions");
-    RT_LAUNCH(spb_count_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
-    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, stream, pres.ptr, pres.M);
-    RT_LAUNCH(spb_prefix_kernel, vecGrid, 64 * SPB_WAVES, stream, pres);
-    uint32_t nPresent = 0; rt_d2h(&nPresent, pres.ptr + pres.M, 4, stream); rt_sync(stream);
-    uint32_t *winner = tmp.alloc<uint32_t>((size_t)nPresent + 1);
-    RT_LAUNCH(coo_winner_kernel, grid, COO_BS, stream, in, pres, winner);
-    RT_LAUNCH(coo_keep_bits_kernel, grid, COO_BS, stream, in, pres, (const uint32_t *)winner, keep);
-    rt_sync(stream);
-}
-
-// The builder's passes over a checked matrix in device memory (sparse_build.h, passes 3 to 5 of the mapped route): the flag bits, the
-// counts, their scan, the prefix counts and the packed values of the sides given, whose flags / prefix / ptr arrays are allocated and
-// zero.  Two sides: a session's samplers.  One side: the gene side alone, which is all the residuals of a result read
-// (cogaps_residuals) -- the mapped kernels then get that side for both of theirs, see that the two are one (spb_mapped_entry) and
-// set every bit, and store every value, once.  mapped: the map repeats indices, so the kept entries are counted in 64 bits before the 32-bit scan (without a map
-// they cannot exceed nnz).  Returns the number of kept entries.
-template <class AllocVals>
-static uint32_t spb_build_sides(const SpbMatrix &dm, const SpbMap &mp, bool mapped, SpbSide *side, int nSides, unsigned computeUnits, rt_stream_t stream, AllocVals &&allocVals)
-{
-    const SpbSide &a = side[0], &b = side[nSides - 1];
-    SpbIn in; CooIn cin;
-    in.nMajor = dm.nMajor(); in.nMinor = dm.nMinor(); in.nnz = dm.nnz; in.indptr = dm.indptr; in.indices = dm.indices; in.values = dm.values;
-    cin.nrow = dm.nrow; cin.ncol = dm.ncol; cin.nnz = dm.nnz; cin.rows = dm.rows; cin.cols = dm.cols; cin.values = dm.values;
-    const uint32_t sliceGrid = (in.nMajor + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, grid = entry_grid(dm.nnz, computeUnits, COO_BS);
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<false>, grid, COO_BS, stream, cin, dm.keep, mp, a, b);
-    else RT_LAUNCH(spb_mapped_kernel<false>, sliceGrid, 64 * SPB_WAVES, stream, in, mp, a, b);
-    for (int w = 0; w < nSides; ++w) RT_LAUNCH(spb_count_kernel, (side[w].M + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES, 64 * SPB_WAVES, stream, side[w]);
-    if (mapped) {
-        std::vector<uint32_t> counts(side[0].M); rt_d2h(counts.data(), side[0].ptr, (size_t)side[0].M * 4, stream); rt_sync(stream);
-        uint64_t total = 0; for (uint32_t c : counts) total += c;
-        spb_check_entries(total);
-    }
-    const uint32_t kept = spb_scan_and_allocate(stream, side, nSides, allocVals);
-    // (the sides now carry their vals: the references above see them)
-    if (dm.coo) RT_LAUNCH(coo_mapped_kernel<true>, grid, COO_BS, stream, cin, dm.keep, mp, a, b);
-    else RT_LAUNCH(spb_mapped_kernel<true>, sliceGrid, 64 * SPB_WAVES, stream, in, mp, a, b);
-    return kept;
-}
-
-// Both samplers of a sparse-model session from a checked matrix in device memory, with or without a subset of its rows or columns
-// (sparse_build.h, the map and the mapped passes): THE builder of the sparse model, whatever form the input had.  subset: subsetData's
-// 1-based indices, or null -- also for a caller that has applied them already.  One read of the entries per mapped pass; the session's
-// allocations are those of any sparse-model session, the temporaries (the subset's indices, counts, cursors, list) O(dim + n).  Nothing
-// is uploaded but the subset's indices.
-static void build_samplers_device_matrix(cogaps_session *s, const SpbMatrix &dm, const std::vector<uint32_t> *subset)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetRows = subset && (p.subsetGenes != 0) == (p.transposeData == 0);
-    const uint32_t nIdx = subset ? (uint32_t)subset->size() : 0u;
-    const uint32_t nrow = subset && subsetRows ? nIdx : dm.nrow, ncol = subset && !subsetRows ? nIdx : dm.ncol;
-    SpbTemps tmp;
-    SpbSide side[2];
-    HostSampler *hs[2] = {&s->A, &s->P};
-    spb_sides(s, nrow, ncol, dm.majorIsRow, side, hs);
-    SpbMap mp; mp.start = mp.list = nullptr; mp.onMajor = subsetRows == dm.majorIsRow ? 1u : 0u;
-    if (subset) {
-        const uint32_t dim = subsetRows ? dm.nrow : dm.ncol;
-        const uint32_t *indices = tmp.stage(subset->data(), nIdx, false, s->stream);
-        uint32_t *start = tmp.alloc<uint32_t>((size_t)dim + 1), *cursor = tmp.alloc<uint32_t>(dim), *list = tmp.alloc<uint32_t>(nIdx);
-        const uint32_t mapGrid = entry_grid(nIdx, s->computeUnits, SPB_MAP_BS);
-        RT_LAUNCH(spb_map_count_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, start);
-        RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, start, dim);
-        RT_LAUNCH(spb_map_fill_kernel, mapGrid, SPB_MAP_BS, s->stream, indices, nIdx, (const uint32_t *)start, cursor, list);
-        mp.start = start; mp.list = list;
-    }
-    const uint32_t kept = spb_build_sides(dm, mp, subset != nullptr, side, 2, s->computeUnits, s->stream,
-                                          [&](int w, size_t n) { float *v = dalloc<float>(n); hs[w]->d.dvals = v; return v; });
-    spb_models(s, side, hs, kept, (float *)(tmp.err() + 1));
-}
-
-// The one-shot entries: the caller's arrays staged for this call (SpbTemps::stage: uploaded from host pointers, read in place from
-// device pointers), checked, then the builder with no subset.  A compressed-sparse matrix is the caller's (cogaps_session_create_sparse)
-// or a dense input's entries > 0 (build_samplers_dense_input, build_samplers_dense_device_sparse); triplets (cogaps_session_create_coo)
-// make the session cogaps_session_create makes from the matrix they denote -- the latest entry of a position decides it.  No nrow x ncol
-// array exists on either side.
-static void build_samplers_sparse_input(cogaps_session *s, const cogaps_sparse_matrix &m)
-{
-    SpbTemps tmp; SpbMatrix d;
-    spb_compressed(d, m, s->stream, [&](auto *src, size_t n) { return tmp.stage(src, n, m.onDevice != 0, s->stream); });
-    build_samplers_device_matrix(s, d, nullptr);
-}
-static void build_samplers_coo_input(cogaps_session *s, const cogaps_coo_matrix &m)
-{
-    SpbTemps tmp; SpbMatrix d;
-    spb_triplets(d, m, tmp.alloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), s->computeUnits, s->stream,
-                 [&](auto *src, size_t n) { return tmp.stage(src, n, m.onDevice != 0, s->stream); });
-    build_samplers_device_matrix(s, d, nullptr);
-}
-
-// The sparse model from a dense matrix: its entries > 0 (SparseVector.cpp:20-33: NaN, zero and negative values are absent), row by row
-// in the data's own orientation, as the CSR matrix build_samplers_sparse_input takes.  subsetData picks rows or columns here, by
-// Matrix.cpp:30-69's rule: 1-based indices in the order given, on the genes or the samples (genes are the data's rows unless
-// transposeData); output row / column i is input indices[i] - 1, so the column indices ascend whatever the order of the subset.
-static void build_samplers_dense_input(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetData = p.subsetData && !s->subset.empty();
-    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0), subsetCols = subsetData && !subsetRows;
-    const uint32_t *indices = s->subset.data(); const uint32_t nIdx = (uint32_t)s->subset.size();
-    cogaps_sparse_matrix m; memset(&m, 0, sizeof(m));
-    m.nrow = subsetRows ? nIdx : nrow; m.ncol = subsetCols ? nIdx : ncol; m.majorIsRow = 1;
-    std::vector<uint64_t> indptr((size_t)m.nrow + 1, 0); std::vector<uint32_t> cols; std::vector<float> vals;
-    for (uint32_t r = 0; r < m.nrow; ++r) {
-        const float *row = data + (size_t)(subsetRows ? indices[r] - 1 : r) * ncol;
-        for (uint32_t c = 0; c < m.ncol; ++c) {
-            const float v = row[subsetCols ? indices[c] - 1 : c];
-            if (v > 0.f) { cols.push_back(c); vals.push_back(v); }
-        }
-        indptr[(size_t)r + 1] = vals.size();
-    }
-    m.indptr = indptr.data(); m.indices = cols.data(); m.values = vals.data();
-    build_samplers_sparse_input(s, m);
-}
-
-// A matrix resident on one device: the description with device copies of the caller's arrays, which it owns -- checked and, for
-// triplets, resolved once, at its creation.  Immutable from then on: any number of sessions, on any host threads, are built from it
-// (build_samplers_device_matrix) and copy nothing of it but what their packed structures hold.
-struct cogaps_device_matrix {
-    SpbMatrix m;
-    int device = 0; unsigned computeUnits = 0;
-    std::atomic<uint64_t> deviceBytes{0};
-    ~cogaps_device_matrix() { rt_free((void *)m.indptr); rt_free((void *)m.indices); rt_free((void *)m.rows); rt_free((void *)m.cols); rt_free((void *)m.keep); rt_free((void *)m.values); }
-};
-// one of the caller's arrays into the handle's own memory (count + 1 elements: never an empty allocation)
-template <class T> static T *dm_copy(const T *src, size_t count, bool onDevice, rt_stream_t stream)
-{
-    T *q = dalloc<T>(count + 1);
-    if (count) { if (onDevice) rt_d2d(q, src, count * sizeof(T), stream); else rt_h2d(q, src, count * sizeof(T), stream); }
-    return q;
-}
-static void device_matrix_from_sparse(cogaps_device_matrix *dm, const cogaps_sparse_matrix &m, rt_stream_t stream)
-{
-    spb_compressed(dm->m, m, stream, [&](auto *src, size_t n) { return dm_copy(src, n, m.onDevice != 0, stream); });
-}
-static void device_matrix_from_coo(cogaps_device_matrix *dm, const cogaps_coo_matrix &m, rt_stream_t stream)
-{
-    spb_triplets(dm->m, m, dalloc<unsigned long long>((size_t)(m.nnz / 64 + 1)), dm->computeUnits, stream,
-                 [&](auto *src, size_t n) { return dm_copy(src, n, m.onDevice != 0, stream); });
-}
-
-// ---- dense input resident on the device (cogaps_session_create with data_on_device = 1; dense_build.h) ----
-// subsetData's indices in device memory (a temporary), or null without a subset
-static const uint32_t *dnb_subset(cogaps_session *s, SpbTemps &tmp)
-{
-    const bool subsetData = s->p.subsetData && !s->subset.empty();
-    return subsetData ? tmp.stage(s->subset.data(), s->subset.size(), false, s->stream) : nullptr;
-}
-static uint32_t dnb_grid(uint64_t workgroups)
-{
-    if (workgroups == 0 || workgroups > 0x7FFFFFFFull) throw std::runtime_error("the matrix has more tiles than one launch has workgroups");
-    return (uint32_t)workgroups;
-}
-
-// Both samplers of the dense model from the device-resident matrix: build_sampler's arrays and constants, bit for bit, with nothing of
-// the matrix on the host.  Per sampler one fill launch (D, Sraw, S2 if kept, the pads, the count of entries > 0), then both ordered sums
-// in one launch (its time: cogaps_session_sparse_build_ms), then the models and the atomic domains in build_sampler's order -- the
-// seeder's outputs go to A's queue, then P's.  The session owns what build_sampler's session owns; the indices, the sums and the
-// counts are temporaries.
-static void build_samplers_dense_device(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol, const float *unc)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetData = p.subsetData && !s->subset.empty();
-    const uint32_t nIdx = (uint32_t)s->subset.size();
-    SpbTemps tmp;
-    const uint32_t *dIdx = dnb_subset(s, tmp);
-    uint32_t *scratch = tmp.err();      // [0], [1]: the counts of entries > 0, [2], [3]: the ordered sums (as floats)
-    const bool defaultS = unc == nullptr && !dev_env("COGAPS_READ_S");      // (build_sampler: no S2 array with the default uncertainty)
-    HostSampler *hs[2] = {&s->A, &s->P};
-    const bool genesInCols[2] = {!p.transposeData, p.transposeData != 0}, subsetGenes[2] = {!p.subsetGenes, p.subsetGenes != 0};      // GapsRunner.cpp:402-406
-    const float alpha[2] = {p.alphaA, p.alphaP}, maxGibbs[2] = {p.maxGibbsMassA, p.maxGibbsMassP};
-    size_t tot[2];
-    for (int w = 0; w < 2; ++w) {
-        HostSampler &h = *hs[w]; SamplerDev &d = h.d;
-        const uint32_t nG = (subsetData && subsetGenes[w]) ? nIdx : (genesInCols[w] ? ncol : nrow);
-        const uint32_t nS = (subsetData && !subsetGenes[w]) ? nIdx : (genesInCols[w] ? nrow : ncol);
-        sampler_dims(s, h, w == 0 ? 'A' : 'P', nG, nS);
-        tot[w] = (size_t)d.M * d.Npad;
-        float *dD = dalloc<float>(tot[w]); d.D = dD;
-        float *dS2 = defaultS ? nullptr : dalloc<float>(tot[w]); d.S2 = dS2;
-        h.Sraw = dalloc<float>(tot[w]); d.defaultS = defaultS ? 1u : 0u;
-        // Matrix.cpp:30-69: the indices pick input rows when subsetGenes != genesInCols, input columns otherwise
-        const uint32_t *rowMap = subsetGenes[w] != genesInCols[w] ? dIdx : nullptr, *colMap = subsetGenes[w] == genesInCols[w] ? dIdx : nullptr;
-        DnbIn in; in.data = data; in.unc = unc; in.nrow = nrow; in.ncol = ncol;
-        DnbOut o; o.D = dD; o.Sraw = h.Sraw; o.S2 = dS2; o.M = d.M; o.N = d.N; o.Npad = d.Npad;
-        if (genesInCols[w]) {      // the vectors are input rows
-            in.vecMap = rowMap; in.elMap = colMap;
-            const uint32_t chunks = (d.Npad + (uint32_t)DNB_BS - 1u) / (uint32_t)DNB_BS;
-            RT_LAUNCH(dnb_rows_kernel, dnb_grid((uint64_t)d.M * chunks), DNB_BS, s->stream, in, o, chunks, scratch + w);
-        } else {                   // the vectors are input columns
-            in.vecMap = colMap; in.elMap = rowMap;
-            const uint32_t tilesI = (d.Npad + (uint32_t)DNB_TILE - 1u) / (uint32_t)DNB_TILE, tilesJ = (d.M + (uint32_t)DNB_TILE - 1u) / (uint32_t)DNB_TILE;
-            RT_LAUNCH(dnb_cols_kernel, dnb_grid((uint64_t)tilesI * tilesJ), DNB_BS, s->stream, in, o, tilesI, scratch + w);
-        }
-    }
-    rt_event_pair ev; rt_event_create(ev); rt_event_start(ev, s->stream);
-    RT_LAUNCH(dnb_ordered_sum_kernel, 2, DNB_SUM_BS, s->stream, s->A.d.D, (uint64_t)tot[0], s->P.d.D, (uint64_t)tot[1], (float *)(scratch + 2));
-    rt_event_stop(ev, s->stream);
-    uint32_t host[4]; rt_d2h(host, scratch, sizeof(host), s->stream); rt_sync(s->stream);
-    s->orderedSumMs = rt_event_ms(ev); rt_event_destroy(ev);
-    for (int w = 0; w < 2; ++w) {
-        float sum; memcpy(&sum, &host[2 + w], 4);
-        sampler_model(*hs[w], alpha[w], maxGibbs[w], sum, host[w]);
-        hs[w]->d.AP = dalloc<float>(tot[w]);
-        sampler_domain(s, *hs[w], alpha[w]);
-    }
-}
-
-// The sparse model from the device-resident matrix: build_samplers_dense_input's CSR matrix -- the entries > 0 of the subset's rows and
-// columns, ascending column indices -- compacted on the device, then the one builder.  The CSR arrays are temporaries of this call.
-static void build_samplers_dense_device_sparse(cogaps_session *s, const float *data, uint32_t nrow, uint32_t ncol)
-{
-    const cogaps_params &p = s->p;
-    const bool subsetData = p.subsetData && !s->subset.empty();
-    const bool subsetRows = subsetData && (p.subsetGenes != 0) == (p.transposeData == 0), subsetCols = subsetData && !subsetRows;
-    const uint32_t nIdx = (uint32_t)s->subset.size();
-    SpbTemps tmp;
-    const uint32_t *dIdx = dnb_subset(s, tmp);
-    cogaps_sparse_matrix m; memset(&m, 0, sizeof(m));
-    m.nrow = subsetRows ? nIdx : nrow; m.ncol = subsetCols ? nIdx : ncol; m.majorIsRow = 1; m.onDevice = 1;
-    DnbIn in; in.data = data; in.unc = nullptr; in.nrow = nrow; in.ncol = ncol; in.vecMap = subsetRows ? dIdx : nullptr; in.elMap = subsetCols ? dIdx : nullptr;
-    uint32_t *ptr = tmp.alloc<uint32_t>((size_t)m.nrow + 1);
-    const uint32_t rowGrid = (m.nrow + (uint32_t)SPB_WAVES - 1u) / (uint32_t)SPB_WAVES;
-    RT_LAUNCH(dnb_csr_count_kernel, rowGrid, 64 * SPB_WAVES, s->stream, in, m.nrow, m.ncol, ptr);
-    // the total in 64 bits before the 32-bit scan
-    std::vector<uint32_t> counts(m.nrow); rt_d2h(counts.data(), ptr, (size_t)m.nrow * 4, s->stream); rt_sync(s->stream);
-    uint64_t total = 0; for (uint32_t c : counts) total += c;
-    spb_check_entries(total);
-    RT_LAUNCH(spb_scan_kernel, 1, SPB_SCAN_BS, s->stream, ptr, m.nrow);
-    uint64_t *indptr = tmp.alloc<uint64_t>((size_t)m.nrow + 1); uint32_t *indices = tmp.alloc<uint32_t>((size_t)total + 1); float *values = tmp.alloc<float>((size_t)total + 1);
-    RT_LAUNCH(dnb_csr_fill_kernel, rowGrid, 64 * SPB_WAVES, s->stream, in, m.nrow, m.ncol, (const uint32_t *)ptr, indptr, indices, values);
-    m.indptr = indptr; m.indices = indices; m.values = values;
-    build_samplers_sparse_input(s, m);
-}
+// building a session's samplers from every form of input, at its place among the chapters: the kernels keep their order of first use
+#include "session_build.h"
 
 #include "sampler_update.h"
 
@@ -1031,46 +507,10 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
 {
     cogaps_session *s = nullptr;
     try {
-        if (!params) { fail("null argument"); return nullptr; }
+        if (sp) { nrow = sp->nrow; ncol = sp->ncol; } else if (coo) { nrow = coo->nrow; ncol = coo->ncol; } else if (dm) { nrow = dm->m.nrow; ncol = dm->m.ncol; }
+        const std::string refusal = session_args_refusal(data, nrow, ncol, params, sp, coo, dm);      // (before the GPU is touched)
+        if (!refusal.empty()) { fail(refusal); return nullptr; }
         const cogaps_params &p = *params;
-        if (sp) {
-            nrow = sp->nrow; ncol = sp->ncol;
-            if (!p.useSparseOptimization) { fail("a compressed-sparse matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
-            if (p.subsetData) { fail("subsetData is not supported with a compressed-sparse matrix: pass the rows / columns of the subset"); return nullptr; }
-            if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a compressed-sparse matrix"); return nullptr; }
-        } else if (coo) {
-            nrow = coo->nrow; ncol = coo->ncol;
-            if (!p.useSparseOptimization) { fail("a triplet matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
-            if (p.subsetData) { fail("subsetData is not supported with a triplet matrix: pass the entries of the subset"); return nullptr; }
-            if (p.reductionMode == COGAPS_REDUCE_SEQ) { fail("reductionMode COGAPS_REDUCE_SEQ is not supported with a triplet matrix"); return nullptr; }
-        } else if (dm) {
-            nrow = dm->m.nrow; ncol = dm->m.ncol;
-            if (!p.useSparseOptimization) { fail("a device-resident matrix needs useSparseOptimization = 1 (the dense model takes a dense matrix)"); return nullptr; }
-            if (p.device != dm->device) { fail("params->device must be -1 or the device the matrix resides on (" + std::to_string(dm->device) + ")"); return nullptr; }
-        } else if (!data) { fail("null argument: data"); return nullptr; }
-        if (const char *refusal = sparse_args_refusal(sp, coo)) { fail(refusal); return nullptr; }
-        // The reference's distributed caller forces asynchronousUpdates = FALSE on its workers (R/DistributedCogaps.R:28-29) -- there to keep
-        // BiocParallel workers single-threaded, not for the sampler's sake.  Documented deviation: a
-        // distributed worker call (runningDistributed, i.e. subsetDim > 0 in cogaps_cpp, Cogaps.cpp:82) runs the asynchronous sampler anyway,
-        // so that GWCoGAPS / scCoGAPS through the real R package reach this library.  Everywhere else FALSE is refused.
-        if (!p.asynchronousUpdates && !p.runningDistributed) { fail("asynchronousUpdates=FALSE (SingleThreadedGibbsSampler) is not part of this library"); return nullptr; }
-        // The sequential sampler (seq_kernel.h) is chosen by `sampler` alone: asynchronousUpdates keeps the meaning above.
-        if (p.sampler != COGAPS_SAMPLER_ASYNC && p.sampler != COGAPS_SAMPLER_SEQUENTIAL) { fail("sampler must be COGAPS_SAMPLER_ASYNC or COGAPS_SAMPLER_SEQUENTIAL"); return nullptr; }
-        if (p.sampler == COGAPS_SAMPLER_SEQUENTIAL && p.useSparseOptimization) { fail("sampler = COGAPS_SAMPLER_SEQUENTIAL supports the dense model only: the SparseNormalModel evaluation of the sequential kernel is missing (useSparseOptimization must be 0)"); return nullptr; }
-        if (p.nPatterns == 0 || nrow == 0 || ncol == 0) { fail("empty problem"); return nullptr; }
-        if (p.whichMatrixFixed != 'N' && p.whichMatrixFixed != 'A' && p.whichMatrixFixed != 'P') { fail("whichMatrixFixed must be 'N', 'A' or 'P'"); return nullptr; }
-        if (p.reductionMode != COGAPS_REDUCE_LANES && p.reductionMode != COGAPS_REDUCE_SEQ) { fail("reductionMode must be COGAPS_REDUCE_LANES or COGAPS_REDUCE_SEQ"); return nullptr; }
-        if (p.mathMode < COGAPS_MATH_PORTABLE || p.mathMode > COGAPS_MATH_GLIBC_SSE2) { fail("mathMode must be COGAPS_MATH_PORTABLE, _GLIBC_FMA or _GLIBC_SSE2"); return nullptr; }
-        if (p.mathMode != COGAPS_MATH_PORTABLE && p.reductionMode != COGAPS_REDUCE_SEQ) { fail("mathMode other than COGAPS_MATH_PORTABLE needs reductionMode COGAPS_REDUCE_SEQ (the verification mode)"); return nullptr; }
-        if (p.pumpThreshold != 0 && p.pumpThreshold != 1) { fail("pumpThreshold must be 0 (PUMP_UNIQUE) or 1 (PUMP_CUT)"); return nullptr; }
-        if (p.whichMatrixFixed != 'N' && p.fixedCols != 0 && (uint32_t)p.fixedCols != p.nPatterns) { fail("fixedPatterns must have nPatterns columns"); return nullptr; }
-        if (p.subsetData && p.dataIndicesSubset) {
-            // 1-based indices into the subset dimension (Matrix.cpp:55-62): genes are the rows of the data unless transposeData
-            const uint32_t dim = (p.subsetGenes != 0) == (p.transposeData == 0) ? nrow : ncol;
-            if (p.nSubset == 0) { fail("dataIndicesSubset is empty"); return nullptr; }
-            for (uint32_t i = 0; i < p.nSubset; ++i)
-                if (p.dataIndicesSubset[i] < 1u || p.dataIndicesSubset[i] > dim) { fail("dataIndicesSubset holds an index outside 1 .. " + std::to_string(dim)); return nullptr; }
-        }
         rt_set_device(p.device);
         s = new cogaps_session(); s->computeUnits = rt_compute_units();
         s->p = p;
@@ -1096,13 +536,13 @@ static cogaps_session *session_create(const float *data, uint32_t nrow, uint32_t
         // seed order: A queue, P queue, runner (AsynchronousGibbsSampler.h:68, GapsRunner.cpp:437)
         if (sp) build_samplers_sparse_input(s, *sp);
         else if (coo) build_samplers_coo_input(s, *coo);
-        else if (dm) build_samplers_device_matrix(s, dm->m, p.subsetData && !s->subset.empty() ? &s->subset : nullptr);
+        else if (dm) build_samplers_device_matrix(s, dm->m, &s->subset);
         else if (data_on_device) {      // device-resident dense input (and uncertainty): built where it lies (dense_build.h)
             if (p.useSparseOptimization) build_samplers_dense_device_sparse(s, data, nrow, ncol); else build_samplers_dense_device(s, data, nrow, ncol, unc);
         } else if (p.useSparseOptimization) build_samplers_dense_input(s, data, nrow, ncol);      // (unc: the sparse model always assumes the default, SparseNormalModel.h:90-96)
         else {
-            build_sampler(s, s->A, 'A', data, nrow, ncol, unc, !p.transposeData, !p.subsetGenes, p.alphaA, p.maxGibbsMassA);
-            build_sampler(s, s->P, 'P', data, nrow, ncol, unc, p.transposeData != 0, p.subsetGenes != 0, p.alphaP, p.maxGibbsMassP);
+            const Orientation o = orientation(s->p, s->subset.size(), nrow, ncol);
+            for (int w = 0; w < 2; ++w) build_sampler(s, w, o, data, ncol, unc);
         }
         s->nGenes = s->A.d.M; s->nSamples = s->P.d.M; s->K = p.nPatterns;
         if (s->A.d.N != s->P.d.M || s->P.d.N != s->A.d.M) throw std::runtime_error("internal: sampler dimensions do not mirror");
@@ -1714,268 +1154,8 @@ int cogaps_session_chained(cogaps_session *s, char which, int *chained)
     SESSION_END
 }
 
-// ================================================================================================================================
-// The library's own STATE FILE: what changes while a chain runs, saved between two iterations and loaded into a session created the
-// ordinary way from the same data and parameters -- the resumed chain is the uninterrupted chain, bit for bit.  (Not the reference's
-// Archive checkpoints: cogaps_checkpoints_enabled stays 0.)  Container: state_file.h.  Sections:
-//   fingerprint  what a file and a session must agree on, as 64-bit words in the order of FP_NAMES
-//   meta         StateMeta: position, host generators, counters, times, the lengths of the variable sections
-//   per session  the seeder's look-ahead, the four statistics accumulators, the PUMP matrix, snapshots, the three histories
-//   per sampler that runs (a fixed matrix's sampler keeps what creation gave it): GenScalars, the factor matrix, colPos, the atomic
-//                domain -- atom records up to the handle high-water mark, the index vector up to the atom count, the free-handle stack up
-//                to its depth, bin heads, occupancy bitmaps --, for the sparse model the row copy, its flags and the lookup tables
-//   A*P          the dense model's cache of ONE sampler: P's, or A's when P is fixed; without a fixed matrix A's is its transpose (do_sync)
-// Not in the file, because the next batch cannot see them: the conflict stamps and queued-move destinations (valid for their own batch
-// epoch only; a load clears them), the queue, the erase cache (empty between updates), hand-over granules; and nothing of the data, the
-// lookup tables or a capacity.  Launch form -- chained or not, graphs, generator window, a batch -- is the loading session's own.
-// ================================================================================================================================
-static const char *const FP_NAMES[] = {
-    "model (useSparseOptimization)", "nGenes", "nSamples", "nPatterns", "seed", "nIterations", "alphaA", "alphaP", "maxGibbsMassA", "maxGibbsMassP",
-    "outputFrequency", "snapshotFrequency", "snapshotPhase", "takePumpSamples", "pumpThreshold", "whichMatrixFixed", "fixedPatterns",
-    "reductionMode", "mathMode", "lambda of A (data)", "lambda of P (data)", "maxGibbsMass / lambda of A (data)", "maxGibbsMass / lambda of P (data)",
-    "dataSparsity of A (data)", "dataSparsity of P (data)", "number of packed values (data)", "data digest (the data differ)" };
-static const int FP_N = (int)(sizeof(FP_NAMES) / sizeof(FP_NAMES[0]));
-struct StateMeta {
-    uint32_t phase, nextIter;
-    uint64_t seeder0, seeder1, runnerRng, totalUpdates;
-    double samplerSeconds, elapsedSeconds;
-    uint32_t statUpdates, pumpUpdates, nSnap[2], nHistory, genScalarsBytes;
-    uint64_t nSeedFifo;
-    struct { uint32_t present, nAtoms; float avgQueue, anneal; } samp[2];
-};
-enum { SEC_FINGERPRINT = 1, SEC_META, SEC_SEEDFIFO, SEC_ASUM, SEC_ASQ, SEC_PSUM, SEC_PSQ, SEC_PUMP, SEC_SNAP_A_EQ, SEC_SNAP_P_EQ, SEC_SNAP_A_SA, SEC_SNAP_P_SA,
-       SEC_CHISQ_HIST, SEC_ATOM_HIST_A, SEC_ATOM_HIST_P,
-       SEC_SAMPLER = 0x100,      // + 0x100 * (0: A, 1: P) + one of:
-       SS_GS = 0, SS_MAT, SS_COLPOS, SS_ATOMS, SS_VEC, SS_FREE, SS_BINHEAD, SS_BITS0, SS_BITS1, SS_BITS2, SS_AP, SS_ROWS, SS_MFLAGS, SS_Z1, SS_Z2 };
-static const size_t STATE_STAGING_BYTES = (size_t)4 << 20;      // device arrays pass through one pinned buffer of this size
-
-static float f_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-// the data digest (state_digest.h), computed once per session, at its first save or load; its scratch word is not the session's
-static uint64_t data_digest(cogaps_session *s)
-{
-    if (s->digestValid) return s->dataDigest;
-    const SamplerDev &d = s->A.d;
-    rt_owner_scope notTheSessions(nullptr);
-    unsigned long long *out = dalloc<unsigned long long>(1);
-    try {
-        uint32_t nVals = 0;
-        if (d.sparse) { rt_d2h(&nVals, d.dptr + d.M, 4, s->stream); rt_sync(s->stream); }
-        const unsigned long long rows = d.sparse ? 1ull : d.M, nFlags = d.sparse ? (unsigned long long)d.M * d.Wn : 0ull;
-        const uint32_t N = d.sparse ? nVals : d.N, stride = d.sparse ? nVals : d.Npad;
-        const unsigned long long items = std::max<unsigned long long>(rows * N, nFlags);
-        const uint32_t grid = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>((items + 4u * DIGEST_BS - 1u) / (4u * DIGEST_BS), 2048u));
-        RT_LAUNCH(state_digest_kernel, grid, DIGEST_BS, s->stream, (const uint32_t *)(d.sparse ? (const void *)d.dvals : (const void *)d.D), rows, N, stride,
-                  (const unsigned long long *)d.dflags, nFlags, out);
-        unsigned long long v = 0; rt_d2h(&v, out, 8, s->stream); rt_sync(s->stream);
-        s->dataDigest = v; s->digestValid = true;
-    } catch (...) { rt_free(out); throw; }
-    rt_free(out);
-    return s->dataDigest;
-}
-static void state_fingerprint(cogaps_session *s, uint64_t *fp)
-{
-    const cogaps_params &p = s->p;
-    uint32_t nVals = 0;
-    if (p.useSparseOptimization) { rt_d2h(&nVals, s->A.d.dptr + s->A.d.M, 4, s->stream); rt_sync(s->stream); }
-    const uint64_t v[] = {
-        (uint64_t)(p.useSparseOptimization != 0), s->nGenes, s->nSamples, s->K, p.seed, p.nIterations, gm_f2u(p.alphaA), gm_f2u(p.alphaP), gm_f2u(p.maxGibbsMassA), gm_f2u(p.maxGibbsMassP),
-        p.outputFrequency, p.snapshotFrequency, (uint64_t)(uint32_t)p.snapshotPhase, (uint64_t)(p.takePumpSamples != 0), (uint64_t)(uint32_t)p.pumpThreshold, (uint64_t)(unsigned char)p.whichMatrixFixed, s->fixedHash,
-        (uint64_t)(uint32_t)p.reductionMode, (uint64_t)(uint32_t)p.mathMode, gm_f2u(s->A.d.lambda), gm_f2u(s->P.d.lambda), gm_f2u(s->A.d.maxGibbsMass), gm_f2u(s->P.d.maxGibbsMass),
-        p.useSparseOptimization ? 0u : gm_f2u(s->A.dataSparsity), p.useSparseOptimization ? 0u : gm_f2u(s->P.dataSparsity), nVals, data_digest(s) };
-    static_assert(sizeof(v) / sizeof(v[0]) == (size_t)FP_N, "one value per name");
-    memcpy(fp, v, sizeof(v));
-}
-// how a differing fingerprint word reads in a message
-static std::string fp_text(int i, uint64_t v)
-{
-    if ((i >= 6 && i <= 9) || (i >= 19 && i <= 24)) { char b[64]; snprintf(b, sizeof(b), "%.9g", (double)f_of((uint32_t)v)); return b; }
-    if (i == 15) return std::string(1, (char)v);
-    if (i == 16 || i == 26) { char b[32]; snprintf(b, sizeof(b), "%016llx", (unsigned long long)v); return b; }
-    return std::to_string(v);
-}
-// host arrays of a state: a save points at the session's own, a load at temporaries of the lengths the file's meta section states
-struct StateHostArrays { uint64_t *fifo; float *snapA[2], *snapP[2], *chisq; uint32_t *histA, *histP; };
-// Every section of the session's state with its size, in file order: the one list a save writes and a load expects.  gs: the samplers'
-// scalars (a save's: just read back; a load's: the file's), which size the atomic domain's sections.
-static std::vector<cgstate::Section> state_sections(cogaps_session *s, uint64_t *fp, StateMeta *meta, GenScalars *gs, const StateHostArrays &ha)
-{
-    std::vector<cgstate::Section> v;
-    auto host = [&](uint32_t id, void *p, uint64_t bytes) { static char none; v.push_back({id, bytes ? p : (void *)&none, nullptr, bytes}); };
-    auto dev = [&](uint32_t id, void *p, uint64_t bytes) { v.push_back({id, nullptr, p, bytes}); };
-    const uint64_t K = s->K, na = (uint64_t)s->nGenes * K, np_ = (uint64_t)s->nSamples * K;
-    host(SEC_FINGERPRINT, fp, (uint64_t)FP_N * 8); host(SEC_META, meta, sizeof(StateMeta));
-    host(SEC_SEEDFIFO, ha.fifo, meta->nSeedFifo * 8);
-    dev(SEC_ASUM, s->Asum, K * s->A.d.Mpad * 4); dev(SEC_ASQ, s->Asq, K * s->A.d.Mpad * 4);
-    dev(SEC_PSUM, s->Psum, K * s->P.d.Mpad * 4); dev(SEC_PSQ, s->Psq, K * s->P.d.Mpad * 4);
-    dev(SEC_PUMP, s->pump, na * 4);
-    host(SEC_SNAP_A_EQ, ha.snapA[0], meta->nSnap[0] * na * 4); host(SEC_SNAP_P_EQ, ha.snapP[0], meta->nSnap[0] * np_ * 4);
-    host(SEC_SNAP_A_SA, ha.snapA[1], meta->nSnap[1] * na * 4); host(SEC_SNAP_P_SA, ha.snapP[1], meta->nSnap[1] * np_ * 4);
-    host(SEC_CHISQ_HIST, ha.chisq, (uint64_t)meta->nHistory * 4); host(SEC_ATOM_HIST_A, ha.histA, (uint64_t)meta->nHistory * 4); host(SEC_ATOM_HIST_P, ha.histP, (uint64_t)meta->nHistory * 4);
-    const char fixed = s->p.whichMatrixFixed;
-    for (int w = 0; w < 2; ++w) {
-        if (!meta->samp[w].present) continue;
-        const SamplerDev &d = (w == 0 ? s->A : s->P).d; const GenScalars &g = gs[w];
-        const uint32_t base = SEC_SAMPLER + 0x100u * (uint32_t)w;
-        host(base + SS_GS, &gs[w], sizeof(GenScalars));
-        dev(base + SS_MAT, d.mat, (uint64_t)d.K * d.Mpad * 4); dev(base + SS_COLPOS, d.colPos, (uint64_t)d.K * 4);
-        dev(base + SS_ATOMS, d.atoms, (uint64_t)g.handleHi * sizeof(AtomRec)); dev(base + SS_VEC, d.vec, (uint64_t)g.nAtoms * 4); dev(base + SS_FREE, d.freeHandles, (uint64_t)g.freeCount * 4);
-        dev(base + SS_BINHEAD, d.binHead, (uint64_t)d.M * d.K * 4);
-        dev(base + SS_BITS0, d.bits0, (uint64_t)d.nWords0 * 8); dev(base + SS_BITS1, d.bits1, (uint64_t)d.nWords1 * 8); dev(base + SS_BITS2, d.bits2, (uint64_t)d.nWords2 * 8);
-        if (d.sparse) {
-            dev(base + SS_ROWS, d.rows, (uint64_t)d.M * d.Kpad * 4); dev(base + SS_MFLAGS, d.mflags, (uint64_t)d.K * d.Mw * 8);
-            dev(base + SS_Z1, d.Z1, (uint64_t)d.K * 4); dev(base + SS_Z2, d.Z2, (uint64_t)d.K * d.K * 4);
-        } else if (w == (fixed == 'P' ? 0 : 1)) dev(base + SS_AP, d.AP, (uint64_t)d.M * d.Npad * 4);
-    }
-    return v;
-}
-// pinned staging buffer of a save or load (not the session's: released before the call returns)
-struct StateStaging { void *p; StateStaging() : p(rt_malloc_host(STATE_STAGING_BYTES)) {} ~StateStaging() { rt_free_host(p); } };
-
-static int state_refusal(cogaps_session *s, const char *path, const char *what)
-{
-    if (!s || !path) return fail("null argument");
-    if (s->poisoned) return fail(std::string("this session was ended by a device error; its state cannot be ") + what);
-    if (s->p.sampler == COGAPS_SAMPLER_SEQUENTIAL) return fail(std::string("a state file holds the asynchronous sampler's chain: the state of a sequential session (sampler = COGAPS_SAMPLER_SEQUENTIAL) cannot be ") + what);
-    return 0;
-}
-
-int cogaps_session_position(cogaps_session *s, int *phase, uint32_t *nextIter)
-{
-    if (!s) return fail("null argument");
-    if (phase) *phase = s->posPhase;
-    if (nextIter) *nextIter = s->posNext;
-    return 0;
-}
-
-int cogaps_session_debug_data_digest(cogaps_session *s, uint64_t *digest)
-{
-    if (!s || !digest) return fail("null argument");
-    SESSION_TRY
-    s->digestValid = false;      // (the hook computes it anew every time)
-    *digest = data_digest(s);
-    SESSION_END
-}
-
-int cogaps_session_save_state(cogaps_session *s, const char *path)
-{
-    if (state_refusal(s, path, "saved")) return 1;
-    SESSION_TRY
-    rt_sync(s->stream);
-    const char fixed = s->p.whichMatrixFixed;
-    StateMeta meta; memset(&meta, 0, sizeof(meta));
-    GenScalars gs[2]; memset(gs, 0, sizeof(gs));
-    HostSampler *hs[2] = {&s->A, &s->P};
-    for (int w = 0; w < 2; ++w) {
-        if (fixed == "AP"[w]) continue;
-        read_gs(s, *hs[w]); gs[w] = *s->hGs;
-        if (gs[w].error) return fail("this session's device state carries an error code; its state cannot be saved");
-        meta.samp[w].present = 1; meta.samp[w].nAtoms = hs[w]->nAtoms; meta.samp[w].avgQueue = hs[w]->avgQueue; meta.samp[w].anneal = hs[w]->anneal;
-    }
-    meta.phase = (uint32_t)s->posPhase; meta.nextIter = s->posNext;
-    meta.seeder0 = s->seeder.s0; meta.seeder1 = s->seeder.s1; meta.runnerRng = s->runnerRng; meta.totalUpdates = s->totalUpdates;
-    meta.samplerSeconds = s->samplerSeconds; meta.elapsedSeconds = now_s() - s->startTime;
-    meta.statUpdates = s->statUpdates; meta.pumpUpdates = s->pumpUpdates; meta.nSnap[0] = s->nSnap[0]; meta.nSnap[1] = s->nSnap[1];
-    meta.nHistory = (uint32_t)s->chisqHist.size(); meta.genScalarsBytes = (uint32_t)sizeof(GenScalars);
-    meta.nSeedFifo = s->seedFifo.size() - s->seedHead;
-    uint64_t fp[FP_N]; state_fingerprint(s, fp);
-    StateHostArrays ha = {s->seedFifo.data() + s->seedHead, {s->snapA[0].data(), s->snapA[1].data()}, {s->snapP[0].data(), s->snapP[1].data()},
-                          s->chisqHist.data(), s->atomHistA.data(), s->atomHistP.data()};
-    const std::vector<cgstate::Section> secs = state_sections(s, fp, &meta, gs, ha);
-    StateStaging staging;
-    cgstate::Writer out(path);
-    out.write(secs, staging.p, STATE_STAGING_BYTES, [&](const cgstate::Section &sec, uint64_t off, size_t n, void *buf) {
-        rt_d2h(buf, (const char *)sec.dev + off, n, s->stream); rt_sync(s->stream); });
-    SESSION_END
-}
-
-int cogaps_session_load_state(cogaps_session *s, const char *path)
-{
-    if (state_refusal(s, path, "replaced")) return 1;
-    if (!s->ownsStream) return fail("this session belongs to a batch: load the state first, then create the batch");
-    SESSION_TRY
-    rt_sync(s->stream);
-    // ---- everything is validated before anything of the session is overwritten ----
-    StateStaging staging;
-    cgstate::Reader in(path, staging.p, STATE_STAGING_BYTES);
-    const std::string name = std::string("state file: ") + path;
-    uint64_t fpFile[FP_N], fpMine[FP_N];
-    const cgstate::TableEntry *e = in.find(SEC_FINGERPRINT);
-    if (!e || e->bytes != sizeof(fpFile)) return fail(name + " is corrupt: it has no fingerprint section of this version's size");
-    in.read(*e, 0, fpFile, sizeof(fpFile));
-    state_fingerprint(s, fpMine);
-    for (int i = 0; i < FP_N; ++i)
-        if (fpFile[i] != fpMine[i]) return fail(name + " does not belong to this session: " + FP_NAMES[i] + " differs (file " + fp_text(i, fpFile[i]) + ", session " + fp_text(i, fpMine[i]) + ")");
-    StateMeta meta;
-    e = in.find(SEC_META);
-    if (!e || e->bytes != sizeof(meta)) return fail(name + " is corrupt: it has no meta section of this version's size");
-    in.read(*e, 0, &meta, sizeof(meta));
-    const char fixed = s->p.whichMatrixFixed;
-    HostSampler *hs[2] = {&s->A, &s->P};
-    GenScalars gs[2]; memset(gs, 0, sizeof(gs));
-    const uint64_t na = (uint64_t)s->nGenes * s->K;
-    bool sane = meta.phase >= 1 && meta.phase <= 3 && meta.genScalarsBytes == sizeof(GenScalars) && meta.nSeedFifo < ((uint64_t)1 << 32)
-                && (na == 0 || (meta.nSnap[0] < ((uint64_t)1 << 40) / na && meta.nSnap[1] < ((uint64_t)1 << 40) / na));
-    for (int w = 0; w < 2 && sane; ++w) {
-        if (meta.samp[w].present != (fixed == "AP"[w] ? 0u : 1u)) { sane = false; break; }
-        if (!meta.samp[w].present) continue;
-        e = in.find(SEC_SAMPLER + 0x100u * (uint32_t)w + SS_GS);
-        if (!e || e->bytes != sizeof(GenScalars)) { sane = false; break; }
-        in.read(*e, 0, &gs[w], sizeof(GenScalars));
-        const GenScalars &g = gs[w];
-        sane = g.error == 0 && g.handleHi < 0x7FFFFFF0u && g.nAtoms <= g.handleHi && g.freeCount <= g.handleHi && g.eraseCount == 0;
-    }
-    if (!sane) return fail(name + " is corrupt: its counters contradict each other or this session");
-    std::vector<uint64_t> fifo(meta.nSeedFifo); std::vector<float> snapA[2], snapP[2], chisq(meta.nHistory); std::vector<uint32_t> histA(meta.nHistory), histP(meta.nHistory);
-    for (int w = 0; w < 2; ++w) { snapA[w].resize((size_t)meta.nSnap[w] * na); snapP[w].resize((size_t)meta.nSnap[w] * s->nSamples * s->K); }
-    StateHostArrays ha = {fifo.data(), {snapA[0].data(), snapA[1].data()}, {snapP[0].data(), snapP[1].data()}, chisq.data(), histA.data(), histP.data()};
-    std::vector<cgstate::Section> secs = state_sections(s, fpFile, &meta, gs, ha);
-    if (secs.size() != in.tab.size()) return fail(name + " holds " + std::to_string(in.tab.size()) + " sections where this session's state has " + std::to_string(secs.size()));
-    for (const cgstate::Section &sec : secs) {
-        e = in.find(sec.id);
-        if (!e || e->bytes != sec.bytes) return fail(name + ": section " + std::to_string(sec.id) + (e ? " has " + std::to_string(e->bytes) + " bytes" : std::string(" is missing")) + " where this session's state has " + std::to_string(sec.bytes) + " bytes");
-    }
-    // capacities are not state: room for the file's atoms first (the session's own atoms move with the arrays)
-    for (int w = 0; w < 2; ++w) if (meta.samp[w].present) grow_atoms(s, *hs[w], gs[w].handleHi);
-    secs = state_sections(s, fpFile, &meta, gs, ha);      // (the same sizes; the arrays may have moved)
-    // ---- from here on the session is overwritten; a failure leaves a state that is no state of any chain ----
-    try {
-        for (const cgstate::Section &sec : secs) {
-            e = in.find(sec.id);
-            if (sec.id == SEC_FINGERPRINT || sec.id == SEC_META || (sec.id >= SEC_SAMPLER && ((sec.id & 0xFFu) == SS_GS))) continue;      // read above
-            if (sec.host) { if (sec.bytes) in.read(*e, 0, sec.host, (size_t)sec.bytes); continue; }
-            for (uint64_t off = 0; off < sec.bytes; ) {
-                const size_t n = (size_t)std::min<uint64_t>(STATE_STAGING_BYTES, sec.bytes - off);
-                in.read(*e, off, staging.p, n);
-                rt_h2d((char *)sec.dev + off, staging.p, n, s->stream); rt_sync(s->stream);      // (the buffer is reused by the next piece)
-                off += n;
-            }
-        }
-        for (int w = 0; w < 2; ++w) {
-            if (!meta.samp[w].present) continue;
-            HostSampler &h = *hs[w]; SamplerDev &d = h.d;
-            gs[w].traceOn = gs[w].traceCount = gs[w].traceCap = gs[w].traceBatchCount = 0;
-            *s->hGs = gs[w];
-            rt_h2d(d.gs, s->hGs, sizeof(GenScalars), s->stream); rt_sync(s->stream);
-            // what a batch of this session left for its own epoch only: cleared, as a fresh session has it
-            rt_memset(d.rowStamp, 0, (size_t)d.M * 8, s->stream); rt_memset(d.atomStamp, 0, (size_t)d.atomCap * 8, s->stream);
-            rt_memset(d.gapStamp, 0, ((size_t)d.atomCap + 1) * 8, s->stream); rt_memset(d.inlineStamp, 0, (size_t)d.atomCap * 8, s->stream);
-            rt_memset(d.atomDest, 0, (size_t)d.atomCap * 8, s->stream);
-            rt_memset(h.chainGrans, 0, (size_t)d.queueCap * CHAIN_GRAN_STRIDE * 8, s->stream); rt_memset(d.grans, 0, (size_t)d.queueCap * 64 * 8, s->stream);
-            h.nAtoms = meta.samp[w].nAtoms; h.avgQueue = meta.samp[w].avgQueue; h.anneal = meta.samp[w].anneal;
-            h.stepsPerBatch = 0.f;      // (the chunk predictor starts over; no result depends on it)
-        }
-        if (!s->p.useSparseOptimization && fixed == 'N') do_sync(s, s->A, s->P);      // A's A*P cache: the transpose of P's
-        rt_sync(s->stream);
-    } catch (...) { s->poisoned = true; throw; }
-    s->seedFifo.swap(fifo); s->seedHead = 0;
-    s->seeder.s0 = meta.seeder0; s->seeder.s1 = meta.seeder1; s->runnerRng = meta.runnerRng; s->totalUpdates = meta.totalUpdates;
-    s->samplerSeconds = meta.samplerSeconds; s->startTime = now_s() - meta.elapsedSeconds;
-    s->statUpdates = meta.statUpdates; s->pumpUpdates = meta.pumpUpdates;
-    for (int w = 0; w < 2; ++w) { s->nSnap[w] = meta.nSnap[w]; s->snapA[w].swap(snapA[w]); s->snapP[w].swap(snapP[w]); }
-    s->chisqHist.swap(chisq); s->atomHistA.swap(histA); s->atomHistP.swap(histP);
-    s->posPhase = (int)meta.phase; s->posNext = meta.nextIter;
-    SESSION_END
-}
+// the library's own state file, at its place among the chapters
+#include "session_state.h"
 
 int cogaps_session_run_to_end(cogaps_session *s, const char *statePath, uint32_t interval, cogaps_result *out)
 {

@@ -2,8 +2,8 @@
 // it once, after everything it takes from there:
 //   fail, fail_exc                    the one home of the library's error message
 //   SpbTemps, SpbMatrix, SpbSide, SpbMap, sparse_args_refusal, spb_compressed, spb_triplets, spb_build_sides
-//                                     the sparse builder's helpers (cogaps_residuals reads the gene side of its packed form)
-//   cogaps_device_matrix              the handle cogaps_residuals takes as data
+//                                     the sparse builder's helpers, of session_build.h (cogaps_residuals reads the gene side of its packed form)
+//   cogaps_device_matrix              the handle cogaps_residuals takes as data, of session_build.h too
 // and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h.
 // The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match.
 #pragma once

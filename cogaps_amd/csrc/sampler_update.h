@@ -1,6 +1,6 @@
 // sampler_update.h -- the update of one sampler of a one-chain session (AsynchronousGibbsSampler::update, SingleThreadedGibbsSampler::update):
 // host code only, a chapter of cogaps_hip.cpp, which includes it once, where the chapter used to stand -- after the kernel headers, by_window,
-// EventPool, GraphCache, HostSampler, cogaps_session, fail, dalloc, dev_env and build_death_prob_table, which it takes from there.  Not a
+// EventPool, GraphCache, HostSampler, cogaps_session, fail, dalloc, dev_env and session_build.h's build_death_prob_table, which it takes from there.  Not a
 // stand-alone header.  Kernels are instantiated, and laid out in the code object, in the order of their first use: one kernel per by_window
 // call, and the LAUNCH_* sites stay in the order they have here.  What chain_batch.h, the second chapter of the drivers, shares with this
 // one is written here once: begin_update / end_update, chunk_size, steps_per_batch, split_geometry / split_per_wave, set_window,

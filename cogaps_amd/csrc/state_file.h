@@ -6,7 +6,7 @@
 //
 // All integers little-endian (the library runs on little-endian hosts only and writes its words as they lie in memory).  The checksum
 // covers everything behind the header -- table, payload, pads -- as 64-bit words.  What the sections mean is the caller's business
-// (cogaps_hip.cpp, the state-file section); this file knows bytes.
+// (session_state.h); this file knows bytes.
 #pragma once
 #include <errno.h>
 #include <stdint.h>
@@ -50,6 +50,12 @@ inline uint64_t hash_bytes(const void *p, size_t bytes)
 // One array of the state: where it lives -- host memory or device memory, never both -- and its size.  The same list describes what a
 // save writes and what a load expects to find.
 struct Section { uint32_t id; void *host; void *dev; uint64_t bytes; };
+// `bytes` bytes in pieces of at most pieceBytes, in order: each(offset, n).  How a device section passes through the staging buffer,
+// whichever way it goes.
+template <class Each> inline void in_pieces(uint64_t bytes, size_t pieceBytes, Each each)
+{
+    for (uint64_t o = 0; o < bytes; ) { const size_t n = (size_t)std::min<uint64_t>(pieceBytes, bytes - o); each(o, n); o += n; }
+}
 
 // Writes path + ".tmp" in the same directory, flushes it to the disk, then renames it over `path`: a save that dies half way leaves the
 // previous file as it was.  `copyOut(section, offset, n, buffer)` fetches n bytes of a device section into the staging buffer.
@@ -78,10 +84,7 @@ struct Writer {
         put(tab.data(), sizeof(TableEntry) * tab.size());
         for (const Section &s : secs) {
             if (s.host) put(s.host, (size_t)(s.bytes & ~(uint64_t)7u));
-            else for (uint64_t o = 0; o < (s.bytes & ~(uint64_t)7u); ) {
-                const size_t n = (size_t)std::min<uint64_t>(stagingBytes, (s.bytes & ~(uint64_t)7u) - o);
-                copyOut(s, o, n, staging); put(staging, n); o += n;
-            }
+            else in_pieces(s.bytes & ~(uint64_t)7u, stagingBytes, [&](uint64_t o, size_t n) { copyOut(s, o, n, staging); put(staging, n); });
             if (const size_t rest = (size_t)(s.bytes & 7u)) {      // the last, partial word with its zero pad
                 uint64_t w = 0;
                 if (s.host) memcpy(&w, (const char *)s.host + (s.bytes - rest), rest); else { copyOut(s, s.bytes - rest, rest, staging); memcpy(&w, staging, rest); }
@@ -123,11 +126,9 @@ struct Reader {
         Checksum sum;
         if (fread(tab.data(), sizeof(TableEntry), tab.size(), f) != tab.size()) fail_io(path);
         sum.feed(tab.data(), sizeof(TableEntry) * tab.size());
-        for (uint64_t left = h.fileBytes - sizeof(Header) - sizeof(TableEntry) * tab.size(); left; ) {
-            const size_t n = (size_t)std::min<uint64_t>(stagingBytes, left);
+        in_pieces(h.fileBytes - sizeof(Header) - sizeof(TableEntry) * tab.size(), stagingBytes, [&](uint64_t, size_t n) {
             if (fread(staging, 1, n, f) != n) fail_io(path);
-            sum.feed(staging, n); left -= n;
-        }
+            sum.feed(staging, n); });
         if (sum.value() != h.checksum) throw std::runtime_error(std::string("state file: ") + path + " is corrupt: its checksum does not match its contents");
         uint64_t off = sizeof(Header) + sizeof(TableEntry) * tab.size();
         for (const TableEntry &e : tab) {      // (behind the checksum this can only be a writer's mistake)
@@ -142,6 +143,11 @@ struct Reader {
     void read(const TableEntry &e, uint64_t offset, void *dst, size_t n)
     {
         if (fseek(f, (long)(e.offset + offset), SEEK_SET) != 0 || fread(dst, 1, n, f) != n) throw std::runtime_error("state file: reading a section failed");
+    }
+    // a device section, the way Writer::write sends one out: `copyIn(section, offset, n, buffer)` takes n bytes from the staging buffer
+    template <class CopyIn> void read_pieces(const TableEntry &e, const Section &s, void *staging, size_t stagingBytes, CopyIn copyIn)
+    {
+        in_pieces(s.bytes, stagingBytes, [&](uint64_t o, size_t n) { read(e, o, staging, n); copyIn(s, o, n, staging); });
     }
 };
 

@@ -1307,3 +1307,15 @@ def test_host_launch_counters_on_the_gpu(hip_lib):
     assert dense == {"A": (222, 222, 163, False), "P": (0, 248, 146, True)}
     assert sparse == {"A": (0, 348, 259, True), "P": (0, 318, 212, True)}
     assert launches == [278, 259] and batches == [[181, 141], [182, 146], [172, 140]] and chained == [[False, True]] * 3
+
+
+def test_session_build_routes_on_the_gpu(hip_lib):
+    """Every input form of both models x transposeData x subsetData (csrc/session_build.h) on the hardware, "device" inputs at real
+    device addresses: the table of tests/test_session_build.py and its constants -- the library before the chapter moved gives them on
+    the MI355X as on the emulator (profiles/session_build_refactor_checks.txt)."""
+    import test_session_build as sb
+    from test_dense_device_input_gpu import dd
+    got = {sb.case_id(case): sb.measure(hip_lib, case, dd) for case in sb.cases()}
+    want = {sb.case_id(case): sb.expected(case) for case in sb.cases()}
+    print(got)
+    assert got == want
