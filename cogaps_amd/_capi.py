@@ -106,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_gene_set_membership", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_gene_set_membership", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match", "cogaps_manova_sscp",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -240,6 +240,7 @@ def bind(L):
                                    u32p, C.c_uint32, C.c_int, dp, dp, dp, dp, u64p]
     L.cogaps_pattern_match.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                        u32p, u32p, dp, fp, dp, u32p]
+    L.cogaps_manova_sscp.argtypes = [fp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -1061,6 +1062,25 @@ def gene_set_membership(z, members, wMember, wNull=None, device=-1, stat=True, c
         if out[k] is not None:
             out[k] = out[k][:int(off[-1])]
     out["offsets"] = off.astype(np.int64)
+    return out
+
+
+def manova_sscp(x, y, device=-1, lib=None):
+    """cogaps_manova_sscp: the column means and the centred sums of squares and cross-products of x (n x K, float32) and y (n x p,
+    float64, p <= 8), any strides: a column-major array or a slice goes in as it is.
+    -> {"xMean" [K], "yMean" [p], "sxx" [K], "sxy" [K][p], "syy" [p][p]}, float64"""
+    L = lib if lib is not None else load()
+    x, y = _strided(x, np.float32, "x must be a matrix"), _strided(y, np.float64, "y must be a matrix")
+    x, y = [np.array(m, order="C") if any(st == 0 and d > 1 for st, d in zip(m.strides, m.shape)) else m for m in (x, y)]      # (a broadcast view)
+    sx, sy = [[st // m.itemsize if d > 1 else 1 for st, d in zip(m.strides, m.shape)] for m in (x, y)]      # (numpy's stride of an axis of one element means nothing)
+    if x.shape[0] != y.shape[0]:
+        raise ValueError("x has %d rows, y %d" % (x.shape[0], y.shape[0]))
+    (n, K), p = x.shape, y.shape[1]
+    out = {"xMean": np.zeros(K), "yMean": np.zeros(p), "sxx": np.zeros(K), "sxy": np.zeros((K, p)), "syy": np.zeros((p, p))}
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    if L.cogaps_manova_sscp(x.ctypes.data_as(fp), n, K, sx[0], sx[1], y.ctypes.data_as(dp), p, sy[0], sy[1],
+                            int(device), *[out[k].ctypes.data_as(dp) for k in ("xMean", "yMean", "sxx", "sxy", "syy")]):
+        raise _error(L)
     return out
 
 

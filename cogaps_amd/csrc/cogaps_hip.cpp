@@ -26,6 +26,7 @@
 #include "gsea_kernel.h"
 #include "residual_kernel.h"
 #include "consensus_kernel.h"
+#include "manova_kernel.h"
 
 #include <math.h>
 #include <cmath>

@@ -1,11 +1,11 @@
-// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.13): host code only, a chapter of cogaps_hip.cpp, which includes
+// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.14): host code only, a chapter of cogaps_hip.cpp, which includes
 // it once, after everything it takes from there:
 //   fail, fail_exc                    the one home of the library's error message
 //   SpbTemps, SpbMatrix, SpbSide, SpbMap, sparse_args_refusal, spb_compressed, spb_triplets, spb_build_sides
 //                                     the sparse builder's helpers, of session_build.h (cogaps_residuals reads the gene side of its packed form)
 //   cogaps_device_matrix              the handle cogaps_residuals takes as data, of session_build.h too
-// and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h.
-// The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match.
+// and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h, manova_kernel.h.
+// The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match, cogaps_manova_sscp.
 #pragma once
 
 // One call's device and stream, its device memory, and the stream announced for its allocations' fills.  However the call ends they go
@@ -674,6 +674,54 @@ int cogaps_pattern_match(const float *patterns, uint32_t nRows, uint32_t nCols, 
         for (uint32_t j = 0; j < n; ++j) { cluster[j] = 0u; if (corr) corr[j] = (double)NAN; }
         for (uint32_t t = 0; t < s.T; ++t) { cluster[slotCol[t]] = slotCluster[t] + 1u; if (corr) corr[slotCol[t]] = r[t]; }
         *nClusters = nC;
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// MANOVA's sums of squares and cross-products (manova_kernel.h)
+// ------------------------------------------------------------------------------------------------
+int cogaps_manova_sscp(const float *x, uint32_t nRows, uint32_t nCols, size_t xRowStride, size_t xColStride,
+                       const double *y, uint32_t nResp, size_t yRowStride, size_t yColStride, int device,
+                       double *xMean, double *yMean, double *sxx, double *sxy, double *syy)
+{
+    try {
+        const std::string me = "cogaps_manova_sscp: ";
+        if (!x || !y) return fail(me + "null argument");
+        if (!xMean && !yMean && !sxx && !sxy && !syy) return fail(me + "null argument: one of xMean, yMean, sxx, sxy and syy must be given");
+        if (nResp < 1u || nResp > MV_MAX_RESP) return fail(me + std::to_string(nResp) + " response columns are outside 1 .. MV_MAX_RESP = " + std::to_string(MV_MAX_RESP));
+        if (nCols < 1u) return fail(me + "the predictor matrix has no column");
+        if ((uint64_t)nRows < (uint64_t)nResp + 2u) return fail(me + std::to_string(nRows) + " rows are fewer than nResp + 2 = " + std::to_string(nResp + 2u) + ": no residual degree of freedom is left");
+        if (!xRowStride || !xColStride || !yRowStride || !yColStride) return fail(me + "a stride of zero");
+        const uint64_t outs64 = (uint64_t)nCols * (1u + nResp) + (uint64_t)nResp * nResp;
+        if (outs64 >= 0x80000000ull) return fail(me + std::to_string(nCols) + " predictor columns with " + std::to_string(nResp) + " responses are 2^31 sums or more");
+        const uint32_t K = nCols, p = nResp, cols = K + p, outs = (uint32_t)outs64;
+        // X and Y row-major without padding: the caller's own array where it lies so already, else repacked
+        const size_t nx = (size_t)nRows * K, ny = (size_t)nRows * p;
+        std::vector<float> xp;
+        std::vector<double> yp;
+        if (!(xColStride == 1u && xRowStride == K)) { xp.resize(nx); stage_matrix(xp, K, false, x, nRows, K, xRowStride, xColStride); }
+        if (!(yColStride == 1u && yRowStride == p)) { yp.resize(ny); stage_matrix(yp, p, false, y, nRows, p, yRowStride, yColStride); }
+
+        GsScratch g(device);
+        MvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = g.mem.stage(xp.empty() ? x : xp.data(), nx, false, g.st);
+        a.y = g.mem.stage(yp.empty() ? y : yp.data(), ny, false, g.st);
+        a.n = nRows; a.K = K; a.p = p; a.nTrips = (uint32_t)(((uint64_t)nRows + MV_TRIP - 1u) / MV_TRIP);
+        a.part1 = g.get<double>((size_t)a.nTrips * cols); a.mean = g.get<double>(cols);
+        a.part2 = g.get<double>((size_t)a.nTrips * outs); a.out2 = g.get<double>(outs);
+        const uint32_t blocks1 = (cols + 63u) / 64u, blocks2 = (K + 63u) / 64u + 1u;      // blocks of 64 columns; pass 2: X's, and one for syy
+        RT_LAUNCH(mv_sum_kernel, gs_grid(a.nTrips), 64u * (blocks1 < 4u ? blocks1 : 4u), g.st, a);
+        RT_LAUNCH(mv_mean_kernel, (cols + MV_THREADS - 1u) / MV_THREADS, MV_THREADS, g.st, a);
+        RT_LAUNCH(mv_sscp_kernel, gs_grid(a.nTrips), 64u * (blocks2 < 4u ? blocks2 : 4u), g.st, a);
+        RT_LAUNCH(mv_fold_kernel, (outs + MV_THREADS - 1u) / MV_THREADS, MV_THREADS, g.st, a);
+        if (xMean) rt_d2h(xMean, a.mean, (size_t)K * 8, g.st);
+        if (yMean) rt_d2h(yMean, a.mean + K, (size_t)p * 8, g.st);
+        if (sxx) rt_d2h(sxx, a.out2, (size_t)K * 8, g.st);
+        if (sxy) rt_d2h(sxy, a.out2 + K, (size_t)K * p * 8, g.st);
+        if (syy) rt_d2h(syy, a.out2 + K + (size_t)K * p, (size_t)p * p * 8, g.st);
+        rt_sync(g.st);
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

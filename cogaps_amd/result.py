@@ -16,8 +16,11 @@ is a NaN row where fgsea drops it), or the hypergeometric test of every set agai
 computeGeneGSProb -- which genes of a set behave like the set: every gene's pattern-weighted statistic and the share of the genes
 outside the set that exceed each member's, for any number of sets, on the GPU (cogaps_gene_set_membership; DESIGN.md 4.13: the weights
 come from calcCoGAPSStat's counts, floored at 1 / numPerm where R's become infinite; one permutation test serves a set's members and
-its null; fp64 in fixed orders), and toCSV / fromCSV, the eleven files of the reference's export.  plotPatternGeneSet and the plots
-themselves are out of scope."""
+its null; fp64 in fixed orders), and toCSV / fromCSV, the eleven files of the reference's export, and MANOVA -- which patterns separate
+the groups of the samples: manova of the factor-coded annotations on every pattern, from column means and centred sums of squares and
+cross-products computed on the GPU in two passes (cogaps_manova_sscp; DESIGN.md 4.14: numpy's sort order for the levels, NaN for a
+pattern without spread, a ValueError for a residual SSCP that is not positive definite), and the getters getOriginalParameters and
+getVersion.  plotPatternGeneSet and the plots themselves are out of scope."""
 import os
 import re
 import warnings
@@ -78,6 +81,80 @@ def _benjamini_hochberg(p):
         down = ok[np.argsort(-p[ok], kind="stable")]
         out[down] = np.minimum(1.0, np.minimum.accumulate(p[down] * ok.size / np.arange(ok.size, 0, -1)))
     return out
+
+
+_MANOVA_TESTS = ("Pillai", "Wilks", "Hotelling-Lawley", "Roy")
+_MANOVA_PIVOT = 1e-12      # below this a pivot of the unit-diagonal Cholesky factorisation, or 1 - Pillai's trace, counts as zero
+
+
+def _annotation_columns(annotations, columns, n, which):
+    """the used columns of MANOVA's interestedVariables, each a 1-D numpy array of n entries"""
+    if isinstance(columns, (int, np.integer)) and not isinstance(columns, (bool, np.bool_)):
+        columns = (columns,)
+    columns = list(columns)
+    if not 1 <= len(columns) <= 8 or not all(_is_index(c) for c in columns):
+        raise ValueError("columns must name one to eight columns of interestedVariables by their 0-based index")
+    if hasattr(annotations, "iloc") and hasattr(annotations, "columns"):         # a pandas DataFrame
+        shape, take = annotations.shape, lambda c: annotations.iloc[:, c].to_numpy()
+    else:
+        table = annotations if isinstance(annotations, np.ndarray) else np.array([list(r) if hasattr(r, "__iter__") and not isinstance(r, (str, bytes)) else r
+                                                                               for r in annotations], dtype=object)
+        if table.ndim != 2:
+            raise ValueError("interestedVariables must have two dimensions: one row per %s, one column per variable" % ("sample" if which == "sampleFactors" else "gene"))
+        shape, take = table.shape, lambda c: table[:, c]
+    if shape[0] != n:
+        raise ValueError("interestedVariables has %d rows, the %s %d" % (shape[0], which, n))
+    for c in columns:
+        if not 0 <= c < shape[1]:
+            raise ValueError("column %d is outside the %d columns of interestedVariables" % (c, shape[1]))
+    return [take(int(c)) for c in columns]
+
+
+def _is_missing(col):
+    """where a column of annotations holds None, a NaN or pandas' NA / NaT"""
+    if col.dtype.kind in "fc":
+        return np.isnan(col)
+    if col.dtype.kind == "O":
+        return np.array([v is None or (isinstance(v, (float, np.floating)) and v != v) or type(v).__name__ in ("NAType", "NaTType") for v in col], dtype=bool)
+    if col.dtype.kind in "mM":
+        return np.isnat(col)
+    return np.zeros(col.shape[0], dtype=bool)
+
+
+def _factor_codes(col):
+    """unclass(factor(col)): -> (the 1-based index of every value among the sorted distinct values as float64, those values)"""
+    try:
+        levels, inverse = np.unique(col, return_inverse=True)
+    except TypeError:
+        raise ValueError("a column of interestedVariables holds values that do not sort against one another")
+    return (inverse.reshape(-1) + 1).astype(np.float64), levels
+
+
+def _unit_cholesky(S):
+    """S [p][p] symmetric -> (L, rank): C = S scaled to a unit diagonal, C = L L^T row by row; a diagonal entry of S that is not
+    positive, or a pivot below _MANOVA_PIVOT, drops its row and column from the factorisation and from the rank (L is then no factor)"""
+    p = S.shape[0]
+    d = np.diag(S)
+    live = [j for j in range(p) if d[j] > 0]
+    L, kept = np.zeros((p, p)), []
+    for j in live:
+        row = np.zeros(p)
+        for m in kept:
+            acc = S[j, m] / np.sqrt(d[j] * d[m])
+            for q in kept:
+                if q >= m:
+                    break
+                acc = acc - row[q] * L[m, q]
+            row[m] = acc / L[m, m]
+        pivot = 1.0
+        for m in kept:
+            pivot = pivot - row[m] * row[m]
+        if pivot < _MANOVA_PIVOT:
+            continue
+        row[j] = np.sqrt(pivot)
+        L[j] = row
+        kept.append(j)
+    return L, len(kept)
 
 
 class CogapsResult:
@@ -469,6 +546,81 @@ class CogapsResult:
         """R/methods-CogapsResult.R:246-263 without the heatmap: 1 where calcZ() of featureLoadings exceeds threshold, 0 elsewhere"""
         return (self.calcZ() > threshold).astype(np.int8)
 
+    def getOriginalParameters(self):
+        """R/methods-CogapsResult.R getOriginalParameters: the parameters the run was made with (metadata["params"])"""
+        return self.metadata["params"]
+
+    def getVersion(self):
+        """R/methods-CogapsResult.R getVersion: the version string toCSV writes (None for a result that carries none)"""
+        return self.metadata.get("version")
+
+    def MANOVA(self, interestedVariables, columns=(0, 1), test="Pillai", whichMatrix="sampleFactors", verbose=False, lib=None):
+        """R/methods-CogapsResult.R:596-619 with the sums on the GPU: which patterns separate the groups of the samples.  For every
+        pattern k the fit manova(Y ~ x_k) and its summary, where x_k is column k of the chosen matrix and Y holds the factor codes of
+        the `columns` of interestedVariables (R: the first two) taken as numbers.  interestedVariables: one row per sample (per gene
+        for featureLoadings) -- a 2-D numpy array of any dtype, a list of rows or a pandas DataFrame; a used column is coded as
+        unclass(factor(column)) codes it, its sorted distinct values as 1, 2, ... (numpy's sort order); a row with a missing value
+        (None, NaN, pandas NA) in a used column is dropped, as na.omit drops it.  test: "Pillai", "Wilks", "Hotelling-Lawley" or "Roy".
+        -> {"patterns": the labels, "test", "Df": (1, n - 2), "stat", "approxF", "numDf", "denDf", "pvalue": float64 [K],
+        "coefficients": [K][2][p] (intercepts, slopes), "SSCP": {"hypothesis", "residuals"}: [K][p][p], "levels": per used column its
+        distinct values, "nOmitted": the rows dropped}.  A pattern without any spread gives NaN; a residual SSCP that is not positive
+        definite is a ValueError ("residuals have rank ...").  verbose: one summary line per pattern.  DESIGN.md 4.14 has the
+        definition, the order of every sum and every deviation from R."""
+        from . import _capi
+        if test not in _MANOVA_TESTS:
+            raise ValueError("test must be one of %s" % ", ".join("'%s'" % t for t in _MANOVA_TESTS))
+        if whichMatrix not in _WHICH:
+            raise ValueError("whichMatrix must be either 'featureLoadings' or 'sampleFactors'")
+        x = np.asarray(getattr(self, _WHICH[whichMatrix][0]), dtype=np.float32)
+        used = _annotation_columns(interestedVariables, columns, x.shape[0], whichMatrix)
+        missing = np.zeros(x.shape[0], dtype=bool)
+        for col in used:
+            missing |= _is_missing(col)
+        nOmitted, p = int(missing.sum()), len(used)
+        if nOmitted:
+            x, used = x[~missing], [col[~missing] for col in used]
+        n, K = x.shape
+        if n < p + 2:
+            raise ValueError("MANOVA: %d complete rows are fewer than the %d that %d response columns need" % (n, p + 2, p))
+        coded = [_factor_codes(col) for col in used]
+        s = _capi.manova_sscp(x, np.stack([c[0] for c in coded], axis=1), lib=lib)
+        sxx, sxy, syy = s["sxx"], s["sxy"], s["syy"]
+
+        # the p x p algebra, float64 on the host (DESIGN.md 4.14): C = the total SSCP scaled to a unit diagonal, C = L L^T
+        L, rank = _unit_cholesky(syy)
+        if rank < p:
+            raise ValueError("MANOVA: residuals have rank %d < %d" % (rank, p))
+        root = np.sqrt(np.diag(syy))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            v = np.linalg.solve(L, (sxy / root[None, :]).T).T / np.sqrt(sxx)[:, None]      # [K][p]: Pillai's trace is |v|^2
+            V = np.zeros(K)
+            for j in range(p):
+                V = V + v[:, j] * v[:, j]
+            flat = sxx == 0
+            V[flat] = np.nan
+            fitted = (1.0 - V) < _MANOVA_PIVOT
+            if fitted.any():                                                         # the residual SSCP has lost the direction of the fit
+                raise ValueError("MANOVA: residuals have rank %d < %d (pattern %d is a perfect fit)" % (p - 1, p, int(np.flatnonzero(fitted)[0]) + 1))
+            ratio = V / (1.0 - V)
+            F = (n - p - 1) / p * ratio
+            slope = sxy / sxx[:, None]
+            H = sxy[:, :, None] * sxy[:, None, :] / sxx[:, None, None]
+        from scipy.special import betainc
+        num, den = float(p), float(n - p - 1)
+        pvalue = np.full(K, np.nan)
+        ok = ~flat
+        pvalue[ok] = betainc(den / 2.0, num / 2.0, den / (den + num * F[ok]))
+        stat = {"Pillai": V, "Wilks": 1.0 - V, "Hotelling-Lawley": ratio, "Roy": ratio}[test]
+        labels = ["Pattern_%d" % (k + 1) for k in range(K)]
+        out = {"patterns": labels, "test": test, "Df": (1, n - 2), "stat": stat, "approxF": F, "numDf": np.full(K, num), "denDf": np.full(K, den),
+               "pvalue": pvalue, "coefficients": np.stack([s["yMean"][None, :] - slope * s["xMean"][:, None], slope], axis=1),
+               "SSCP": {"hypothesis": H, "residuals": syy[None, :, :] - H}, "levels": [c[1].tolist() for c in coded], "nOmitted": nOmitted}
+        if verbose:
+            for k in range(K):
+                print("%s: Df 1, %s %.5g, approx F %.5g, num Df %d, den Df %d, Pr(>F) %.4g; residuals Df %d" % (
+                    labels[k], test, stat[k], F[k], p, n - p - 1, pvalue[k], n - 2))
+        return out
+
 
 def _csv_value(v):
     if v is None:
@@ -557,6 +709,19 @@ def residuals(result, data, uncertainty=None, genes=None, matrix=True, transpose
 
 def binaryA(result, threshold):
     return result.binaryA(threshold)
+
+
+def getOriginalParameters(object):
+    return object.getOriginalParameters()
+
+
+def getVersion(object):
+    return object.getVersion()
+
+
+def MANOVA(interestedVariables, object, **kw):
+    """the reference's argument order: the annotations first, then the result"""
+    return object.MANOVA(interestedVariables, **kw)
 
 
 def patternMarkers(result, threshold="all", lp=None, axis=1, **kw):

@@ -678,6 +678,30 @@ int cogaps_pattern_match(const float *patterns, uint32_t nRows, uint32_t nCols, 
                          uint32_t cut, uint32_t minNS, uint32_t maxNS, int device,
                          uint32_t *nClusters, uint32_t *cluster, double *corr, float *consensus, double *dist, uint32_t *firstLabels);
 
+/* ------------------------------------------------------------------------------------------------
+ * Result statistics: the sums that the reference's MANOVA stands on (R/methods-CogapsResult.R:596-619) -- the column
+ * means and the centred sums of squares and cross-products of a predictor matrix X (a result's patterns) and a response matrix Y (the
+ * factor codes of the sample annotations).  With one numeric predictor per fit, manova(Y ~ x_k) follows from them for every k.
+ *
+ * x: nRows x nCols floats, element (i, k) at x[i * xRowStride + k * xColStride]; y: nRows x nResp doubles, element (i, j) at
+ * y[i * yRowStride + j * yColStride] (strides in elements: R's column-major matrix and a row-major array both pass as they are).
+ * Both are host pointers, uploaded per call (repacked row-major unless they lie so already).  All arithmetic is fp64 on the exactly
+ * widened floats, in two passes, every product rounded before it is added, and every sum over the rows follows one rule: trips of 256
+ * consecutive rows, a trip's terms added in ascending row order from +0.0, the trips' sums in ascending trip order from +0.0:
+ *   xMean[k] = (sum of column k of x) / nRows          yMean[j] = (sum of column j of y) / nRows
+ *   sxx[k]    = sum over i of dx * dx,    dx = x[i][k] - xMean[k]                        ([nCols])
+ *   sxy[k][j] = sum over i of dx * dy_j,  dy_j = y[i][j] - yMean[j]                      ([nCols][nResp], row-major)
+ *   syy[a][b] = sum over i of dy_a * dy_b                                                ([nResp][nResp], row-major; symmetric bit for bit)
+ * Each output may be NULL, but not all five.  Nothing of size nRows x nCols is allocated on the device beyond the upload of x.  No
+ * output depends on the device, on the grid, on scheduling or on how the columns are shared among waves; each can be recomputed bit for
+ * bit.  device: -1 for the calling thread's current one (it is restored before the call returns).  Refused, with a message: x or y NULL,
+ * all five outputs NULL, nResp outside 1 .. 8, nCols == 0, nRows < nResp + 2 (no residual degree of freedom), a stride of zero,
+ * nCols * (1 + nResp) + nResp * nResp of 2^31 or more.  nCols has no other limit.
+ * ---------------------------------------------------------------------------------------------- */
+int cogaps_manova_sscp(const float *x, uint32_t nRows, uint32_t nCols, size_t xRowStride, size_t xColStride,
+                       const double *y, uint32_t nResp, size_t yRowStride, size_t yColStride, int device,
+                       double *xMean, double *yMean, double *sxx, double *sxy, double *syy);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
