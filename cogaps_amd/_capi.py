@@ -106,7 +106,7 @@ EXPORTS = [
     "cogaps_session_create_from_device_matrix", "cogaps_run_device_matrix",
     "cogaps_run_device", "cogaps_session_debug_dense_data",
     "cogaps_session_position", "cogaps_session_save_state", "cogaps_session_load_state", "cogaps_session_run_to_end", "cogaps_session_debug_data_digest",
-    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_gene_set_membership", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match", "cogaps_manova_sscp",
+    "cogaps_gene_set_stat", "cogaps_debug_permutation_draw", "cogaps_gene_set_membership", "cogaps_pattern_markers", "cogaps_residuals", "cogaps_pattern_gsea", "cogaps_pattern_match", "cogaps_manova_sscp", "cogaps_project",
     "cogaps_session_debug_check_domain", "cogaps_batch_create", "cogaps_batch_destroy", "cogaps_batch_run_iterations", "cogaps_batch_set_timing", "cogaps_batch_perf",
 ]
 
@@ -241,6 +241,8 @@ def bind(L):
     L.cogaps_pattern_match.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                        u32p, u32p, dp, fp, dp, u32p]
     L.cogaps_manova_sscp.argtypes = [fp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, dp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, dp, dp, dp, dp, dp]
+    if hasattr(L, "cogaps_project"):      # (an A/B build of an older source tree lacks it)
+        L.cogaps_project.argtypes = [fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(CogapsResidualDataC), u32p, C.c_int, dp, dp, dp, dp, dp, u64p]
     L.cogaps_batch_create.restype = vp
     L.cogaps_batch_create.argtypes = [C.POINTER(vp), C.c_uint32]
     L.cogaps_batch_destroy.argtypes = [vp]
@@ -1154,18 +1156,8 @@ def pattern_gsea(stat, members, numPerm, seed=0, device=-1, ranks=False, lib=Non
 RESIDUAL_DATA_NONE, RESIDUAL_DATA_DENSE, RESIDUAL_DATA_SPARSE, RESIDUAL_DATA_COO, RESIDUAL_DATA_DEVICE_MATRIX = 0, 1, 2, 3, 4      # COGAPS_RESIDUAL_DATA_*
 
 
-def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=-1, lib=None):
-    """cogaps_residuals: how well A (genes x K) and P (samples x K), float32 with any strides, fit `data`.  data: None (the
-    reconstruction A P^T alone), a dense matrix (numpy, any strides -- a column-major array goes in as it is; a torch tensor or a
-    DeviceDense on the GPU is read where it lies) with an optional `unc` of its shape, or a scipy.sparse matrix, SparseMatrix, CooMatrix
-    or DeviceMatrix (never densified; the default uncertainty only).  rows: 0-based genes whose rows of the residual matrix (of the
-    reconstruction without data) are wanted, any order, repeats allowed.  -> {"matrix": float64 [len(rows)][samples] or None,
-    "geneChiSq", "sampleChiSq": float64 vectors, "chiSq": float (the three are None without data), "peakDeviceBytes": int}"""
-    L = lib if lib is not None else load()
-    A, P = _strided(A, np.float32), _strided(P, np.float32)
-    if A.shape[1] != P.shape[1]:
-        raise ValueError("featureLoadings has %d patterns, sampleFactors %d" % (A.shape[1], P.shape[1]))
-    G, N, K = A.shape[0], P.shape[0], A.shape[1]
+def _residual_data(data, unc, transposeData, device):
+    """the cogaps_residual_data descriptor of any kind of input (None: kind _NONE) -> (descriptor, what must stay alive while it is used, device)"""
     desc, keep = CogapsResidualDataC(), []
     desc.kind, desc.transposeData = RESIDUAL_DATA_NONE, int(bool(transposeData))
     if data is not None:
@@ -1203,8 +1195,25 @@ def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=
             desc.nrow, desc.ncol = d.shape
             desc.dense, desc.uncertainty = d.ctypes.data, None if u is None else u.ctypes.data
             desc.rowStride, desc.colStride = d.strides[0] // 4, d.strides[1] // 4
+        keep.append(data)
     elif unc is not None:
         raise ValueError("an uncertainty matrix without data")
+    return desc, keep, device
+
+
+def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=-1, lib=None):
+    """cogaps_residuals: how well A (genes x K) and P (samples x K), float32 with any strides, fit `data`.  data: None (the
+    reconstruction A P^T alone), a dense matrix (numpy, any strides -- a column-major array goes in as it is; a torch tensor or a
+    DeviceDense on the GPU is read where it lies) with an optional `unc` of its shape, or a scipy.sparse matrix, SparseMatrix, CooMatrix
+    or DeviceMatrix (never densified; the default uncertainty only).  rows: 0-based genes whose rows of the residual matrix (of the
+    reconstruction without data) are wanted, any order, repeats allowed.  -> {"matrix": float64 [len(rows)][samples] or None,
+    "geneChiSq", "sampleChiSq": float64 vectors, "chiSq": float (the three are None without data), "peakDeviceBytes": int}"""
+    L = lib if lib is not None else load()
+    A, P = _strided(A, np.float32), _strided(P, np.float32)
+    if A.shape[1] != P.shape[1]:
+        raise ValueError("featureLoadings has %d patterns, sampleFactors %d" % (A.shape[1], P.shape[1]))
+    G, N, K = A.shape[0], P.shape[0], A.shape[1]
+    desc, keep, device = _residual_data(data, unc, transposeData, device)
     u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
     idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
     n_out = 0 if idx is None else idx.size
@@ -1219,6 +1228,42 @@ def residuals(A, P, data=None, unc=None, rows=None, transposeData=False, device=
         raise _error(L)
     return {"matrix": out, "geneChiSq": gene if have else None, "sampleChiSq": sample if have else None,
             "chiSq": float(chi.value) if have else None, "peakDeviceBytes": int(peak.value)}
+
+
+PROJECT_TRIP, PROJECT_MAX_PATTERNS = 1024, 128       # COGAPS_PROJECT_TRIP, COGAPS_PROJECT_MAX_PATTERNS
+
+
+def project(L, data, rows=None, transposeData=False, device=-1, lib=None):
+    """cogaps_project: every sample of `data` regressed on the loadings L (genes x K, float32, any strides) by least squares
+    (DESIGN.md 4.15).  data: what residuals() takes, without an uncertainty; rows: None (gene i is row i of the data) or, per gene of L,
+    its 0-based row of the data, any order, repeats allowed.  -> {"coef", "cross": float64 [K][samples], "gram": [K][K],
+    "stdevUnscaled": [K], "rss": [samples], "peakDeviceBytes": int}"""
+    lib_ = lib if lib is not None else load()
+    L = _strided(L, np.float32, "the loadings must be a matrix")
+    if any(st == 0 and d > 1 for st, d in zip(L.strides, L.shape)):      # (a broadcast view)
+        L = np.array(L, order="C")
+    n, K = L.shape
+    sl = [st // 4 if d > 1 else 1 for st, d in zip(L.strides, L.shape)]      # (numpy's stride of an axis of one element means nothing)
+    if data is None:
+        raise ValueError("there is no data to project")
+    desc, keep, device = _residual_data(data, None, transposeData, device)
+    if desc.kind == RESIDUAL_DATA_DENSE:
+        S = desc.nrow if transposeData else desc.ncol
+    elif desc.kind == RESIDUAL_DATA_DEVICE_MATRIX:
+        S = data.shape[0 if transposeData else 1]
+    else:
+        S = keep[0].nrow if transposeData else keep[0].ncol
+    idx = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    if idx is not None and idx.size != n:
+        raise ValueError("one data row per gene of the loadings: %d rows for %d genes" % (idx.size, n))
+    out = {"coef": np.zeros((K, S)), "rss": np.zeros(S), "gram": np.zeros((K, K)), "stdevUnscaled": np.zeros(K), "cross": np.zeros((K, S))}
+    peak = C.c_uint64(0)
+    dp = C.POINTER(C.c_double)
+    if lib_.cogaps_project(_fp(L), n, sl[0], sl[1], K, C.byref(desc), None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_uint32)), int(device),
+                           *[out[k].ctypes.data_as(dp) for k in ("coef", "rss", "gram", "stdevUnscaled", "cross")], C.byref(peak)):
+        raise _error(lib_)
+    out["peakDeviceBytes"] = int(peak.value)
+    return out
 
 
 PATTERN_MATCH_MAX_COLS = 4096         # COGAPS_PATTERN_MATCH_MAX_COLS

@@ -27,6 +27,7 @@
 #include "residual_kernel.h"
 #include "consensus_kernel.h"
 #include "manova_kernel.h"
+#include "project_kernel.h"
 
 #include <math.h>
 #include <cmath>

@@ -1,11 +1,11 @@
-// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.14): host code only, a chapter of cogaps_hip.cpp, which includes
+// result_stats.h -- the statistics of a finished run (DESIGN.md 4.8 to 4.15): host code only, a chapter of cogaps_hip.cpp, which includes
 // it once, after everything it takes from there:
 //   fail, fail_exc                    the one home of the library's error message
 //   SpbTemps, SpbMatrix, SpbSide, SpbMap, sparse_args_refusal, spb_compressed, spb_triplets, spb_build_sides
 //                                     the sparse builder's helpers, of session_build.h (cogaps_residuals reads the gene side of its packed form)
 //   cogaps_device_matrix              the handle cogaps_residuals takes as data, of session_build.h too
-// and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h, manova_kernel.h.
-// The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match, cogaps_manova_sscp.
+// and after the kernel headers geneset_kernel.h, genemember_kernel.h, markers_kernel.h, gsea_kernel.h, residual_kernel.h, consensus_kernel.h, manova_kernel.h, project_kernel.h.
+// The entries here: cogaps_gene_set_stat, cogaps_debug_permutation_draw, cogaps_gene_set_membership, cogaps_pattern_markers, cogaps_pattern_gsea, cogaps_residuals, cogaps_pattern_match, cogaps_manova_sscp, cogaps_project.
 #pragma once
 
 // One call's device and stream, its device memory, and the stream announced for its allocations' fills.  However the call ends they go
@@ -415,6 +415,72 @@ static std::string rs_dims(const char *what, uint64_t has, const char *of, uint6
     return std::string("cogaps_residuals: the data has ") + std::to_string(has) + " " + what + ", " + of + " has " + std::to_string(wants) + " rows";
 }
 
+// A data descriptor's matrix as a call sees it: the handle of a device matrix, and its genes and samples (transposeData applied)
+struct RsData { const cogaps_device_matrix *handle = nullptr; uint32_t G = 0, N = 0; };
+// What a descriptor with data (its kind is not _NONE) is refused for, in `me`'s name (empty: nothing); a device matrix decides the device
+static std::string rs_data_refusal(const std::string &me, const cogaps_residual_data *data, int &device, RsData &d)
+{
+    const int kind = data->kind;
+    uint32_t dr = 0, dc = 0;
+    if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
+        if (!data->dense) return me + "null argument: dense";
+        dr = data->nrow; dc = data->ncol;
+    } else if (kind == COGAPS_RESIDUAL_DATA_SPARSE || kind == COGAPS_RESIDUAL_DATA_COO) {
+        const cogaps_sparse_matrix *sp = kind == COGAPS_RESIDUAL_DATA_SPARSE ? data->sparse : nullptr;
+        const cogaps_coo_matrix *coo = kind == COGAPS_RESIDUAL_DATA_COO ? data->coo : nullptr;
+        if (!sp && !coo) return me + "null argument: the matrix";
+        if (const char *refusal = sparse_args_refusal(sp, coo)) return refusal;
+        dr = sp ? sp->nrow : coo->nrow; dc = sp ? sp->ncol : coo->ncol;
+    } else if (kind == COGAPS_RESIDUAL_DATA_DEVICE_MATRIX) {
+        d.handle = data->deviceMatrix;
+        if (!d.handle) return me + "null argument: deviceMatrix";
+        if (device != -1 && device != d.handle->device)
+            return me + "the matrix resides on device " + std::to_string(d.handle->device) + ", the call was given device " + std::to_string(device);
+        device = d.handle->device;
+        dr = d.handle->m.nrow; dc = d.handle->m.ncol;
+    } else return me + "unknown kind of data " + std::to_string(kind);
+    d.G = data->transposeData ? dc : dr; d.N = data->transposeData ? dr : dc;
+    return std::string();
+}
+// The data where the kernels read them.  Dense: the caller's arrays as they lie, from the first element to the last the strides reach
+// (uploaded unless they are on the device), (gene i, sample j) at [i * rowStride + j * colStride].  The sparse kinds: the gene side of
+// the sparse model's packed form, by the one builder; nothing of size genes x samples exists.
+static void rs_stage_data(GsScratch &g, const cogaps_residual_data *data, const RsData &d, int &source, const float *&dense, const float *&unc,
+                          size_t &rowStride, size_t &colStride, SpbSide &sideOut)
+{
+    const int kind = data->kind;
+    const uint32_t G = d.G, N = d.N;
+    if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
+        source = RS_DATA_DENSE;
+        rowStride = data->transposeData ? data->colStride : data->rowStride;
+        colStride = data->transposeData ? data->rowStride : data->colStride;
+        dense = data->dense; unc = data->uncertainty;
+        if (!data->onDevice) {
+            const size_t span = (size_t)(G - 1u) * rowStride + (size_t)(N - 1u) * colStride + 1u;
+            float *dd = g.get<float>(span); rt_h2d(dd, data->dense, span * 4, g.st); dense = dd;
+            if (data->uncertainty) { float *du = g.get<float>(span); rt_h2d(du, data->uncertainty, span * 4, g.st); unc = du; }
+        }
+        return;
+    }
+    SpbMatrix staged; const SpbMatrix *src = &staged;
+    const unsigned cu = rt_compute_units();
+    if (kind == COGAPS_RESIDUAL_DATA_SPARSE) {
+        const cogaps_sparse_matrix &m = *data->sparse;
+        spb_compressed(staged, m, g.st, [&](auto *from, size_t n) { return g.mem.stage(from, n, m.onDevice != 0, g.st); });
+    } else if (kind == COGAPS_RESIDUAL_DATA_COO) {
+        const cogaps_coo_matrix &m = *data->coo;
+        spb_triplets(staged, m, g.get<unsigned long long>((size_t)(m.nnz / 64 + 1)), cu, g.st,
+                     [&](auto *from, size_t n) { return g.mem.stage(from, n, m.onDevice != 0, g.st); });
+    } else src = &d.handle->m;
+    SpbSide side;
+    side.M = G; side.Wn = N / 64u + 1u; side.vals = nullptr;
+    side.swap = (data->transposeData == 0) == src->majorIsRow ? 0u : 1u;      // genes are the data's rows unless transposeData
+    side.flags = g.get<unsigned long long>((size_t)G * side.Wn); side.prefix = g.get<uint32_t>((size_t)G * side.Wn); side.ptr = g.get<uint32_t>((size_t)G + 1u);
+    SpbMap identity; identity.start = identity.list = nullptr; identity.onMajor = 0u;
+    spb_build_sides(*src, identity, false, &side, 1, cu, g.st, [&](int, size_t n) { return g.get<float>(n); });
+    source = RS_DATA_PACKED; sideOut = side;
+}
+
 extern "C" {
 
 int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t aColStride,
@@ -432,31 +498,14 @@ int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t 
             if (rows[x] >= G) return fail("cogaps_residuals: output row " + std::to_string(x) + " asks for gene " + std::to_string(rows[x]) + ", the result has " + std::to_string(G));
         const int kind = data ? data->kind : COGAPS_RESIDUAL_DATA_NONE;
         if (kind == COGAPS_RESIDUAL_DATA_NONE && nRowsOut == 0u) return fail("cogaps_residuals: neither data nor rows: nothing to compute");
-        const cogaps_device_matrix *handle = nullptr;
+        RsData d;
         if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            uint32_t dr = 0, dc = 0;
-            if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
-                if (!data->dense) return fail("cogaps_residuals: null argument: dense");
-                dr = data->nrow; dc = data->ncol;
-            } else if (kind == COGAPS_RESIDUAL_DATA_SPARSE || kind == COGAPS_RESIDUAL_DATA_COO) {
-                const cogaps_sparse_matrix *sp = kind == COGAPS_RESIDUAL_DATA_SPARSE ? data->sparse : nullptr;
-                const cogaps_coo_matrix *coo = kind == COGAPS_RESIDUAL_DATA_COO ? data->coo : nullptr;
-                if (!sp && !coo) return fail("cogaps_residuals: null argument: the matrix");
-                if (const char *refusal = sparse_args_refusal(sp, coo)) return fail(refusal);
-                dr = sp ? sp->nrow : coo->nrow; dc = sp ? sp->ncol : coo->ncol;
-            } else if (kind == COGAPS_RESIDUAL_DATA_DEVICE_MATRIX) {
-                handle = data->deviceMatrix;
-                if (!handle) return fail("cogaps_residuals: null argument: deviceMatrix");
-                if (device != -1 && device != handle->device)
-                    return fail("cogaps_residuals: the matrix resides on device " + std::to_string(handle->device) + ", the call was given device " + std::to_string(device));
-                device = handle->device;
-                dr = handle->m.nrow; dc = handle->m.ncol;
-            } else return fail("cogaps_residuals: unknown kind of data " + std::to_string(kind));
+            const std::string refusal = rs_data_refusal("cogaps_residuals: ", data, device, d);
+            if (!refusal.empty()) return fail(refusal);
             if (kind != COGAPS_RESIDUAL_DATA_DENSE && data->uncertainty)
                 return fail("cogaps_residuals: a sparse matrix takes the default uncertainty only (no uncertainty matrix)");
-            const uint32_t dG = data->transposeData ? dc : dr, dN = data->transposeData ? dr : dc;
-            if (dG != G) return fail(rs_dims("genes", dG, "featureLoadings", G));
-            if (dN != N) return fail(rs_dims("samples", dN, "sampleFactors", N));
+            if (d.G != G) return fail(rs_dims("genes", d.G, "featureLoadings", G));
+            if (d.N != N) return fail(rs_dims("samples", d.N, "sampleFactors", N));
         }
         const uint32_t nSteps = (uint32_t)(((uint64_t)N + 63u) / 64u), nBlocks = (G + (uint32_t)RS_BLOCK - 1u) / (uint32_t)RS_BLOCK;
         const size_t ldp = (size_t)nSteps * 64u;
@@ -480,36 +529,7 @@ int cogaps_residuals(const float *a, uint32_t nGenes, size_t aRowStride, size_t 
         memset(&r, 0, sizeof(r));
         r.G = G; r.N = N; r.K = K; r.nSteps = nSteps; r.ldp = ldp; r.source = RS_DATA_NONE;
         r.a64 = g.up(a64); r.pt64 = g.up(pt64);
-        if (kind == COGAPS_RESIDUAL_DATA_DENSE) {
-            r.source = RS_DATA_DENSE;
-            r.rowStride = data->transposeData ? data->colStride : data->rowStride;
-            r.colStride = data->transposeData ? data->rowStride : data->colStride;
-            r.data = data->dense; r.unc = data->uncertainty;
-            if (!data->onDevice) {      // the caller's arrays as they lie, from the first element to the last the strides reach
-                const size_t span = (size_t)(G - 1u) * r.rowStride + (size_t)(N - 1u) * r.colStride + 1u;
-                float *dd = g.get<float>(span); rt_h2d(dd, data->dense, span * 4, g.st); r.data = dd;
-                if (data->uncertainty) { float *du = g.get<float>(span); rt_h2d(du, data->uncertainty, span * 4, g.st); r.unc = du; }
-            }
-        } else if (kind != COGAPS_RESIDUAL_DATA_NONE) {
-            // the gene side of the sparse model's packed form, by the one builder; nothing of size genes x samples exists
-            SpbMatrix staged; const SpbMatrix *src = &staged;
-            const unsigned cu = rt_compute_units();
-            if (kind == COGAPS_RESIDUAL_DATA_SPARSE) {
-                const cogaps_sparse_matrix &m = *data->sparse;
-                spb_compressed(staged, m, g.st, [&](auto *from, size_t n) { return g.mem.stage(from, n, m.onDevice != 0, g.st); });
-            } else if (kind == COGAPS_RESIDUAL_DATA_COO) {
-                const cogaps_coo_matrix &m = *data->coo;
-                spb_triplets(staged, m, g.get<unsigned long long>((size_t)(m.nnz / 64 + 1)), cu, g.st,
-                             [&](auto *from, size_t n) { return g.mem.stage(from, n, m.onDevice != 0, g.st); });
-            } else src = &handle->m;
-            SpbSide side;
-            side.M = G; side.Wn = N / 64u + 1u; side.vals = nullptr;
-            side.swap = (data->transposeData == 0) == src->majorIsRow ? 0u : 1u;      // genes are the data's rows unless transposeData
-            side.flags = g.get<unsigned long long>((size_t)G * side.Wn); side.prefix = g.get<uint32_t>((size_t)G * side.Wn); side.ptr = g.get<uint32_t>((size_t)G + 1u);
-            SpbMap identity; identity.start = identity.list = nullptr; identity.onMajor = 0u;
-            spb_build_sides(*src, identity, false, &side, 1, cu, g.st, [&](int, size_t n) { return g.get<float>(n); });
-            r.source = RS_DATA_PACKED; r.side = side;
-        }
+        if (kind != COGAPS_RESIDUAL_DATA_NONE) rs_stage_data(g, data, d, r.source, r.data, r.unc, r.rowStride, r.colStride, r.side);
         double *dSample = nullptr, *dChi = nullptr;
         if (kind != COGAPS_RESIDUAL_DATA_NONE) {
             r.geneChiSq = g.get<double>(G); r.partial = g.get<double>((size_t)nBlocks * ldp);
@@ -722,6 +742,78 @@ int cogaps_manova_sscp(const float *x, uint32_t nRows, uint32_t nCols, size_t xR
         if (sxy) rt_d2h(sxy, a.out2 + K, (size_t)K * p * 8, g.st);
         if (syy) rt_d2h(syy, a.out2 + K + (size_t)K * p, (size_t)p * p * 8, g.st);
         rt_sync(g.st);
+        return 0;
+    } catch (const std::exception &e) { return fail_exc(e); }
+}
+
+// ------------------------------------------------------------------------------------------------
+// New data projected onto a result's patterns (project_kernel.h)
+// ------------------------------------------------------------------------------------------------
+int cogaps_project(const float *loadings, uint32_t nGenes, size_t lRowStride, size_t lColStride, uint32_t nPatterns,
+                   const cogaps_residual_data *data, const uint32_t *dataRows, int device,
+                   double *coef, double *rss, double *gram, double *stdevUnscaled, double *cross, uint64_t *peakDeviceBytes)
+{
+    static_assert(COGAPS_PROJECT_TRIP == PJ_TRIP && COGAPS_PROJECT_MAX_PATTERNS == PJ_MAX_PATTERNS, "the header's constants are the kernels'");
+    try {
+        const std::string me = "cogaps_project: ";
+        const uint32_t n = nGenes, K = nPatterns;
+        if (!loadings || !coef) return fail(me + "null argument");
+        if (!data || data->kind == COGAPS_RESIDUAL_DATA_NONE) return fail(me + "null argument: there is no data to project");
+        RsData d;
+        const std::string refusal = rs_data_refusal(me, data, device, d);
+        if (!refusal.empty()) return fail(refusal);
+        if (data->uncertainty) return fail(me + "an uncertainty matrix is not taken: the fit is unweighted");
+        if (d.G == 0u || d.N == 0u) return fail(me + "the data is empty");
+        if (K == 0u) return fail(me + "nPatterns must be at least 1");
+        if (K > PJ_MAX_PATTERNS) return fail(me + std::to_string(K) + " patterns are more than PJ_MAX_PATTERNS = " + std::to_string(PJ_MAX_PATTERNS));
+        if (n <= K) return fail(me + std::to_string(n) + " genes are not more than nPatterns = " + std::to_string(K) + ": no residual degree of freedom is left");
+        if (!dataRows && n != d.G) return fail(me + "the data has " + std::to_string(d.G) + " genes, the loadings have " + std::to_string(n) + " rows (and no dataRows match them)");
+        for (uint32_t i = 0; dataRows && i < n; ++i)
+            if (dataRows[i] >= d.G) return fail(me + "gene " + std::to_string(i) + " asks for row " + std::to_string(dataRows[i]) + ", the data has " + std::to_string(d.G));
+        const uint32_t S = d.N, tri = PJ_TRI(K);
+        // the loadings widened, row-major without padding
+        std::vector<double> l64((size_t)n * K);
+        bool finite = true;
+        stage_matrix(l64, K, false, loadings, n, K, lRowStride, lColStride, [&](float v, size_t, size_t) { if (!std::isfinite(v)) finite = false; return (double)v; });
+        if (!finite) return fail(me + "the loadings hold a NaN or an infinite value");
+
+        rt_alloc_meter meter;                                                // (outlives everything the call allocates)
+        rt_meter_scope metered(&meter);
+        GsScratch g(device);
+        PjArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = n; a.K = K; a.S = S; a.nTrips = (uint32_t)(((uint64_t)n + PJ_TRIP - 1u) / PJ_TRIP); a.nSBlocks = (uint32_t)(((uint64_t)S + PJ_THREADS - 1u) / PJ_THREADS);
+        a.l64 = g.up(l64);
+        if (dataRows) { uint32_t *dr = g.get<uint32_t>(n); rt_h2d(dr, dataRows, (size_t)n * 4, g.st); a.rows = dr; }
+        const float *noUnc = nullptr;
+        rs_stage_data(g, data, d, a.source, a.data, noUnc, a.rowStride, a.colStride, a.side);
+        const size_t nKS = (size_t)K * S;
+        a.gramPart = g.get<double>((size_t)a.nTrips * tri); a.gramTri = g.get<double>(tri); a.gram = g.get<double>((size_t)K * K);
+        a.factor = g.get<double>(tri); a.unit = g.get<double>((size_t)K * K); a.stdev = g.get<double>(K); a.bad = g.get<uint32_t>(1);
+        a.crossPart = g.get<double>((size_t)a.nTrips * nKS); a.cross = g.get<double>(nKS); a.coef = g.get<double>(nKS);
+        if (rss) { a.rssPart = g.get<double>((size_t)a.nTrips * S); a.rss = g.get<double>(S); }
+
+        RT_LAUNCH(pj_gram_kernel, gs_grid(a.nTrips), PJ_THREADS, g.st, a);
+        RT_LAUNCH(pj_gram_fold_kernel, (tri + PJ_THREADS - 1u) / PJ_THREADS, PJ_THREADS, g.st, a);
+        RT_LAUNCH(pj_factor_kernel, 1, PJ_THREADS, g.st, a);
+        uint32_t bad = CG_NONE;
+        rt_d2h(&bad, a.bad, 4, g.st); rt_sync(g.st);
+        if (bad != CG_NONE) return fail(me + "loadings are rank deficient (pattern " + std::to_string(bad) + " adds nothing to the patterns before it)");
+        const unsigned long long units = (unsigned long long)a.nTrips * a.nSBlocks;
+        RT_LAUNCH(pj_cross_kernel, gs_grid(units), PJ_THREADS, g.st, a);
+        RT_LAUNCH(pj_fold_kernel, (uint32_t)((nKS + PJ_THREADS - 1u) / PJ_THREADS), PJ_THREADS, g.st, (const double *)a.crossPart, nKS, a.nTrips, a.cross, a.coef);
+        RT_LAUNCH(pj_solve_kernel, a.nSBlocks, PJ_THREADS, g.st, a);
+        if (rss) {
+            RT_LAUNCH(pj_rss_kernel, gs_grid(units), PJ_THREADS, g.st, a);
+            RT_LAUNCH(pj_fold_kernel, a.nSBlocks, PJ_THREADS, g.st, (const double *)a.rssPart, (size_t)S, a.nTrips, a.rss, (double *)nullptr);
+            rt_d2h(rss, a.rss, (size_t)S * 8, g.st);
+        }
+        rt_d2h(coef, a.coef, nKS * 8, g.st);
+        if (cross) rt_d2h(cross, a.cross, nKS * 8, g.st);
+        if (gram) rt_d2h(gram, a.gram, (size_t)K * K * 8, g.st);
+        if (stdevUnscaled) rt_d2h(stdevUnscaled, a.stdev, (size_t)K * 8, g.st);
+        rt_sync(g.st);
+        if (peakDeviceBytes) *peakDeviceBytes = meter.peak.load();
         return 0;
     } catch (const std::exception &e) { return fail_exc(e); }
 }

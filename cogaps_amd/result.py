@@ -157,6 +157,89 @@ def _unit_cholesky(S):
     return L, len(kept)
 
 
+def _data_input(data, uncertainty, lib):
+    """data (and its uncertainty, or None) as the C layer takes them, under CoGAPS()'s input checks: a path is read (.mtx as triplets,
+    kept sparse), a dense matrix becomes float32, a sparse one takes no uncertainty"""
+    from . import _capi
+    from .api import check_values, warn_small_uncertainty
+    from .io import read_matrix
+    if isinstance(data, str):
+        data = _capi.read_mtx_triplets(data, lib=lib) if data.lower().endswith(".mtx") else read_matrix(data)
+    if isinstance(uncertainty, str):
+        uncertainty = read_matrix(uncertainty)
+    sparse = isinstance(data, (_capi.SparseMatrix, _capi.CooMatrix, _capi.DeviceMatrix)) or _capi.is_sparse(data)
+    if sparse and uncertainty is not None:
+        raise ValueError("a sparse matrix takes no uncertainty matrix: the default uncertainty only")
+    if _capi.is_sparse(data):
+        data = data.astype(np.float32)
+    elif not sparse and not _capi.is_tensor(data):
+        data = np.asarray(data, dtype=np.float32)
+    if uncertainty is not None and not _capi.is_tensor(uncertainty):
+        uncertainty = np.asarray(uncertainty, dtype=np.float32)
+    check_values(data, uncertainty)               # CoGAPS()'s own: NA, negative values ...
+    warn_small_uncertainty(uncertainty)           # ... and the warning for uncertainties below 1e-5
+    return data, uncertainty
+
+
+def _project(loadings, loadingsNames, data, dataNames, NP, full, transposeData, lib):
+    """projectR's lmFit route: the fit on the GPU, sigma, t and the normal tail in float64 on the host"""
+    from . import _capi
+    from scipy.special import erfc
+    L = np.asarray(loadings, dtype=np.float32)
+    if L.ndim != 2:
+        raise ValueError("the loadings must be a matrix (genes x patterns)")
+    labels = ["Pattern_%d" % (k + 1) for k in range(L.shape[1])]
+    if NP is not None:
+        if isinstance(NP, (str, bytes)) or not hasattr(NP, "__iter__"):
+            NP = [NP]
+        flat = [x.item() if isinstance(x, np.generic) else x for x in NP]
+        if not flat:
+            raise ValueError("NP is empty")
+        if all(isinstance(x, str) for x in flat):
+            if any(x not in labels for x in flat):
+                raise ValueError("unknown pattern name: %s" % [x for x in flat if x not in labels][0])
+            cols = [labels.index(x) for x in flat]
+        elif all(_is_index(x) for x in flat):
+            if any(x < 1 or x > L.shape[1] for x in flat):
+                raise ValueError("NP holds an index outside 1 .. %d" % L.shape[1])
+            cols = [int(x) - 1 for x in flat]
+        else:
+            raise ValueError("NP must be all indices or all names")
+        L, labels = L[:, cols], [labels[c] for c in cols]
+    K = L.shape[1]
+    data, _ = _data_input(data, None, lib)
+    nData = int(tuple(data.shape)[1 if transposeData else 0])
+    if dataNames is None:
+        if nData != L.shape[0]:
+            raise ValueError("projectR: the data has %d genes, the loadings have %d: give dataNames to match them by name" % (nData, L.shape[0]))
+        rows, matched = None, (list(loadingsNames) if loadingsNames is not None else list(range(1, L.shape[0] + 1)))
+    else:
+        if loadingsNames is None:
+            raise ValueError("projectR: dataNames are given but the loadings carry no gene names")
+        if len(dataNames) != nData or len(loadingsNames) != L.shape[0]:
+            raise ValueError("projectR: one name per gene: %d names for %d genes of the data, %d for %d of the loadings"
+                             % (len(dataNames), nData, len(loadingsNames), L.shape[0]))
+        first = {}
+        for r, nm in enumerate(dataNames):
+            first.setdefault(nm, r)                   # a duplicated name keeps its first row
+        keep = [i for i, nm in enumerate(loadingsNames) if nm in first]      # the intersection, in the loadings' order
+        if len(keep) < K + 1:
+            raise ValueError("projectR: %d genes matched by name, %d patterns need at least %d" % (len(keep), K, K + 1))
+        L, matched = L[keep], [loadingsNames[i] for i in keep]
+        rows = np.array([first[nm] for nm in matched], dtype=np.uint32)
+    fit = _capi.project(L, data, rows=rows, transposeData=transposeData, lib=lib)
+    df = L.shape[0] - K
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sigma = np.sqrt(fit["rss"] / df)
+        t = fit["coef"] / fit["stdevUnscaled"][:, None] / sigma[None, :]
+        pval = erfc(np.abs(t) / np.sqrt(2.0))
+    out = {"projection": fit["coef"], "pval": pval}
+    if full:
+        out.update({"t": t, "sigma": sigma, "stdevUnscaled": fit["stdevUnscaled"], "df": df, "rss": fit["rss"], "gram": fit["gram"],
+                    "genesMatched": matched, "patterns": labels})
+    return out
+
+
 class CogapsResult:
     def __init__(self, raw, params=None, geneNames=None, sampleNames=None):
         self.featureLoadings = np.asarray(raw["Amean"])      # Amean
@@ -521,26 +604,24 @@ class CogapsResult:
         matrix=False: none.  -> {"residuals": float64 [rows][samples] or None, "geneChiSq", "sampleChiSq", "chiSq", "genes": the
         rows' labels}"""
         from . import _capi
-        from .api import check_values, warn_small_uncertainty
-        from .io import read_matrix
-        if isinstance(data, str):
-            data = _capi.read_mtx_triplets(data, lib=lib) if data.lower().endswith(".mtx") else read_matrix(data)
-        if isinstance(uncertainty, str):
-            uncertainty = read_matrix(uncertainty)
-        sparse = isinstance(data, (_capi.SparseMatrix, _capi.CooMatrix, _capi.DeviceMatrix)) or _capi.is_sparse(data)
-        if sparse and uncertainty is not None:
-            raise ValueError("a sparse matrix takes no uncertainty matrix: the default uncertainty only")
-        if _capi.is_sparse(data):
-            data = data.astype(np.float32)
-        elif not sparse and not _capi.is_tensor(data):
-            data = np.asarray(data, dtype=np.float32)
-        if uncertainty is not None and not _capi.is_tensor(uncertainty):
-            uncertainty = np.asarray(uncertainty, dtype=np.float32)
-        check_values(data, uncertainty)               # CoGAPS()'s own: NA, negative values ...
-        warn_small_uncertainty(uncertainty)           # ... and the warning for uncertainties below 1e-5
+        data, uncertainty = _data_input(data, uncertainty, lib)
         rows, labels = self._gene_rows(genes) if matrix else (None, [])
         out = _capi.residuals(self.featureLoadings, self.sampleFactors, data=data, unc=uncertainty, rows=rows, transposeData=transposeData, lib=lib)
         return {"residuals": out["matrix"], "geneChiSq": out["geneChiSq"], "sampleChiSq": out["sampleChiSq"], "chiSq": out["chiSq"], "genes": labels}
+
+    def projectR(self, data, dataNames=None, NP=None, full=False, transposeData=False, lib=None):
+        """How strongly each pattern shows in other data: projectR(data, loadings = result) by its lmFit route, on the GPU.  Every
+        sample of `data` is regressed on featureLoadings by least squares and every coefficient gets a z-test.  data: whatever
+        residuals() takes -- numpy, torch (one on the GPU stays there), scipy.sparse, DeviceMatrix (neither is densified), a file path
+        -- genes x samples unless transposeData, under CoGAPS()'s input checks.  dataNames: the data's gene names; the genes are then
+        matched with the result's geneNames (the intersection, in the result's order; a duplicated data name keeps its first row;
+        fewer than K + 1 matches are a ValueError).  Without them the data must have the result's genes, matched by position.  NP:
+        1-based pattern indices or names ("Pattern_3") that select the patterns before the fit.  -> {"projection": float64
+        [K][samples], "pval": 2 Phi(-|t|), a normal tail}; full=True adds "t", "sigma" [samples], "stdevUnscaled" [K], "df" = genes -
+        K, "rss" [samples], "gram" [K][K], "genesMatched" (their labels) and "patterns".  A sample with rss == 0 gets t = +-inf and
+        pval = 0 where its coefficient is not zero, and NaN where it is zero.  Collinear or all-zero patterns are refused ("loadings
+        are rank deficient"), as are more than 128.  DESIGN.md 4.15 has the definition, every order and every deviation from projectR."""
+        return _project(self.featureLoadings, self.geneNames, data, dataNames, NP, full, transposeData, lib)
 
     def binaryA(self, threshold):
         """R/methods-CogapsResult.R:246-263 without the heatmap: 1 where calcZ() of featureLoadings exceeds threshold, 0 elsewhere"""
@@ -722,6 +803,16 @@ def getVersion(object):
 def MANOVA(interestedVariables, object, **kw):
     """the reference's argument order: the annotations first, then the result"""
     return object.MANOVA(interestedVariables, **kw)
+
+
+def projectR(data, loadings, dataNames=None, loadingsNames=None, NP=None, full=False, transposeData=False, **kw):
+    """projectR(data, loadings): loadings is a CogapsResult (CogapsResult.projectR) or a plain matrix, genes x patterns, with the
+    loadingsNames of its rows where dataNames are given"""
+    if isinstance(loadings, CogapsResult):
+        if loadingsNames is not None:
+            raise ValueError("projectR: a result carries its own gene names (loadingsNames is for a plain matrix)")
+        return loadings.projectR(data, dataNames=dataNames, NP=NP, full=full, transposeData=transposeData, **kw)
+    return _project(loadings, loadingsNames, data, dataNames, NP, full, transposeData, kw.pop("lib", None), **kw)
 
 
 def patternMarkers(result, threshold="all", lp=None, axis=1, **kw):

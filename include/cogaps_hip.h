@@ -702,6 +702,45 @@ int cogaps_manova_sscp(const float *x, uint32_t nRows, uint32_t nCols, size_t xR
                        const double *y, uint32_t nResp, size_t yRowStride, size_t yColStride, int device,
                        double *xMean, double *yMean, double *sxx, double *sxy, double *syy);
 
+/* ------------------------------------------------------------------------------------------------
+ * New data projected onto a result's patterns: how strongly each pattern shows in each sample of a second data set -- the lmFit route of
+ * projectR(data, loadings = cogapsResult), the companion package of the reference.  Every sample s of the data is
+ * regressed on the loadings by least squares, D[:, s] ~ L c[:, s].
+ *
+ * loadings: L, nGenes x nPatterns floats in host memory, element (i, k) at loadings[i * lRowStride + k * lColStride].  data: D, a
+ * descriptor as cogaps_residuals takes it (every kind but _NONE; no uncertainty: the fit is unweighted), genes x samples unless
+ * transposeData.  dataRows: NULL -- the data has nGenes genes, matched by position -- or nGenes 0-based rows of the data: gene i of the
+ * fit is data row dataRows[i], any order, repeats allowed (another gene set, or the same genes in another order, without a copy).
+ * All arithmetic is fp64 on the exactly widened floats.  Every sum over the genes follows one rule: trips of COGAPS_PROJECT_TRIP
+ * consecutive genes of the fit, a trip's terms added in ascending gene order from +0.0, the trips' sums in ascending trip order from +0.0:
+ *   gram[a][b]  = sum over g of L[g][a] * L[g][b]            cross[k][s] = sum over g of L[g][k] * D[g][s]
+ *                 (products of two widened floats: exact, so fused or not they give the same bits; a zero that a sparse kind never
+ *                 stores adds +-0.0 to a sum that started at +0.0 and changes no bit: the sparse kinds give the dense kind's bits)
+ *   gram = U diag(d) U^T, U unit lower triangular, column by column: w[m] = U[j][m] * d[m]; s = sum over m < j, ascending from +0.0, of
+ *                 U[i][m] * w[m]; d[j] = gram[j][j] - s (i = j); U[i][j] = (gram[i][j] - s) / d[j] (i > j).  d[j] <= 1e-12 * gram[j][j]:
+ *                 "loadings are rank deficient" (an all-zero pattern, collinear patterns)
+ *   x = gram^-1 b: z[i] = b[i] - sum over m < i of U[i][m] * z[m]; y[i] = z[i] / d[i]; x[i] = y[i] - sum over m > i of U[m][i] * x[m], i
+ *                 descending; both sums ascending in m from +0.0
+ *   coef[:, s] = gram^-1 cross[:, s]                         stdevUnscaled[k] = sqrt(x[k]) for b = the unit vector e_k
+ *   rss[s]      = sum over g of r * r, r = D[g][s] - fitted, fitted = sum over k, ascending from +0.0, of L[g][k] * coef[k][s] -- over every
+ *                 position, the zeros of sparse data included
+ * Every product of the factorisation, the substitutions and the fitted value is rounded before it is added (no fused multiply-add).
+ * No output depends on the device, on the grid or on scheduling; each can be recomputed bit for bit.
+ *
+ * Outputs: coef and cross [nPatterns][nSamples], gram [nPatterns][nPatterns] (symmetric bit for bit), stdevUnscaled [nPatterns], rss
+ * [nSamples]; all but coef may be NULL (without rss its pass is not run).  peakDeviceBytes (may be NULL): as for cogaps_residuals; a
+ * sparse kind allocates nothing of the size genes x samples.  device: -1 for the calling thread's current one (it is restored before
+ * the call returns).  Refused, with a message: loadings or coef NULL, no data, what cogaps_residuals refuses of a descriptor, an
+ * uncertainty, empty data, nPatterns == 0 or above COGAPS_PROJECT_MAX_PATTERNS (the factor's packed triangle lives in LDS), nGenes <=
+ * nPatterns, without dataRows a data set of another number of genes, a dataRows entry that is no row of the data, a loading that is not
+ * finite, rank deficiency.
+ * ---------------------------------------------------------------------------------------------- */
+#define COGAPS_PROJECT_TRIP 1024
+#define COGAPS_PROJECT_MAX_PATTERNS 128
+int cogaps_project(const float *loadings, uint32_t nGenes, size_t lRowStride, size_t lColStride, uint32_t nPatterns,
+                   const cogaps_residual_data *data, const uint32_t *dataRows, int device,
+                   double *coef, double *rss, double *gram, double *stdevUnscaled, double *cross, uint64_t *peakDeviceBytes);
+
 /* lanes of the evaluation workgroup for data vectors of length N (the reduction-order contract) */
 uint32_t cogaps_reduction_width(uint32_t N);
 /* threads (= virtual lanes) of the sparse model's evaluation workgroup: one per 64-bit flag word of a data vector, 64..256 */
